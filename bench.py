@@ -26,6 +26,12 @@ Other workloads (DESIGN.md numbers; the driver's bench line is the default):
   --workload fedadam_eager --dtype bf16   the eager FedOPT round on a 16-bit model (bf16 / f16:
                                           every op rounded to the dtype as torch-CPU does)
   --e2e                                   host-resident updates: H2D + kernel + D2H
+
+A plain run sets up, settles, warms up, times ``--steps`` steps and prints the line.  ``--full``
+adds what takes runs of its own: the CPU baseline (the reference's op sequence on host cores), the
+same-device read-ceiling / PCIe probes behind the roofline's measured ceiling, the uncapped HBM
+settle, and the sharded lines' self-check against the host restatement; in a plain run those
+fields are null.  ``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import collections
@@ -125,11 +131,21 @@ def parse():
                          "encodes the whole model (MessageEncoder)")
     ap.add_argument("--e2e-placement", default="slab", choices=["slab", "hbm"],
                     help="eager mode: DeviceUpdateCache placement of the arriving updates")
-    ap.add_argument("--cpu-clients", type=int, default=128, help="cpu_baseline sample size (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the line's own figure: the CPU baseline, the same-device read-ceiling and PCIe "
+                         "probes, the uncapped HBM settle and the sharded lines' self-check against the host "
+                         "restatement (their fields are null in a plain run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as "
+                         "DIR/<name>.npy (float32 / float64; a fixed seeded sample of a tensor beyond the size cap)")
+    ap.add_argument("--cpu-clients", type=int, default=128, help="--full: cpu_baseline sample size (0: skip)")
     ap.add_argument("--cpu-rounds", type=int, default=3)
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch (tools/gpu_prof.sh -> tools/pmc_traffic.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        args.cpu_clients = 0
+    return args
 
 
 def setup_dist(force_group=False):
@@ -360,6 +376,41 @@ def cpu_baseline_hier(rows, P, stale, rnd, rounds):
 
 
 SETTLE = None   # what settle_hbm() saw before the timed region (every bench line reports it)
+FULL = False    # --full (set by main())
+DUMP_CAP_BYTES = 48 << 20   # --dump-outputs: all files together stay under 64 MB
+DUMP_SEED = 20240229
+
+
+def dump_sample_indices(numel, keep, seed=DUMP_SEED):
+    """``keep`` sorted, distinct element indices of a ``numel``-element tensor, the same for every
+    run: one seeded pick out of each of ``keep`` equal strata (so the sample spans the tensor)."""
+    if numel <= keep:
+        return np.arange(numel, dtype=np.int64)
+    lo = np.arange(keep, dtype=np.int64) * numel // keep
+    hi = (np.arange(keep, dtype=np.int64) + 1) * numel // keep
+    u = np.random.default_rng(seed).random(keep)
+    return lo + (u * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(args, rank, outputs):
+    """--dump-outputs DIR: the tensors the timed path handed its caller in the last timed step,
+    as DIR/<name>.npy (rank 0 writes; fp64 stays fp64, every other dtype is widened to fp32).  The
+    size cap is shared equally by the tensors; one beyond its share is sampled at
+    dump_sample_indices(numel, share), fixed by DUMP_SEED -- two builds run with the same
+    arguments write the same elements of the same inputs' results."""
+    if not args.dump_outputs or rank != 0:
+        return
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(outputs))
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        wide = torch.float64 if flat.dtype == torch.float64 else torch.float32
+        keep = share // (8 if wide == torch.float64 else 4)
+        if flat.numel() > keep:
+            flat = flat[torch.as_tensor(dump_sample_indices(flat.numel(), keep), device=flat.device)]
+        np.save(os.path.join(args.dump_outputs, f"{name}.npy"), flat.to(wide).cpu().numpy())
 
 
 def settle_hbm(min_s: float = 7.0, window_s: float = 2.0, every_s: float = 0.25, tol: float = 0.015,
@@ -401,7 +452,8 @@ def settle_hbm(min_s: float = 7.0, window_s: float = 2.0, every_s: float = 0.25,
 def timed(world, steps, warmup, step):
     from flame_amd import engine
     if SETTLE is None and torch.cuda.is_available() and os.environ.get("FLAME_BENCH_SETTLE", "1") != "0":
-        settle_hbm()
+        # a plain run keeps the wait (the figure depends on it) but bounds it: the full wipe, then 3 s at most
+        settle_hbm() if FULL else settle_hbm(max_s=10.0)
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -560,6 +612,7 @@ def bench_feddyn_scaffold(args, world, rank, dev, n, P, client_w, base, counts):
     elapsed, events = timed(world, args.steps, args.warmup, step)
     kname = "flame_feddyn_round" if args.workload == "feddyn" else "flame_agg_reduce"
     ks = kernel_stats(events, kname)
+    dump_outputs(args, rank, {"model": state["weights"]["model"]})
     if rank == 0:
         k_time = ks["avg_s"] * ks["launches"] / args.steps
         k_bytes = ks["bytes_per_launch"] * ks["launches"] / args.steps
@@ -658,6 +711,7 @@ def bench_eager(args, world, rank, dev, n, P, client_w, base, counts, host_row=N
                                                                if defer else "arrivals 3..n: fused, one launch each")}
     elapsed, events = timed(world, args.steps, args.warmup, step)
     ks = kernel_stats(events, kname)
+    dump_outputs(args, rank, {"model": state["weights"]["model"]})
     if rank == 0:
         k_time = ks["avg_s"] * ks["launches"] / args.steps
         k_bytes = ks["bytes_per_launch"] * ks["launches"] / args.steps
@@ -745,6 +799,8 @@ def launcher(world):
 
 def main():
     args = parse()
+    global FULL
+    FULL = args.full
     what, arg = launch_plan(args.gpus, os.environ)
     if what == "error":
         raise SystemExit(arg)
@@ -822,6 +878,7 @@ def main():
     elapsed, events = timed(world, args.steps, args.warmup, step)
     name = "flame_agg_reduce" if args.workload == "fedavg" else "flame_fedopt_reduce_adapt"
     ks = kernel_stats(events, name)
+    dump_outputs(args, rank, {"model": state["weights"]["model"]})
 
     if rank == 0:
         traffic, traffic_source = traffic_lookup(args.traffic, kernel=name, clients=n, params=P, layout=args.layout,
@@ -834,7 +891,7 @@ def main():
                                       args.cpu_rounds)
         # (the kernel's own per-workgroup region too: n x 4 KiB of the tiled slab)
         ceiling, probes = (read_ceiling(slab_buf, regions=(n * 4096,) if args.layout == "slab" and n * 4096 != 1 << 20
-                                        else ()) if world == 1 else (None, {}))
+                                        else ()) if world == 1 and args.full else (None, {}))
         # a piece-pipelined step has several launches: price the step's kernels as one
         launches_per_step = ks["launches"] / args.steps
         k_time = ks["avg_s"] * launches_per_step
@@ -1079,7 +1136,9 @@ def verify_sharded(model: torch.Tensor, idx, expected) -> dict:
 
 
 def _checked(gc) -> None:
-    """A failed self-check fails the run (after the line is printed)."""
+    """A failed self-check fails the run (after the line is printed); None: a plain run made none."""
+    if gc is None:
+        return
     if not gc["ranks_agree"] or any(gc["sample_mismatches_per_rank"]):
         raise SystemExit(f"bench.py: N>1 self-check failed: ranks_agree={gc['ranks_agree']}, "
                          f"sample mismatches per rank {gc['sample_mismatches_per_rank']}")
@@ -1135,16 +1194,19 @@ def bench_sharded(args, world, rank, dev, n, P):
     ks = kernel_stats(events, name)
     attrib = time_attribution(world, ks["avg_s"] * ks["launches"] / args.steps * 1e3 if ks else None,
                               elapsed / args.steps * 1e3, gt)
-    # untimed self-check: every rank holds the same full model, sampled elements == the host
-    idx = sample_indices(plan, "model", seed=args.seed)
-    if fedavg:
-        expected = host_fedavg_rounds(args.seed, counts, idx, rounds[0])
-    else:
-        expected = host_fedopt_rounds(args.workload, engine.fedopt_scalars(inner.beta_1, inner.beta_2, inner.eta,
-                                                                           inner.tau),
-                                      args.seed, counts, idx, rounds[0])
-    gc = verify_sharded(state["weights"]["model"], idx, expected)
-    gc["rounds_checked"] = rounds[0]
+    dump_outputs(args, rank, {"model": state["weights"]["model"]})
+    # untimed self-check (--full): every rank holds the same full model, sampled elements == the host
+    gc = None
+    if args.full:
+        idx = sample_indices(plan, "model", seed=args.seed)
+        if fedavg:
+            expected = host_fedavg_rounds(args.seed, counts, idx, rounds[0])
+        else:
+            expected = host_fedopt_rounds(args.workload, engine.fedopt_scalars(inner.beta_1, inner.beta_2, inner.eta,
+                                                                               inner.tau),
+                                          args.seed, counts, idx, rounds[0])
+        gc = verify_sharded(state["weights"]["model"], idx, expected)
+        gc["rounds_checked"] = rounds[0]
     if rank == 0:
         lps = ks["launches"] / args.steps
         k_time, k_bytes = ks["avg_s"] * lps, ks["bytes_per_launch"] * lps
@@ -1283,10 +1345,13 @@ def bench_hier_sharded(args, world, rank, dev, M, C, P):
     ks = kernel_stats(events, "flame_hier_fedbuff")
     attrib = time_attribution(world, ks["avg_s"] * ks["launches"] / args.steps * 1e3 if ks else None,
                               elapsed / args.steps * 1e3, gt)
-    idx = sample_indices(plan, "model", seed=args.seed)
-    gc = verify_sharded(gw, idx, host_hier_rounds(args.seed + 4, M, C, idx, rounds[0], rnd, fetched,
-                                                  args.hier_mode == "sync"))
-    gc["rounds_checked"] = rounds[0]
+    dump_outputs(args, rank, {"model": gw})
+    gc = None
+    if args.full:
+        idx = sample_indices(plan, "model", seed=args.seed)
+        gc = verify_sharded(gw, idx, host_hier_rounds(args.seed + 4, M, C, idx, rounds[0], rnd, fetched,
+                                                      args.hier_mode == "sync"))
+        gc["rounds_checked"] = rounds[0]
     if rank == 0:
         lps = ks["launches"] / args.steps
         k_time, k_bytes = ks["avg_s"] * lps, ks["bytes_per_launch"] * lps
@@ -1363,6 +1428,7 @@ def bench_fedbuff(args, world, rank, dev):
         opt.scale_add_agg_weights({"model": model}, agg, K)
 
     elapsed, events = timed(world, args.steps, args.warmup, step)
+    dump_outputs(args, rank, {"model": model})
     if rank == 0:
         traffic, traffic_source = traffic_lookup(args.traffic, kernel="flame_hier_fedbuff", workload="fedbuff",
                                                  clients=K, params=P)
@@ -1511,8 +1577,9 @@ def bench_hier(args, world, rank, dev):
     step = {"fused": step_fused, "group": step_group, "serial": step_serial, "sync": step_sync,
             "sync_serial": step_sync_serial}[args.hier_mode]
     elapsed, events = timed(world, args.steps, args.warmup, step)
+    dump_outputs(args, rank, {"model": gw})
     ceiling, probes = None, {}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the same-process read ceiling over the slab, with the kernel's own per-workgroup region
         # (every arrival's tile of one chunk: M x C x 4 KiB) beside the fastest (1 MiB) one
         ceiling, probes = read_ceiling(store.storage[dt], regions=(M * C * 4096,))
@@ -1769,23 +1836,28 @@ def _e2e_shm_sharded_run(args, world, rank, dev, n, P, G, counts, total, sopt, p
         k_ms = ks["avg_s"] * ks["launches"] / args.steps * 1e3 if ks else None
         attrib = time_attribution(world, k_ms, elapsed / args.steps * 1e3, gt)
         per_rank = gather_objects(world, ph)
-        # untimed self-checks: gathered -- every rank holds the same model == the host restatement on
-        # sampled elements; both -- rank 0's egress payload decodes (the trainers' cloudpickle.loads)
+        if args.dump_outputs and rank == 0:     # what the trainers receive: the model in the egress payload
+            import cloudpickle
+            dump_outputs(args, rank, {"model": cloudpickle.loads(bytes(out["payload"]))["weights"]["model"]})
+        # untimed self-checks (--full): gathered -- every rank holds the same model == the host restatement
+        # on sampled elements; both -- rank 0's egress payload decodes (the trainers' cloudpickle.loads)
         # to a model whose every rank's ranges equal that rank's device copy (digests) and whose
         # sampled elements equal the host restatement, bitwise
-        idx = sample_indices(plan, "model", seed=args.seed)
-        expected = host_fedavg_rounds(args.seed, counts, idx, rounds[0])
-        gc = verify_sharded(model, idx, expected) if gathered else {}
-        gc["rounds_checked"] = rounds[0]
-        ec = egress_check(plan, world, rank, model, out.get("payload"), idx, expected)
-        gc.update(ec)
-        if not gathered:      # (for _checked) no rank holds the whole model: the payload is the check
-            gc["ranks_agree"] = ec["egress_range_mismatches"] == 0
-            gc["sample_mismatches_per_rank"] = [ec["egress_sample_mismatches"]] + [0] * (world - 1)
-            gc["sample_parity"] = "bitwise" if ec["egress_payload_bitwise"] else "MISMATCH"
-        elif not ec["egress_payload_bitwise"]:
-            gc["ranks_agree"] = False
-        probe = pcie_probe(dev, world)
+        gc = probe = None
+        if args.full:
+            idx = sample_indices(plan, "model", seed=args.seed)
+            expected = host_fedavg_rounds(args.seed, counts, idx, rounds[0])
+            gc = verify_sharded(model, idx, expected) if gathered else {}
+            gc["rounds_checked"] = rounds[0]
+            ec = egress_check(plan, world, rank, model, out.get("payload"), idx, expected)
+            gc.update(ec)
+            if not gathered:      # (for _checked) no rank holds the whole model: the payload is the check
+                gc["ranks_agree"] = ec["egress_range_mismatches"] == 0
+                gc["sample_mismatches_per_rank"] = [ec["egress_sample_mismatches"]] + [0] * (world - 1)
+                gc["sample_parity"] = "bitwise" if ec["egress_payload_bitwise"] else "MISMATCH"
+            elif not ec["egress_payload_bitwise"]:
+                gc["ranks_agree"] = False
+            probe = pcie_probe(dev, world)
         ref = None
         if rank == 0 and args.cpu_clients > 0:
             ref = e2e_reference_sample(names, sizes, counts, total, G, dev)
@@ -1794,7 +1866,7 @@ def _e2e_shm_sharded_run(args, world, rank, dev, n, P, G, counts, total, sopt, p
             h2d = n * G * 4          # every update's bytes cross PCIe once (each rank its ranges)
             d2h = G * 4              # the model, once, into the egress payload
             achieved = (h2d + d2h) / (ms / 1e3) / 1e9
-            peak = probe["h2d_aggregate_GBps"]
+            peak = probe["h2d_aggregate_GBps"] if probe else None     # the probe is a --full run's
             line = {
                 "metric": "aggregated params/sec, END-TO-END (LIFL shm payloads -> model message in host memory)",
                 "mode": "shm (sharded ingest)", "value": n * G / (ms / 1e3), "unit": "client-params/s",
@@ -1814,7 +1886,7 @@ def _e2e_shm_sharded_run(args, world, rank, dev, n, P, G, counts, total, sopt, p
                              "spec_GBps": PCIE_SPEC_GBS * world, "frac_of_spec": achieved / (PCIE_SPEC_GBS * world),
                              "bytes_per_step": {"h2d": h2d, "d2h": d2h},
                              "per_link_achieved_GBps": h2d / world / (ms / 1e3) / 1e9,
-                             "per_link_peak_GBps": probe["h2d_GBps_by_rank"], **{"probe": probe}},
+                             "per_link_peak_GBps": probe["h2d_GBps_by_rank"] if probe else None, **{"probe": probe}},
                 "phases_ms_by_rank": per_rank,
                 "time_attribution": attrib,
                 "collective": _collective_note(plan, world, 4),
@@ -2064,7 +2136,9 @@ def bench_e2e(args, n, P, dev):
                 seg.close()
                 seg.unlink()
     ks = kernel_stats(events, "flame_agg_reduce")
-    probe = pcie_probe(dev, 1)
+    dump_outputs(args, 0, {"model": out_h})
+    probe = pcie_probe(dev, 1) if args.full else None
+    peak = probe["h2d_aggregate_GBps"] if probe else None
     ms = elapsed / args.steps * 1e3
     # bytes over PCIe per step: every update in (the wire modes: their payloads' tensors), the base
     # model in and the aggregated model out (out_h)
@@ -2076,8 +2150,8 @@ def bench_e2e(args, n, P, dev):
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "clients": n, "params": P, "settle": SETTLE,
         "host_read_GBps": n * P * 4 / (ms / 1e3) / 1e9,
         "kernel_ms_per_step": ks["avg_s"] * ks["launches"] / args.steps * 1e3,
-        "roofline": {"bound": "pcie", "achieved": achieved, "peak": probe["h2d_aggregate_GBps"], "unit": "GB/s",
-                     "frac": achieved / probe["h2d_aggregate_GBps"], "bytes_per_step": {"h2d": h2d, "d2h": d2h},
+        "roofline": {"bound": "pcie", "achieved": achieved, "peak": peak, "unit": "GB/s",
+                     "frac": achieved / peak if peak else None, "bytes_per_step": {"h2d": h2d, "d2h": d2h},
                      "spec_GBps": PCIE_SPEC_GBS, "frac_of_spec": achieved / PCIE_SPEC_GBS,
                      "note": "peak = this process's pinned-copy probe (one SDMA copy); a kernel streaming "
                              "pinned memory, or copies from a registered segment, can read a few % above it",

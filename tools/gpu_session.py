@@ -37,7 +37,7 @@ STEPS = {
                            "tests/test_gpu_fastmath.py", "tests/test_gpu_dtype_matrix.py", "-m", "gpu", "-x", "-q",
                            "--timeout", "200", "--timeout-method", "thread"]),
     "smoke": (300, [PY, "-c", "import __graft_entry__ as g; g.smoke(); print('smoke ok')"]),
-    "bench_default": (300, [PY, "bench.py"]),
+    "bench_default": (300, [PY, "bench.py", "--full", "--full"]),
     "probe": (300, [PY, "tools/fp_probe.py"]),
     "h2d_paths": (200, [PY, "tools/h2d_paths.py", "--offsets", "{offsets}"]),
     "ingest_diag": (300, [PY, "tools/ingest_diag.py"]),
@@ -45,7 +45,7 @@ STEPS = {
     **{f"chain_{v}_{dt}": (400, [PY, "tools/chain_sweep.py", "--variant", f"fed{v}", "--dtype", dt, "--rounds", "6",
                                   "--libs", f"flame_amd/libflame_amd.so,{AB}"])
        for v in ("adam", "yogi", "adagrad") for dt in ("f32", "bf16", "f16")},
-    **{f"eager_{v}": (300, [PY, "bench.py", "--workload", f"fed{v}_eager"]) for v in ("adam", "yogi", "adagrad")},
+    **{f"eager_{v}": (300, [PY, "bench.py", "--full", "--workload", f"fed{v}_eager"]) for v in ("adam", "yogi", "adagrad")},
     # the 16-bit steps' admission (FLAME_T_HALF_ADMIT) against the fp32 step's, one process, bitwise, over
     # enough rounds for stalled weights' m to decay through [2^-133, 2^-85] (bf16)
     **{f"chain_admit_{v}_{dt}": (400, [PY, "tools/chain_sweep.py", "--variant", f"fed{v}", "--dtype", dt, "--rounds",
@@ -86,23 +86,23 @@ STEPS = {
                                       "--dtype", dt, "--rounds", "6", "--libs", "flame_amd/libflame_amd.so"])
        for dt in ("f32", "bf16", "f16")},
     # end-to-end rows, 64 clients x 25M fp32 from host memory back to host memory
-    **{f"e2e_{m}": (400, [PY, "bench.py", "--e2e", "--e2e-mode", m])
+    **{f"e2e_{m}": (400, [PY, "bench.py", "--full", "--e2e", "--e2e-mode", m])
        for m in ("zerocopy", "copy", "pageable", "shm", "shm_reference", "eager", "shard", "shm_shard", "wire",
                  "wire_reference")},
     # the N-GPU end-to-end line rehearsed with gloo ranks sharing the box's one GPU
-    **{f"e2e_shm_gloo{n}{suf}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--gpus", str(n), "--e2e",
+    **{f"e2e_shm_gloo{n}{suf}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--full", "--gpus", str(n), "--e2e",
                                        "--e2e-mode", "shm", "--e2e-egress", eg, "--clients", "{clients}", "--params",
                                        "{params}"])
        for n in (2, 8) for suf, eg in (("", "sharded"), ("_gathered", "gathered"))},
-    **{f"e2e_shm_shard{suf}": (400, [PY, "bench.py", "--e2e", "--e2e-mode", "shm_shard", "--e2e-egress", eg])
+    **{f"e2e_shm_shard{suf}": (400, [PY, "bench.py", "--full", "--e2e", "--e2e-mode", "shm_shard", "--e2e-egress", eg])
        for suf, eg in (("_sharded_egress", "sharded"), ("_gathered", "gathered"))},
-    **{f"sharded_gloo{n}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--gpus", str(n), "--clients",
+    **{f"sharded_gloo{n}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--full", "--gpus", str(n), "--clients",
                                   "{clients}", "--params", "{params}"]) for n in (2, 8)},
-    **{f"hier_gloo{n}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--gpus", str(n), "--workload",
+    **{f"hier_gloo{n}": (600, ["env", "FLAME_BENCH_BACKEND=gloo", PY, "bench.py", "--full", "--gpus", str(n), "--workload",
                                "hier_fedbuff", "--clients", "256", "--params", "{params}"]) for n in (2,)},
-    "force_shard": (300, [PY, "bench.py", "--force-shard"]),
+    "force_shard": (300, [PY, "bench.py", "--full", "--force-shard"]),
     # plain bench lines of the secondary paths (DESIGN §0's second table)
-    **{f"line_{w}": (300, [PY, "bench.py", "--cpu-clients", "0", *a]) for w, a in {
+    **{f"line_{w}": (300, [PY, "bench.py", "--full", "--cpu-clients", "0", *a]) for w, a in {
         "c2": ["--clients", "256", "--params", "1000000", "--steps", "50", "--warmup", "5"],
         "fedavg_eager": ["--workload", "fedavg_eager", "--steps", "10", "--warmup", "3"],
         "scaffold": ["--workload", "scaffold", "--steps", "10", "--warmup", "3"],
@@ -110,7 +110,7 @@ STEPS = {
         "hier_sync": ["--workload", "hier_fedbuff", "--hier-mode", "sync", "--steps", "10", "--warmup", "3"]}.items()},
     # the evidence collection (round 5's gpu_r05_prof.sh): each default path's bench line under
     # rocprofv3 --kernel-trace --stats (the SAME process's kernel summary) ...
-    **{f"prof_{w}": (400, ["rocprof:", PY, "bench.py", *a]) for w, a in {
+    **{f"prof_{w}": (400, ["rocprof:", PY, "bench.py", "--full", *a]) for w, a in {
         "fedavg": ["--steps", "20", "--warmup", "5"],
         "fedadam": ["--workload", "fedadam", "--steps", "10", "--warmup", "3", "--cpu-clients", "16"],
         "fedyogi": ["--workload", "fedyogi", "--steps", "10", "--warmup", "3", "--cpu-clients", "0"],
@@ -122,16 +122,16 @@ STEPS = {
         "fedadagrad_eager": ["--workload", "fedadagrad_eager", "--steps", "10", "--warmup", "3"],
         "feddyn": ["--workload", "feddyn", "--steps", "6", "--warmup", "2", "--cpu-clients", "0"]}.items()},
     # the eager lines at 16-bit dtypes (bench.py --dtype): line + CPU baseline under rocprofv3 stats
-    **{f"prof_{v}_eager_{dt}": (400, ["rocprof:", PY, "bench.py", "--workload", f"fed{v}_eager", "--dtype", dt,
+    **{f"prof_{v}_eager_{dt}": (400, ["rocprof:", PY, "bench.py", "--full", "--workload", f"fed{v}_eager", "--dtype", dt,
                                       "--steps", "10", "--warmup", "3"])
        for v in ("adam", "yogi", "adagrad") for dt in ("bf16", "f16")},
-    **{f"pmc_{v}_eager_{dt}_{c}": (120, ["pmc:", c, "fedopt_chain", PY, "bench.py", "--workload", f"fed{v}_eager",
+    **{f"pmc_{v}_eager_{dt}_{c}": (120, ["pmc:", c, "fedopt_chain", PY, "bench.py", "--full", "--workload", f"fed{v}_eager",
                                          "--dtype", dt, "--steps", "3", "--warmup", "1", "--cpu-clients", "0"])
        for v in ("adam", "yogi", "adagrad") for dt in ("bf16", "f16") for c in ("FETCH_SIZE", "WRITE_SIZE")},
     "prof_chain_bf16": (300, ["rocprof:", PY, "tools/chain_sweep.py", "--variant", "fedadam,fedyogi,fedadagrad",
                               "--dtype", "bf16", "--rounds", "3", "--libs", "flame_amd/libflame_amd.so"]),
     # ... and PMC passes, one counter per run (no trace domains), for the HBM traffic of a kernel
-    **{f"pmc_{w}_{c}": (120, ["pmc:", c, rx, PY, "bench.py", *a, "--steps", "3", "--warmup", "1", "--cpu-clients", "0"])
+    **{f"pmc_{w}_{c}": (120, ["pmc:", c, rx, PY, "bench.py", "--full", *a, "--steps", "3", "--warmup", "1", "--cpu-clients", "0"])
        for w, rx, a in (("fedavg", "agg_reduce", []),
                         ("fedadam_eager", "fedopt_chain", ["--workload", "fedadam_eager"]),
                         ("fedyogi_eager", "fedopt_chain", ["--workload", "fedyogi_eager"]),
