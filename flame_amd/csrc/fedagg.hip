@@ -1365,6 +1365,231 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel(const flame_segmen
                                                  omb2, eta, tau);
 }
 
+// ---------------------------------------------------------------- FedOPT, fp64 keys
+// fedopt.py:102-129 (+ the _delta_v variants) for a key whose base, current, m, v and updates
+// are all fp64.  Bodies of their own: the fp32-typed ones above round into a 16- or 32-bit dtype
+// after every op and pick fp32 fast paths, none of which applies here.  Every torch op is one
+// IEEE fp64 rounding (no fma: -ffp-contract=off), denormals kept; the scalars are the Python
+// floats themselves (torch multiplies an fp64 tensor by a Python scalar in double, so none of
+// them passes through fp32); the root and the quotient are flame_fm::dsqrt_rn / ddiv_rn.  Op for
+// op what ew_kernel's FLAME_F64 arms compute for the same statements, so which of the two a key
+// takes never shows in its bits.
+struct Hyper64 { double b1, omb1, b2, omb2, eta, tau; };
+
+__device__ __forceinline__ double sign_d(double x) {      // torch.sign: NaN -> 0, -0 -> 0
+    return static_cast<double>((0.0 < x) - (x < 0.0));
+}
+
+template <int VARIANT>
+__device__ __forceinline__ void adapt_elem_f64(double avg, double cur, double& m, double& v, double& cur_out,
+                                               const Hyper64& h) {
+    const double d = __dsub_rn(avg, cur);
+    const double mn = __dadd_rn(__dmul_rn(m, h.b1), __dmul_rn(d, h.omb1));
+    const double d2 = __dmul_rn(d, d);
+    double vn;
+    if constexpr (VARIANT == FLAME_FEDADAM) {
+        vn = __dadd_rn(__dmul_rn(v, h.b2), __dmul_rn(d2, h.omb2));
+    } else if constexpr (VARIANT == FLAME_FEDYOGI) {
+        vn = __dsub_rn(v, __dmul_rn(__dmul_rn(d2, h.omb2), sign_d(__dsub_rn(v, d2))));
+    } else {
+        vn = __dadd_rn(v, d2);
+    }
+    m = mn;
+    v = vn;
+    const double den = __dadd_rn(flame_fm::dsqrt_rn(vn), h.tau);
+    cur_out = __dadd_rn(cur, flame_fm::ddiv_rn(__dmul_rn(mn, h.eta), den));
+}
+
+// One chunk of an fp64 FedOPT round (fedopt_chunk's layout: a lane owns one 16-byte vector, two
+// doubles): the clients reduced in order with the fp64 rates (reduce_clients, the arithmetic of
+// agg_reduce_kernel<FLAME_F64>), then the step, then avg (if seg.out), m, v and cur_out stored.
+template <int VARIANT, int CU>
+__device__ __forceinline__ void fedopt_chunk_f64(const flame_segment* __restrict__ segs, int n_segs, int64_t chunk,
+                                                 const uint64_t* __restrict__ clients, int n_clients,
+                                                 const double* __restrict__ r64, unsigned flags, const Hyper64& h) {
+    constexpr int DT = FLAME_F64;
+    constexpr int EPT = Tr<DT>::EPT;
+    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const int64_t coff = client_offset<DT>(sg, chunk);
+    const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
+    const bool cur_avg = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;   // cur IS the FedAvg result
+    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    double acc[kVPT][EPT];
+    const double* base = reinterpret_cast<const double*>(sg.in) + e0;
+    const double* curp = reinterpret_cast<const double*>(sg.cur) + e0;
+    double* mp = reinterpret_cast<double*>(sg.m) + e0;
+    double* vp = reinterpret_cast<double*>(sg.v) + e0;
+    double* ap = sg.out ? reinterpret_cast<double*>(sg.out) + e0 : nullptr;
+    double* cop = reinterpret_cast<double*>(sg.cur_out) + e0;
+    if (vec) {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) unpack<double, EPT>(ld_v(base + v * VS), acc[v]);
+        reduce_clients<DT, CU, true>(acc, false, cp, n_clients, nullptr, r64, e0, sg.numel, coff);
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) {
+            double c[EPT], m[EPT], vv[EPT], co[EPT];
+            if (!cur_avg) unpack<double, EPT>(ld_v(curp + v * VS), c);
+            if (!zero_state) {
+                unpack<double, EPT>(ld_v(mp + v * VS), m);
+                unpack<double, EPT>(ld_v(vp + v * VS), vv);
+            }
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) {
+                if (cur_avg) c[j] = acc[v][j];
+                if (zero_state) m[j] = vv[j] = 0.0;
+                adapt_elem_f64<VARIANT>(acc[v][j], c[j], m[j], vv[j], co[j], h);
+            }
+            if (ap) st_v(ap + v * VS, pack<double, EPT>(acc[v]));
+            st_v(mp + v * VS, pack<double, EPT>(m));
+            st_v(vp + v * VS, pack<double, EPT>(vv));
+            st_v(cop + v * VS, pack<double, EPT>(co));
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) acc[v][j] = (e0 + v * VS + j < sg.numel) ? ld1(base + v * VS + j) : 0.0;
+        reduce_clients<DT, 1, false>(acc, false, cp, n_clients, nullptr, r64, e0, sg.numel, coff);
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) {
+                const int64_t o = v * VS + j;
+                if (e0 + o >= sg.numel) continue;
+                double mj = zero_state ? 0.0 : ld1(mp + o), vj = zero_state ? 0.0 : ld1(vp + o), cj;
+                adapt_elem_f64<VARIANT>(acc[v][j], cur_avg ? acc[v][j] : ld1(curp + o), mj, vj, cj, h);
+                if (ap) st1(ap + o, acc[v][j]);
+                st1(mp + o, mj);
+                st1(vp + o, vj);
+                st1(cop + o, cj);
+            }
+    }
+}
+
+template <int VARIANT, int CU>
+__global__ __launch_bounds__(kBlock) void fedopt_kernel_f64(const flame_segment* __restrict__ segs, int n_segs,
+                                                            const uint64_t* __restrict__ clients, int n_clients,
+                                                            const double* __restrict__ r64, unsigned flags,
+                                                            const Hyper64 h, int64_t n_chunks) {
+    const int64_t chunk = (flags & FLAME_OPT_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (chunk >= n_chunks) return;
+    fedopt_chunk_f64<VARIANT, CU>(segs, n_segs, chunk, clients, n_clients, r64, flags, h);
+}
+
+// fedopt_chain_body for an fp64 model: per arrival base = base + round(w_i * r_i) with the fp64
+// rate, the step of adapt_elem_f64 wherever a do() call closes.  What stays in registers between
+// steps is what the per-call launches would store and reload (every op rounds to fp64).
+template <int VARIANT, int CU, bool VEC>
+__device__ __forceinline__ void fedopt_chain_body_f64(const flame_segment& sg, int64_t e0,
+                                                      const uint64_t* __restrict__ cp, int64_t coff, int n_clients,
+                                                      const double* __restrict__ r64,
+                                                      const uint8_t* __restrict__ step_end, unsigned flags,
+                                                      const Hyper64& h) {
+    using X = Tr<FLAME_F64>;
+    constexpr int EPT = X::EPT;
+    const int nv = VEC ? EPT : static_cast<int>(sg.numel - e0 < EPT ? sg.numel - e0 : EPT);
+    bool aliased = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;
+    const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
+    const double* bp = reinterpret_cast<const double*>(sg.in) + e0;
+    const double* curp = reinterpret_cast<const double*>(sg.cur) + e0;
+    double* mp = reinterpret_cast<double*>(sg.m) + e0;
+    double* vp = reinterpret_cast<double*>(sg.v) + e0;
+    auto load = [&](const double* p, double (&x)[EPT], bool nt) {
+        if constexpr (VEC) {
+            unpack<double, EPT>(nt ? ld_nt(p) : ld_v(p), x);
+        } else {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) x[j] = j < nv ? ld1(p + j) : 0.0;
+        }
+    };
+    auto store = [&](double* p, const double (&x)[EPT]) {
+        if constexpr (VEC) {
+            st_v(p, pack<double, EPT>(x));
+        } else {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                if (j < nv) st1(p + j, x[j]);
+        }
+    };
+    double b[EPT], c[EPT] = {}, m[EPT] = {}, v[EPT] = {};
+    load(bp, b, false);
+    if (!aliased) load(curp, c, false);
+    if (!zero_state) {
+        load(mp, m, false);
+        load(vp, v, false);
+    }
+    auto load_client = [&](int i, double (&x)[EPT]) {
+        load(reinterpret_cast<const double*>(reinterpret_cast<const char*>(cp[i]) + coff), x, true);
+    };
+    auto arrive = [&](const double (&x)[EPT], double r, bool ends) {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) b[j] = X::add(b[j], X::tmp(x[j], 0.f, r));
+        if (ends) {     // uniform: one do() call ends here
+            if (__builtin_expect(aliased, 0)) {   // the first step after the passthrough: current IS base
+#pragma unroll
+                for (int j = 0; j < EPT; ++j) c[j] = b[j];
+                aliased = false;
+            }
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) adapt_elem_f64<VARIANT>(b[j], c[j], m[j], v[j], c[j], h);
+        }
+    };
+    int i = 0;
+    for (; i + CU <= n_clients; i += CU) {
+        double x[CU][EPT], rr[CU];
+        bool ends[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) load_client(i + u, x[u]);
+#pragma unroll
+        for (int u = 0; u < CU; ++u) {     // the batch's scalar loads issued together, one wait
+            rr[u] = r64[i + u];
+            ends[u] = step_ends(step_end, i + u);
+        }
+#pragma unroll
+        for (int u = 0; u < CU; ++u) arrive(x[u], rr[u], ends[u]);
+    }
+    for (; i < n_clients; ++i) {
+        double x[EPT];
+        load_client(i, x);
+        arrive(x, r64[i], step_ends(step_end, i));
+    }
+    if (aliased) {             // no step closed: current is still the base
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) c[j] = b[j];
+    }
+    store(reinterpret_cast<double*>(sg.out) + e0, b);
+    store(mp, m);
+    store(vp, v);
+    store(reinterpret_cast<double*>(sg.cur_out) + e0, c);
+}
+
+template <int VARIANT, int CU>
+__global__ __launch_bounds__(kBlock) void fedopt_chain_kernel_f64(const flame_segment* __restrict__ segs, int n_segs,
+                                                                  const uint64_t* __restrict__ clients,
+                                                                  int n_clients, const double* __restrict__ r64,
+                                                                  const uint8_t* __restrict__ step_end,
+                                                                  unsigned flags, const Hyper64 h) {
+    constexpr int DT = FLAME_F64;
+    static_assert(kVPT == 1, "fedopt_chain_kernel_f64: a lane handles one 16-byte vector of its chunk");
+    const int64_t chunk = blockIdx.x;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t c0 = (chunk - sg.chunk_begin) * chunk_elems<DT>();
+    const int64_t e0 = c0 + static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
+    if (e0 >= sg.numel) return;
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const int64_t coff = client_offset<DT>(sg, chunk);
+    if (c0 + chunk_elems<DT>() <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED))   // workgroup-uniform
+        fedopt_chain_body_f64<VARIANT, CU, true>(sg, e0, cp, coff, n_clients, r64, step_end, flags, h);
+    else
+        fedopt_chain_body_f64<VARIANT, 1, false>(sg, e0, cp, coff, n_clients, r64, step_end, flags, h);
+}
+
 // ---------------------------------------------------------------- FedBuff scale-add (+delta)
 template <int DT> struct SA;
 template <> struct SA<FLAME_F32> {
@@ -2133,7 +2358,9 @@ enum : int {
     BR_AGG_LOB = 89,        // + dt (f32, bf16, f16): flame_agg_reduce, low residency, LDS-held output bursts
     BR_EW = 92,             // flame_elementwise
     BR_EW_SEG = 93,         // flame_elementwise_segments
-    BR_COUNT = 94
+    BR_OPT_F64 = 94,        // + variant: flame_fedopt_reduce_adapt_f64 (appended: BR_OPT + dt * 3 would run into BR_OPT_MULTI)
+    BR_CHAIN_F64 = 97,      // + variant: flame_fedopt_chain_f64
+    BR_COUNT = 100
 };
 std::atomic<long long> g_launches[BR_COUNT];
 
@@ -2164,7 +2391,9 @@ const char* branch_name(int i) {
             else if (b < BR_AGG_LOB) snprintf(n, z, "flame_fedopt_chain/%s/%s", dts[(b - BR_CHAIN) / 3], var[(b - BR_CHAIN) % 3]);
             else if (b < BR_EW) snprintf(n, z, "flame_agg_reduce/lo_burst/%s", dts[b - BR_AGG_LOB]);
             else if (b < BR_EW_SEG) snprintf(n, z, "flame_elementwise");
-            else snprintf(n, z, "flame_elementwise_segments");
+            else if (b < BR_OPT_F64) snprintf(n, z, "flame_elementwise_segments");
+            else if (b < BR_CHAIN_F64) snprintf(n, z, "flame_fedopt_reduce_adapt/f64/%s", var[b - BR_OPT_F64]);
+            else snprintf(n, z, "flame_fedopt_chain/f64/%s", var[b - BR_CHAIN_F64]);
         }
         return true;
     }();
@@ -2405,6 +2634,57 @@ int flame_fedopt_chain(int dtype, int variant, unsigned flags, const flame_segme
 #undef FLAME_CHAIN_VARIANTS
 #undef FLAME_CHAIN_LAUNCH
     return launched(BR_CHAIN + dtype * 3 + variant, "flame_fedopt_chain");
+}
+
+int flame_fedopt_reduce_adapt_f64(int variant, unsigned flags, const flame_segment* segs, int32_t n_segs,
+                                  int64_t n_chunks, const void* const* clients, int32_t n_clients,
+                                  const double* rates64, double b1, double omb1, double b2, double omb2, double eta,
+                                  double tau, void* stream) {
+    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
+    if (rc) return rc;
+    if (n_clients > 0 && !rates64) return set_err(FLAME_EINVAL, "rate array is NULL");
+    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
+        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt_f64: unknown variant %d", variant);
+    if (flags & ~(FLAME_OPT_STATE_ZERO | FLAME_OPT_XCD_MAP))
+        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_f64: unknown flags 0x%x", flags);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    auto cl = reinterpret_cast<const uint64_t*>(clients);
+    const Hyper64 h{b1, omb1, b2, omb2, eta, tau};
+#define FLAME_OPT64_LAUNCH(V)                                                                                   \
+    hipLaunchKernelGGL((fedopt_kernel_f64<V, kClientUnroll>), grid, block, 0, st, segs, n_segs, cl, n_clients,  \
+                       rates64, flags, h, n_chunks)
+    if (variant == FLAME_FEDADAM) FLAME_OPT64_LAUNCH(FLAME_FEDADAM);
+    else if (variant == FLAME_FEDYOGI) FLAME_OPT64_LAUNCH(FLAME_FEDYOGI);
+    else FLAME_OPT64_LAUNCH(FLAME_FEDADAGRAD);
+#undef FLAME_OPT64_LAUNCH
+    return launched(BR_OPT_F64 + variant, "flame_fedopt_reduce_adapt_f64");
+}
+
+int flame_fedopt_chain_f64(int variant, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                           const void* const* clients, int32_t n_clients, const double* rates64,
+                           const uint8_t* step_end, double b1, double omb1, double b2, double omb2, double eta,
+                           double tau, void* stream) {
+    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
+    if (rc) return rc;
+    if (n_clients < 1 || !rates64 || !step_end)
+        return set_err(FLAME_EINVAL, "flame_fedopt_chain_f64: needs >= 1 client, a rate array and a step_end array");
+    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
+        return set_err(FLAME_ENOTSUP, "flame_fedopt_chain_f64: unknown variant %d", variant);
+    if (flags & ~FLAME_OPT_STATE_ZERO)
+        return set_err(FLAME_EINVAL, "flame_fedopt_chain_f64: unknown flags 0x%x", flags);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    auto cl = reinterpret_cast<const uint64_t*>(clients);
+    const Hyper64 h{b1, omb1, b2, omb2, eta, tau};
+#define FLAME_CHAIN64_LAUNCH(V)                                                                                     \
+    hipLaunchKernelGGL((fedopt_chain_kernel_f64<V, kClientUnroll>), grid, block, 0, st, segs, n_segs, cl, n_clients, \
+                       rates64, step_end, flags, h)
+    if (variant == FLAME_FEDADAM) FLAME_CHAIN64_LAUNCH(FLAME_FEDADAM);
+    else if (variant == FLAME_FEDYOGI) FLAME_CHAIN64_LAUNCH(FLAME_FEDYOGI);
+    else FLAME_CHAIN64_LAUNCH(FLAME_FEDADAGRAD);
+#undef FLAME_CHAIN64_LAUNCH
+    return launched(BR_CHAIN_F64 + variant, "flame_fedopt_chain_f64");
 }
 
 int flame_fedopt_reduce_adapt_argmeta(int dtype, int variant, unsigned flags, const void* host_meta,

@@ -1,6 +1,8 @@
 """The reference's torch statements for the keys the fused kernels do not take -- int buffers
-(``num_batches_tracked``), mixed-dtype keys, fp64 / int8 / uint8 / int16 tensors -- run as
-``flame_elementwise`` programs (include/flame_amd.h) instead of PyTorch ops.
+(``num_batches_tracked``), mixed-dtype keys, int8 / uint8 / int16 tensors, fp64 keys whose
+state or updates have another dtype -- run as ``flame_elementwise`` programs
+(include/flame_amd.h) instead of PyTorch ops.  (An all-fp64 FedOPT key has a compiled kernel of
+its own, ``flame_fedopt_reduce_adapt_f64``, which computes the same bits.)
 
 A :class:`Lazy` tensor records the statement it is built by (``a - c``, ``beta * m + x``,
 ``torch.sqrt(v) + tau``, ``torch.sign(...)``, ``torch.zeros_like(d)``, ``.to(dtype)``); the

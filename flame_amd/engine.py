@@ -465,8 +465,9 @@ def fedopt_reduce_adapt_(variant: str, avg_out: List[Optional[torch.Tensor]], ba
                          cur: List[torch.Tensor], cur_out: List[torch.Tensor], m: List[torch.Tensor],
                          v: List[torch.Tensor], clients: List[List[torch.Tensor]], rates: Sequence[float],
                          hyper, state_zero: bool, cur_is_avg: Optional[Sequence[bool]] = None) -> None:
-    """Fused FedAvg + FedOPT step (kernel: flame_fedopt_reduce_adapt), one launch per dtype
-    (fp32 / bf16 / fp16; every tensor of a segment shares its dtype).  ``cur_is_avg[s]``:
+    """Fused FedAvg + FedOPT step (kernel: flame_fedopt_reduce_adapt, for fp64
+    flame_fedopt_reduce_adapt_f64 with fp64 rates and ``hyper.raw``), one launch per dtype
+    (fp32 / bf16 / fp16 / fp64; every tensor of a segment shares its dtype).  ``cur_is_avg[s]``:
     segment s's current weights ARE its FedAvg result (FLAME_SEG_CUR_IS_AVG: the caller's
     current aliases base, so d = avg - avg); ``cur[s]`` is then not read."""
     if not base:
@@ -476,6 +477,7 @@ def fedopt_reduce_adapt_(variant: str, avg_out: List[Optional[torch.Tensor]], ba
     groups = collections.OrderedDict()
     for s_, b in enumerate(base):
         groups.setdefault(dtype_code(b.dtype), []).append(s_)
+    h64 = _scalars64(hyper) if N.FLAME_F64 in groups else None
     for code, idx in groups.items():
         segs, keep = [], []
         p_alias = 0
@@ -497,6 +499,18 @@ def fedopt_reduce_adapt_(variant: str, avg_out: List[Optional[torch.Tensor]], ba
         if code in (N.FLAME_BF16, N.FLAME_F16):  # torch-CPU rounds the scalar of `sqrt(v) + tau`
             h[5] = float(torch.tensor(float(h[5]), dtype=base[idx[0]].dtype))
         opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
+        if code == N.FLAME_F64:
+            # fp64 rates, the unrounded scalars, always the device table (no kernel-argument variant)
+            p = plan(code, segs, rates)
+            dm = _staging.upload(p.meta, device)
+            segp, clp, _, r64p = _device_ptrs(dm, p)
+            with _timed("flame_fedopt_reduce_adapt", device, nbytes):
+                N.check(L.flame_fedopt_reduce_adapt_f64(FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs,
+                                                        p.n_chunks, clp, p.n_clients, r64p, *h64,
+                                                        _stream_ptr(device)))
+            keep.append(dm)
+            _keepalive(keep, device)
+            continue
         if ARGMETA and compact_meta_bytes(code, len(segs), len(rates)) <= argmeta_max_bytes():
             # small round: the metadata block rides in the kernel arguments (no H2D blit)
             p = plan(code, segs, rates, compact=True)
@@ -522,8 +536,9 @@ def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[tor
                   cur_out: List[torch.Tensor], m: List[torch.Tensor], v: List[torch.Tensor],
                   clients: List[List[torch.Tensor]], rates: Sequence[float], step_end: Sequence[bool], hyper,
                   state_zero: bool, first_aliased: Sequence[bool]) -> None:
-    """A queue of eager FedOPT do() calls in one pass (kernel: flame_fedopt_chain), one launch
-    per dtype (fp32 / bf16 / fp16; every tensor of a segment shares its dtype): per element,
+    """A queue of eager FedOPT do() calls in one pass (kernel: flame_fedopt_chain, for fp64
+    flame_fedopt_chain_f64), one launch per dtype (fp32 / bf16 / fp16 / fp64; every tensor of a
+    segment shares its dtype): per element,
     for each client in order, FedAvg into ``base`` (in place) with its rate, and after every
     client with ``step_end`` set, the adaptive step from the running current / m / v.
     ``first_aliased[s]``: segment s's current IS its base at the first step (``cur[s]`` unread);
@@ -539,8 +554,9 @@ def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[tor
     for s_, b in enumerate(base):
         groups.setdefault(dtype_code(b.dtype), []).append(s_)
     for code, idx in groups.items():
-        if code not in (N.FLAME_F32, N.FLAME_BF16, N.FLAME_F16):
+        if code not in FLOAT_CODES:
             raise NotImplementedError(f"fedopt_chain_: dtype {base[idx[0]].dtype}")
+    h64 = _scalars64(hyper) if N.FLAME_F64 in groups else None
     # every dtype group is planned and its tables uploaded BEFORE the first launch: a failure
     # there (a bad tensor, an allocation) leaves base / m / v untouched.  Only a
     # launch itself failing after another group's launch ran can leave the groups out of step;
@@ -573,13 +589,18 @@ def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[tor
         keep.append(dm)
         launches.append((code, p, dm, h, nbytes, keep))
     for i, (code, p, dm, h, nbytes, keep) in enumerate(launches):
-        segp, clp, r32p, _ = _device_ptrs(dm, p)
+        segp, clp, r32p, r64p = _device_ptrs(dm, p)
+        opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
         try:
             with _timed("flame_fedopt_chain", device, nbytes):
-                N.check(L.flame_fedopt_chain(code, FEDOPT_VARIANT[variant],
-                                             N.FLAME_OPT_STATE_ZERO if state_zero else 0, segp, p.n_segs, p.n_chunks,
-                                             clp, p.n_clients, r32p, dm.data_ptr() + p.meta.nbytes,
-                                             *[float(x) for x in h], _stream_ptr(device)))
+                if code == N.FLAME_F64:      # fp64 rates, the unrounded scalars
+                    N.check(L.flame_fedopt_chain_f64(FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs, p.n_chunks,
+                                                     clp, p.n_clients, r64p, dm.data_ptr() + p.meta.nbytes,
+                                                     *h64, _stream_ptr(device)))
+                else:
+                    N.check(L.flame_fedopt_chain(code, FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs,
+                                                 p.n_chunks, clp, p.n_clients, r32p, dm.data_ptr() + p.meta.nbytes,
+                                                 *[float(x) for x in h], _stream_ptr(device)))
         except Exception as e:
             if i:
                 e.flame_partial = True
@@ -587,10 +608,34 @@ def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[tor
         _keepalive(keep, device)
 
 
+class FedoptScalars(tuple):
+    """The six fp32 scalars (a plain tuple to every caller that unpacks them), with the Python
+    floats they were rounded from in ``raw``: an fp64 tensor multiplies by those unrounded."""
+
+    def __new__(cls, rounded, raw):
+        self = super().__new__(cls, rounded)
+        self.raw = tuple(float(x) for x in raw)
+        return self
+
+    def __reduce__(self):
+        return (FedoptScalars, (tuple(self), self.raw))
+
+
 def fedopt_scalars(beta_1, beta_2, eta, tau):
-    """fp32 scalars torch uses for `beta_1 * m`, `(1 - beta_1) * d`, ... (fedopt.py:113-129)."""
+    """fp32 scalars torch uses for `beta_1 * m`, `(1 - beta_1) * d`, ... (fedopt.py:113-129);
+    ``.raw`` keeps the Python floats, which are what an fp64 tensor is multiplied by."""
     f = np.float32
-    return (f(beta_1), f(1 - beta_1), f(beta_2), f(1 - beta_2), f(eta), f(tau))
+    raw = (beta_1, 1 - beta_1, beta_2, 1 - beta_2, eta, tau)
+    return FedoptScalars([f(x) for x in raw], raw)
+
+
+def _scalars64(hyper):
+    """The double scalars of an fp64 dtype group."""
+    raw = getattr(hyper, "raw", None)
+    if raw is None:
+        raise TypeError("flame_amd: an fp64 FedOPT launch needs the unrounded scalars "
+                        "(pass engine.fedopt_scalars(...), not its fp32 values)")
+    return [float(x) for x in raw]
 
 
 def scale_add_(bases: List[torch.Tensor], aggs: List[torch.Tensor], goal: int,

@@ -5,13 +5,15 @@ return ``current_weights``; round 1 -> ``current_weights = agg_weights`` (no
 adaptive step); afterwards the adaptive step of ``_adapt_pytorch``
 (:102-129) with the subclass's ``_delta_v``.
 
-From the second adaptive-capable round on, fp32 / bf16 / fp16 keys go through
-ONE fused kernel per dtype (``flame_fedopt_reduce_adapt``): the client
+From the second adaptive-capable round on, fp32 / bf16 / fp16 / fp64 keys go through
+ONE fused kernel per dtype (``flame_fedopt_reduce_adapt``, for fp64
+``flame_fedopt_reduce_adapt_f64``): the client
 reduction, ``d``, ``m_t``, ``v_t`` and the new ``current`` are computed in
 registers with one rounding per reference op, reading base/cur/m/v once and
 writing avg/m/v/cur once, instead of ~12 unfused torch passes.  Other keys
 (BatchNorm's int64 ``num_batches_tracked``, which the reference silently
-promotes to fp32 in this step, fp64 keys, and any key whose dtype changed) are
+promotes to fp32 in this step, and any key whose dtype changed or whose state has
+another dtype) are
 reduced by the FedAvg kernel and then run the reference's statements as one
 ``flame_elementwise`` program per key (``flame_amd.elementwise``: torch's own dtype
 promotions, torch-CPU's arithmetic per dtype).
@@ -24,7 +26,7 @@ lazily from ``agg_weights`` and the previous ``current_weights`` on access.
 
 ``defer=True`` (opt-in, like ``FedAvg(defer=True)``) batches the EAGER caller
 (eager_syncfl/top_aggregator.py:36-90: one ``do()`` per arrival into the round's base):
-each eligible call (fp32 / bf16 / fp16 keys on the GPU) pops its cache entries, queues them and
+each eligible call (fp32 / bf16 / fp16 / fp64 keys on the GPU) pops its cache entries, queues them and
 returns a :class:`DeferredCurrent`; the queue runs as ONE ``flame_fedopt_chain`` launch
 when anything reads the results (the returned mapping, ``current_weights``, ``m_t``,
 ``v_t``, ``agg_weights``), bit-identical to a launch per call.  Until then the base dict
@@ -189,7 +191,7 @@ class FedOPT(FedAvg):
         device = engine.pick_device(base_weights, current, *[w for w, _ in entries])
         keys = list(base_weights.keys())
         fused, generic = [], []
-        float_dts = (torch.float32, torch.bfloat16, torch.float16)
+        float_dts = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
         for k in keys:
             dt = base_weights[k].dtype
             # the eager caller hands the same base dict to every do() of a round, so after the
@@ -322,7 +324,7 @@ class FedOPT(FedAvg):
         ch.last_empty = False
         ch.steps.append(step)
         ch.n_entries += len(step)
-        ch.nbytes += len(step) * sum(base_weights[k].numel() * 4 for k in keys)
+        ch.nbytes += len(step) * sum(base_weights[k].numel() * base_weights[k].element_size() for k in keys)
         ch.results.append([])
         return ch.result(self, len(ch.steps) - 1, keys)
 
@@ -400,7 +402,7 @@ class FedOPT(FedAvg):
 
     def _adapt_generic(self, keys, average, current, state_zero):
         """fedopt.py:106-129 for the keys the fused kernel does not take (int buffers such as
-        num_batches_tracked, mixed-dtype and fp64 keys): the reference's statements, the
+        num_batches_tracked and mixed-dtype keys): the reference's statements, the
         subclass's _delta_v_tensor included, recorded on elementwise.Lazy operands and run as
         ONE flame_elementwise launch per key -- torch's own dtype promotions, torch-CPU's
         arithmetic per dtype (include/flame_amd.h), no PyTorch compute."""
@@ -441,11 +443,11 @@ class FedOPT(FedAvg):
 _SHARD_KWARGS = {"flame_amd_key_groups", "flame_amd_after_group", "flame_amd_out_alloc"}
 
 
-_CHAIN_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+_CHAIN_DTYPES = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
 
 
 def _chain_tensors(weights) -> bool:
-    """A base dict flame_fedopt_chain can update in place: fp32 / bf16 / fp16, contiguous, one GPU."""
+    """A base dict flame_fedopt_chain can update in place: fp32 / bf16 / fp16 / fp64, contiguous, one GPU."""
     try:
         ts = list(weights.values())
     except AttributeError:

@@ -11,7 +11,10 @@
  *                                                             _aggregate_pytorch)
  *   flame_fedopt_reduce_adapt   optimizer/fedopt.py:80-90,102-129 (FedAvg.do + _adapt_pytorch)
  *                               + fedadam.py:33-35 / fedyogi.py:34-36 / fedadagrad.py:33-35
- *   flame_fedbuff_scale_add     optimizer/fedbuff.py:101-127 (scale_add_agg_weights), fused with
+ *   flame_fedopt_reduce_adapt_f64, flame_fedopt_chain_f64
+ *                               the same statements on float64 tensors (fp64 rates, unrounded
+ *                               Python-float scalars), per round and per eager queue
+ *   flame_fedbuff_scale_add    optimizer/fedbuff.py:101-127 (scale_add_agg_weights), fused with
  *                               common/util.py:152-159 (delta_weights_pytorch) as used by
  *                               mode/horizontal/asyncfl/middle_aggregator.py:221-226,246
  *   flame_hier_fedbuff          a node's co-located two-level FedBuff hierarchy in one pass
@@ -24,7 +27,7 @@
  *   flame_feddyn_round          optimizer/feddyn.py:90-113,125-139 (FedDyn.do: add_to_hist,
  *                               FedAvg with rate 1/len(cache), mean of the histories, cld_model)
  *   flame_elementwise           the same statements for the keys the fused kernels do not take
- *                               (int / mixed-dtype / fp64 keys): optimizer/fedopt.py:102-129,
+ *                               (int and mixed-dtype keys; fp64 outside FedOPT): optimizer/fedopt.py:102-129,
  *                               scaffold.py:141-150, feddyn.py:90-113,125-139
  *   flame_synth_fill            (bench/test plumbing: counter-based synthetic updates)
  *   flame_hier_resident_per_cu  (no reference counterpart: occupancy query the parameter
@@ -214,6 +217,45 @@ int flame_fedopt_reduce_adapt_argmeta(int dtype, int variant, unsigned flags, co
                                       int32_t n_clients, int64_t off_clients, int64_t off_r32,
                                       float b1, float omb1, float b2, float omb2, float eta,
                                       float tau, void *stream);
+
+/*
+ * flame_fedopt_reduce_adapt for FLAME_F64 segments (base, cur, m, v, outputs and clients all
+ * fp64; chunk_begin counts flame_chunk_elems(FLAME_F64) chunks): one launch per round for all
+ * fp64 keys.  Per element the clients are reduced in order with the fp64 rates,
+ * acc = round(acc + round(w_i * rates64[i])) as flame_agg_reduce does for FLAME_F64, then
+ *   d = avg - cur; m = b1*m + omb1*d;
+ *   Adam: v = b2*v + omb2*(d*d);  Yogi: v = v - (omb2*(d*d))*sign(v - d*d);  AdaGrad: v = v + d*d
+ *   cur_out = cur + (eta*m) / (sqrt(v) + tau)
+ * with every op one IEEE fp64 rounding (no FMA, denormals kept, sqrt and divide correctly
+ * rounded, sign as torch.sign: NaN and +-0 give 0), and avg (if seg.out), m, v, cur_out stored.
+ * Scalars are the Python floats themselves, not their fp32 roundings: torch multiplies an fp64
+ * tensor by a Python scalar in double (b1 = beta_1, omb1 = 1 - beta_1, b2 = beta_2,
+ * omb2 = 1 - beta_2, eta, tau).  Flags and FLAME_SEG_CUR_IS_AVG as flame_fedopt_reduce_adapt.
+ * Replaces optimizer/fedopt.py:80-90,102-129 + fedadam.py:33-35 / fedyogi.py:34-36 /
+ * fedadagrad.py:33-35 on float64 tensors; bitwise equal to flame_agg_reduce followed by the
+ * same statements through flame_elementwise.
+ */
+int flame_fedopt_reduce_adapt_f64(int variant, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                                  int64_t n_chunks, const void *const *clients, int32_t n_clients,
+                                  const double *rates64, double b1, double omb1, double b2, double omb2,
+                                  double eta, double tau, void *stream);
+
+/*
+ * flame_fedopt_chain for FLAME_F64 segments (fp64 rates, scalars as for
+ * flame_fedopt_reduce_adapt_f64): per element, for each client i in order
+ * base = base + round(w_i * rates64[i]); where step_end[i] != 0 the adaptive step of
+ * flame_fedopt_reduce_adapt_f64 with avg = base and the running current (the first step of a
+ * segment flagged FLAME_SEG_CUR_IS_AVG takes cur = base; if no step closes, cur_out = base).
+ * Writes base to seg.out, m and v in place, the final current to seg.cur_out.
+ * FLAME_OPT_STATE_ZERO: m, v start as zeros and are not read.  Needs >= 1 client and a step_end
+ * array.  Bitwise equal to one flame_fedopt_reduce_adapt_f64 launch per do() call.  Replaces,
+ * per round, optimizer/fedopt.py:80-90,102-129 as the eager role
+ * (eager_syncfl/top_aggregator.py:36-90) calls it on float64 tensors.
+ */
+int flame_fedopt_chain_f64(int variant, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                           int64_t n_chunks, const void *const *clients, int32_t n_clients,
+                           const double *rates64, const uint8_t *step_end, double b1, double omb1,
+                           double b2, double omb2, double eta, double tau, void *stream);
 
 /*
  * FedBuff scale-add: out[e] = round(out[e] + round(in[e] / goal)); if seg.cur_out

@@ -49,7 +49,7 @@ def main():
     ap.add_argument("--keys", type=int, default=53)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--fp64", action="store_true", help="instead: an fp64 key's step, device time (fp64_rate)")
+    ap.add_argument("--fp64", action="store_true", help="instead: an fp64 key's step, device time of three arms (fp64_rate)")
     a = ap.parse_args()
     from flame_amd.optimizers import optimizer_provider
     dev = torch.device("cuda", 0)
@@ -98,38 +98,59 @@ if __name__ == "__main__" and "--fp64" not in sys.argv:
     main()
 
 
-def fp64_rate(n=25_000_000, rounds=5):
-    """Device time of one FedAdam adaptive step of an n-element fp64 key: the elementwise program
-    (flame_elementwise, one launch) against the same statements as torch ops (round 5's path)."""
+def fp64_rate(n=25_000_000, rounds=7, blocks=3):
+    """Device time of one FedAdam adaptive step of an n-element fp64 key, three arms in one
+    process, their rounds alternating: the elementwise program (flame_elementwise, one launch),
+    the same statements as torch ops (round 5's path), and the compiled kernel
+    (flame_fedopt_reduce_adapt_f64 through engine.fedopt_reduce_adapt_ with no clients: the
+    split-launch form).  ``blocks`` medians per arm show the run-to-run spread a lead has to beat."""
+    from flame_amd import engine
     from flame_amd.optimizers import optimizer_provider
     dev = torch.device("cuda", 0)
     opt = optimizer_provider.get("fedadam")
     g = torch.Generator(device=dev).manual_seed(3)
     avg = torch.randn(n, dtype=torch.float64, device=dev, generator=g)
     cur = torch.randn(n, dtype=torch.float64, device=dev, generator=g)
-    opt.m_t = {"k": torch.randn(n, dtype=torch.float64, device=dev, generator=g) * 1e-2}
-    opt.v_t = {"k": torch.rand(n, dtype=torch.float64, device=dev, generator=g) * 1e-2}
-    m0, v0 = opt.m_t["k"].clone(), opt.v_t["k"].clone()
+    m0 = torch.randn(n, dtype=torch.float64, device=dev, generator=g) * 1e-2
+    v0 = torch.rand(n, dtype=torch.float64, device=dev, generator=g) * 1e-2
+    hyper = engine.fedopt_scalars(opt.beta_1, opt.beta_2, opt.eta, opt.tau)
+
+    def fused():
+        out = torch.empty_like(cur)
+        engine.fedopt_reduce_adapt_("fedadam", [None], [avg], [cur], [out], [opt.m_t["k"]], [opt.v_t["k"]],
+                                    [[]], [], hyper, False)
+        return {"k": out}
+
+    arms = (("elementwise", lambda: opt._adapt_generic(["k"], {"k": avg}, {"k": cur}, False)),
+            ("torch-ops", lambda: torch_ops_generic(opt, ["k"], {"k": avg}, {"k": cur}, False)),
+            ("fused", fused))
+    meds = {name: [] for name, _ in arms}
     res = {}
-    for name, fn in (("elementwise", lambda: opt._adapt_generic(["k"], {"k": avg}, {"k": cur}, False)),
-                     ("torch-ops", lambda: torch_ops_generic(opt, ["k"], {"k": avg}, {"k": cur}, False))):
-        ts = []
+    for b in range(blocks):
+        ts = {name: [] for name, _ in arms}
         for r in range(rounds + 1):
-            opt.m_t, opt.v_t = {"k": m0.clone()}, {"k": v0.clone()}
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if r:
-                ts.append(e0.elapsed_time(e1))
-        res[name] = (sorted(ts)[len(ts) // 2], out["k"].clone())
-    same = torch.equal(res["elementwise"][1], res["torch-ops"][1])
+            for name, fn in arms:
+                opt.m_t, opt.v_t = {"k": m0.clone()}, {"k": v0.clone()}
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn()
+                e1.record()
+                torch.cuda.synchronize()
+                if r:                  # the first round of a block warms the arm up
+                    ts[name].append(e0.elapsed_time(e1))
+                res[name] = (out["k"], opt.m_t["k"], opt.v_t["k"])
+        for name in ts:
+            meds[name].append(sorted(ts[name])[len(ts[name]) // 2])
+    same = {name: all(torch.equal(x, y) for x, y in zip(res["fused"], res[name])) for name in ("elementwise", "torch-ops")}
     gb = n * 8 * 7 / 1e9          # avg, cur, m, v read; m, v, out written
-    print(f"fp64 FedAdam step, {n} elements: elementwise {res['elementwise'][0]:.3f} ms "
-          f"({gb / res['elementwise'][0] * 1e3:.0f} GB/s of its {gb:.2f} GB), torch ops {res['torch-ops'][0]:.3f} ms; "
-          f"bitwise equal: {same}", flush=True)
+    mid = {name: sorted(t)[len(t) // 2] for name, t in meds.items()}
+    print(f"fp64 FedAdam step, {n} elements, {gb:.2f} GB, medians of {rounds} alternating rounds x {blocks} blocks:", flush=True)
+    for name, _ in arms:
+        print(f"  {name:12s} {mid[name]:.3f} ms ({gb / mid[name] * 1e3:.0f} GB/s); block medians "
+              f"{' '.join(f'{t:.3f}' for t in meds[name])} (spread {max(meds[name]) - min(meds[name]):.3f} ms)", flush=True)
+    print(f"  fused bitwise equal (current, m, v) to elementwise: {same['elementwise']}, to torch ops: {same['torch-ops']}",
+          flush=True)
 
 
 if __name__ == "__main__" and "--fp64" in sys.argv:
