@@ -2336,65 +2336,87 @@ __global__ __launch_bounds__(kEwBlock) void ew_kernel(EwArgs args) {
 // ---------------------------------------------------------------- launch-branch counters
 // Every host-side launch branch of the C ABI has an index; a successful launch counts it, so
 // tests can assert which instantiation a call took and that every branch is reached by an
-// oracle test (tests/test_gpu_zz_launch_branches.py).  dt = FLAME_F32 .. FLAME_I32.
+// oracle test (tests/test_gpu_zz_launch_branches.py).
+//
+// The host side from here to flame_feddyn_round:
+//   * the branch table: the BR_* bases and kBranchRows, one row per family; branch_name() looks a
+//     name up in it.  A new family takes the next free base, a row and a larger BR_COUNT (rows
+//     that do not tile [0, BR_COUNT) do not compile).
+//   * dispatch<VALUES...>(): a runtime dtype / variant / mode becomes a std::integral_constant,
+//     so the fan-out over template arguments is written once per family.
+//   * the shared argument checks (check_chunks, check_variant, check_flags, load_argmeta, inside).
+//   * per family (agg, fedopt, hier) one pick_*(), the only rule that chooses an instantiation --
+//     the device-table entry point, the kernel-argument one and flame_hier_resident_per_cu all
+//     call it -- and one launch_*(), templated on where the metadata comes from.
 enum : int {
-    BR_AGG = 0,           // + dt (6): flame_agg_reduce, full residency
-    BR_AGG_LO = 6,        // + dt (f32, bf16, f16): flame_agg_reduce, 2 workgroups per CU
-    BR_AGG_ARG = 9,       // + dt (6): flame_agg_reduce_argmeta
-    BR_OPT = 15,          // + dt * 3 + variant (f32, bf16, f16): flame_fedopt_reduce_adapt, one chunk per workgroup
-    BR_OPT_MULTI = 24,    // + variant: fp32, kOptWGC chunks per workgroup
-    BR_OPT_ARG = 27,      // + dt * 3 + variant: flame_fedopt_reduce_adapt_argmeta
-    BR_SA = 36,           // + dt (f32, bf16, f16, f64): flame_fedbuff_scale_add
-    BR_HIER_REG = 40,     // + dt * 2 + sync: flame_hier_fedbuff, register store groups
-    BR_HIER_LDS = 46,     // + dt * 2 + sync: LDS store groups (>= kHLdsMinMids middles)
-    BR_HIER_LO = 52,      // + dt: one middle over a long launch, low residency (FedBuff only)
-    BR_HIER_ARG = 55,     // + dt * 2 + sync: flame_hier_fedbuff_argmeta
-    BR_DYN = 61,          // + dt (f32, bf16, f16, f64): flame_feddyn_round
-    BR_AGG_ARG_LO = 65,   // + dt (f32, bf16, f16): flame_agg_reduce_argmeta, 2 workgroups per CU, output bursts
-    BR_HIER_ARG_LO = 68,  // + dt: flame_hier_fedbuff_argmeta, one middle over a long launch
-    BR_OPT_ARG_MULTI = 71,  // + variant: flame_fedopt_reduce_adapt_argmeta, fp32, kOptWGC chunks per workgroup
-    BR_HIER_ARG_LDS = 74,   // + dt * 2 + sync: flame_hier_fedbuff_argmeta, LDS store groups
-    BR_CHAIN = 80,          // + dt * 3 + variant (f32, bf16, f16): flame_fedopt_chain
-    BR_AGG_LOB = 89,        // + dt (f32, bf16, f16): flame_agg_reduce, low residency, LDS-held output bursts
-    BR_EW = 92,             // flame_elementwise
-    BR_EW_SEG = 93,         // flame_elementwise_segments
-    BR_OPT_F64 = 94,        // + variant: flame_fedopt_reduce_adapt_f64 (appended: BR_OPT + dt * 3 would run into BR_OPT_MULTI)
-    BR_CHAIN_F64 = 97,      // + variant: flame_fedopt_chain_f64
-    BR_COUNT = 100
+    BR_AGG = 0, BR_AGG_LO = 6, BR_AGG_ARG = 9, BR_OPT = 15, BR_OPT_MULTI = 24, BR_OPT_ARG = 27, BR_SA = 36,
+    BR_HIER_REG = 40, BR_HIER_LDS = 46, BR_HIER_LO = 52, BR_HIER_ARG = 55, BR_DYN = 61, BR_AGG_ARG_LO = 65,
+    BR_HIER_ARG_LO = 68, BR_OPT_ARG_MULTI = 71, BR_HIER_ARG_LDS = 74, BR_CHAIN = 80, BR_AGG_LOB = 89, BR_EW = 92,
+    BR_EW_SEG = 93, BR_OPT_F64 = 94, BR_CHAIN_F64 = 97, BR_COUNT = 100
 };
 std::atomic<long long> g_launches[BR_COUNT];
+
+// How a branch's offset from its family's base becomes the rest of its name (dt = FLAME_F32 ..
+// FLAME_I32): BK_DT offset = dt, BK_DT_VARIANT dt * 3 + variant, BK_DT_SYNC dt * 2 + sync
+// (fedbuff / sync), BK_VARIANT variant, BK_NONE the prefix alone
+enum BranchKey : int { BK_NONE, BK_DT, BK_DT_VARIANT, BK_DT_SYNC, BK_VARIANT };
+struct BranchRow {
+    int base, count;
+    BranchKey key;
+    const char* prefix;
+    const char* suffix = "";
+};
+constexpr BranchRow kBranchRows[] = {
+    {BR_AGG, 6, BK_DT, "flame_agg_reduce"},                        // full residency
+    {BR_AGG_LO, 3, BK_DT, "flame_agg_reduce/lo"},                  // f32, bf16, f16: 2 workgroups per CU
+    {BR_AGG_ARG, 6, BK_DT, "flame_agg_reduce_argmeta"},
+    {BR_OPT, 9, BK_DT_VARIANT, "flame_fedopt_reduce_adapt"},       // f32, bf16, f16: one chunk per workgroup
+    {BR_OPT_MULTI, 3, BK_VARIANT, "flame_fedopt_reduce_adapt/multi/f32"},      // kOptWGC chunks per workgroup
+    {BR_OPT_ARG, 9, BK_DT_VARIANT, "flame_fedopt_reduce_adapt_argmeta"},
+    {BR_SA, 4, BK_DT, "flame_fedbuff_scale_add"},                  // f32, bf16, f16, f64
+    {BR_HIER_REG, 6, BK_DT_SYNC, "flame_hier_fedbuff/reg"},        // register store groups
+    {BR_HIER_LDS, 6, BK_DT_SYNC, "flame_hier_fedbuff/lds"},        // LDS store groups (>= kHLdsMinMids middles)
+    {BR_HIER_LO, 3, BK_DT, "flame_hier_fedbuff/lo", "/fedbuff"},   // one middle over a long launch, low residency
+    {BR_HIER_ARG, 6, BK_DT_SYNC, "flame_hier_fedbuff_argmeta"},
+    {BR_DYN, 4, BK_DT, "flame_feddyn_round"},                      // f32, bf16, f16, f64
+    {BR_AGG_ARG_LO, 3, BK_DT, "flame_agg_reduce_argmeta/lo_burst"},
+    {BR_HIER_ARG_LO, 3, BK_DT, "flame_hier_fedbuff_argmeta/lo", "/fedbuff"},
+    {BR_OPT_ARG_MULTI, 3, BK_VARIANT, "flame_fedopt_reduce_adapt_argmeta/multi/f32"},
+    {BR_HIER_ARG_LDS, 6, BK_DT_SYNC, "flame_hier_fedbuff_argmeta/lds"},
+    {BR_CHAIN, 9, BK_DT_VARIANT, "flame_fedopt_chain"},            // f32, bf16, f16
+    {BR_AGG_LOB, 3, BK_DT, "flame_agg_reduce/lo_burst"},           // low residency, LDS-held output bursts
+    {BR_EW, 1, BK_NONE, "flame_elementwise"},
+    {BR_EW_SEG, 1, BK_NONE, "flame_elementwise_segments"},
+    {BR_OPT_F64, 3, BK_VARIANT, "flame_fedopt_reduce_adapt/f64"},
+    {BR_CHAIN_F64, 3, BK_VARIANT, "flame_fedopt_chain/f64"},
+};
+constexpr bool branch_rows_tile() {
+    int next = 0;
+    for (const BranchRow& r : kBranchRows) {
+        if (r.base != next || r.count < 1) return false;      // a gap, an overlap or rows out of index order
+        next += r.count;
+    }
+    return next == BR_COUNT;
+}
+static_assert(branch_rows_tile(), "kBranchRows must tile [0, BR_COUNT) in index order, without gap or overlap");
 
 const char* branch_name(int i) {
     static const char* const dts[6] = {"f32", "bf16", "f16", "f64", "i64", "i32"};
     static const char* const var[3] = {"fedadam", "fedyogi", "fedadagrad"};
     static char names[BR_COUNT][64];
     static const bool once = [] {
-        for (int b = 0; b < BR_COUNT; ++b) {
-            char* n = names[b];
-            const size_t z = sizeof(names[b]);
-            if (b < BR_AGG_LO) snprintf(n, z, "flame_agg_reduce/%s", dts[b - BR_AGG]);
-            else if (b < BR_AGG_ARG) snprintf(n, z, "flame_agg_reduce/lo/%s", dts[b - BR_AGG_LO]);
-            else if (b < BR_OPT) snprintf(n, z, "flame_agg_reduce_argmeta/%s", dts[b - BR_AGG_ARG]);
-            else if (b < BR_OPT_MULTI) snprintf(n, z, "flame_fedopt_reduce_adapt/%s/%s", dts[(b - BR_OPT) / 3], var[(b - BR_OPT) % 3]);
-            else if (b < BR_OPT_ARG) snprintf(n, z, "flame_fedopt_reduce_adapt/multi/f32/%s", var[b - BR_OPT_MULTI]);
-            else if (b < BR_SA) snprintf(n, z, "flame_fedopt_reduce_adapt_argmeta/%s/%s", dts[(b - BR_OPT_ARG) / 3], var[(b - BR_OPT_ARG) % 3]);
-            else if (b < BR_HIER_REG) snprintf(n, z, "flame_fedbuff_scale_add/%s", dts[b - BR_SA]);
-            else if (b < BR_HIER_LDS) snprintf(n, z, "flame_hier_fedbuff/reg/%s/%s", dts[(b - BR_HIER_REG) / 2], (b - BR_HIER_REG) % 2 ? "sync" : "fedbuff");
-            else if (b < BR_HIER_LO) snprintf(n, z, "flame_hier_fedbuff/lds/%s/%s", dts[(b - BR_HIER_LDS) / 2], (b - BR_HIER_LDS) % 2 ? "sync" : "fedbuff");
-            else if (b < BR_HIER_ARG) snprintf(n, z, "flame_hier_fedbuff/lo/%s/fedbuff", dts[b - BR_HIER_LO]);
-            else if (b < BR_DYN) snprintf(n, z, "flame_hier_fedbuff_argmeta/%s/%s", dts[(b - BR_HIER_ARG) / 2], (b - BR_HIER_ARG) % 2 ? "sync" : "fedbuff");
-            else if (b < BR_AGG_ARG_LO) snprintf(n, z, "flame_feddyn_round/%s", dts[b - BR_DYN]);
-            else if (b < BR_HIER_ARG_LO) snprintf(n, z, "flame_agg_reduce_argmeta/lo_burst/%s", dts[b - BR_AGG_ARG_LO]);
-            else if (b < BR_OPT_ARG_MULTI) snprintf(n, z, "flame_hier_fedbuff_argmeta/lo/%s/fedbuff", dts[b - BR_HIER_ARG_LO]);
-            else if (b < BR_HIER_ARG_LDS) snprintf(n, z, "flame_fedopt_reduce_adapt_argmeta/multi/f32/%s", var[b - BR_OPT_ARG_MULTI]);
-            else if (b < BR_CHAIN) snprintf(n, z, "flame_hier_fedbuff_argmeta/lds/%s/%s", dts[(b - BR_HIER_ARG_LDS) / 2], (b - BR_HIER_ARG_LDS) % 2 ? "sync" : "fedbuff");
-            else if (b < BR_AGG_LOB) snprintf(n, z, "flame_fedopt_chain/%s/%s", dts[(b - BR_CHAIN) / 3], var[(b - BR_CHAIN) % 3]);
-            else if (b < BR_EW) snprintf(n, z, "flame_agg_reduce/lo_burst/%s", dts[b - BR_AGG_LOB]);
-            else if (b < BR_EW_SEG) snprintf(n, z, "flame_elementwise");
-            else if (b < BR_OPT_F64) snprintf(n, z, "flame_elementwise_segments");
-            else if (b < BR_CHAIN_F64) snprintf(n, z, "flame_fedopt_reduce_adapt/f64/%s", var[b - BR_OPT_F64]);
-            else snprintf(n, z, "flame_fedopt_chain/f64/%s", var[b - BR_CHAIN_F64]);
-        }
+        for (const BranchRow& r : kBranchRows)
+            for (int o = 0; o < r.count; ++o) {
+                char* n = names[r.base + o];
+                const size_t z = sizeof(names[0]);
+                switch (r.key) {
+                case BK_NONE: snprintf(n, z, "%s", r.prefix); break;
+                case BK_DT: snprintf(n, z, "%s/%s%s", r.prefix, dts[o], r.suffix); break;
+                case BK_DT_VARIANT: snprintf(n, z, "%s/%s/%s", r.prefix, dts[o / 3], var[o % 3]); break;
+                case BK_DT_SYNC: snprintf(n, z, "%s/%s/%s", r.prefix, dts[o / 2], o % 2 ? "sync" : "fedbuff"); break;
+                case BK_VARIANT: snprintf(n, z, "%s/%s", r.prefix, var[o]); break;
+                }
+            }
         return true;
     }();
     (void)once;
@@ -2408,12 +2430,248 @@ int launched(int br, const char* what) {
     return rc;
 }
 
+// ---------------------------------------------------------------- compile-time dispatch
+// Calls f(std::integral_constant<int, V>{}) for the V of VALUES that equals v; false when none
+// does.  Inlines to the if-chain a switch would give.  A left fold: the compiler expands it, and
+// so instantiates the kernels, in the order VALUES are written.
+template <int V> using ic = std::integral_constant<int, V>;
+template <int... VALUES, typename F>
+inline bool dispatch(int v, F&& f) {
+    return (... || (v == VALUES && (f(ic<VALUES>{}), true)));
+}
+template <typename F> inline bool dispatch_variant(int variant, F&& f) {
+    return dispatch<FLAME_FEDADAM, FLAME_FEDYOGI, FLAME_FEDADAGRAD>(variant, f);
+}
+constexpr bool is16(int dt) { return dt == FLAME_BF16 || dt == FLAME_F16; }
+constexpr bool is_f32_or_16(int dt) { return dt == FLAME_F32 || is16(dt); }
+
+// ---------------------------------------------------------------- shared argument checks
+int check_chunks(int64_t n_chunks) {
+    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
+    return FLAME_OK;
+}
+int check_variant(const char* who, int variant) {
+    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD) return set_err(FLAME_ENOTSUP, "%s: unknown variant %d", who, variant);
+    return FLAME_OK;
+}
+int check_flags(const char* who, unsigned flags, unsigned allowed) {
+    if (flags & ~allowed) return set_err(FLAME_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    return FLAME_OK;
+}
+
 int validate(const flame_segment* segs, int32_t n_segs, int64_t n_chunks, int32_t n_clients, const void* clients) {
     if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is NULL or n_segs <= 0");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
+    if (int rc = check_chunks(n_chunks)) return rc;
     if (n_clients < 0) return set_err(FLAME_EINVAL, "n_clients < 0");
     if (n_clients > 0 && !clients) return set_err(FLAME_EINVAL, "client pointer table is NULL");
     return FLAME_OK;
+}
+
+// The kernel-argument entry points: the caller's metadata block, checked and copied into the
+// ArgMeta the launch passes by value; a table of `bytes` at byte offset `off` lies inside it
+int load_argmeta(const char* who, const void* host_meta, int64_t meta_bytes, ArgMeta& m) {
+    if (!host_meta || meta_bytes <= 0 || meta_bytes % 8 || meta_bytes > static_cast<int64_t>(sizeof(ArgMeta)))
+        return set_err(FLAME_EINVAL, "%s: metadata block must be 8..%d bytes, a multiple of 8", who,
+                       static_cast<int>(sizeof(ArgMeta)));
+    std::memcpy(m.w, host_meta, static_cast<size_t>(meta_bytes));
+    return FLAME_OK;
+}
+
+bool inside(int64_t meta_bytes, int64_t off, int64_t bytes) { return off >= 0 && off % 8 == 0 && off + bytes <= meta_bytes; }
+
+// ---------------------------------------------------------------- flame_agg_reduce[_argmeta]
+// Where a launch's metadata comes from: tables in device memory, or word offsets into the ArgMeta
+// that travels as the first kernel argument
+struct AggTables { const flame_segment* segs; const uint64_t* clients; const float* r32; const double* r64; };
+struct AggArgMeta { const ArgMeta* m; int oc, o32, o64; };
+constexpr unsigned kAggFlags = FLAME_AGG_INIT_FIRST | FLAME_AGG_SEG_RATES | FLAME_AGG_XCD_MAP;
+
+int check_agg_flags(const char* who, unsigned flags, int32_t n_clients) {
+    if ((flags & FLAME_AGG_INIT_FIRST) && n_clients < 1)
+        return set_err(FLAME_EINVAL, "FLAME_AGG_INIT_FIRST needs at least one client");
+    return check_flags(who, flags, kAggFlags);
+}
+
+enum AggMode : int {
+    AGG_FULL,  // one chunk per workgroup, full residency
+    AGG_LO,    // long-lived workgroups over many chunks: two per CU, fewer loads in flight per lane
+    AGG_LOB    // the same with kLoWGC chunks' outputs held in LDS and stored in bursts
+};
+int pick_agg(int dtype, int32_t n_clients, int64_t n_chunks, bool argmeta) {
+    // f64 / integers have no low-residency instantiation: the general launch
+    if (!is_f32_or_16(dtype) || n_clients < kLoMinClients || n_chunks < kLoMinChunks) return AGG_FULL;
+    // the kernel-argument block cannot hold enough clients to need the plain instantiation
+    static_assert((kArgMetaWords - 10) < kLoBurstMaxClients,
+                  "a kernel-argument launch can hold kLoBurstMaxClients clients: it needs the plain instantiation too");
+    return (argmeta || n_clients < kLoBurstMaxClients) ? AGG_LOB : AGG_LO;
+}
+constexpr bool agg_exists(int dt, int mode, bool argmeta) {
+    return mode == AGG_FULL || (is_f32_or_16(dt) && !(argmeta && mode == AGG_LO));
+}
+constexpr int agg_branch(int mode, bool argmeta) {
+    if (argmeta) return mode == AGG_FULL ? BR_AGG_ARG : BR_AGG_ARG_LO;
+    return mode == AGG_FULL ? BR_AGG : mode == AGG_LO ? BR_AGG_LO : BR_AGG_LOB;
+}
+template <int DT, int MODE> struct AggInst {
+    static constexpr int CU = MODE != AGG_FULL ? (is16(DT) ? kLoUnroll16 : kLoUnroll)
+                              : (DT == FLAME_I64 || DT == FLAME_I32) ? 4 : is16(DT) ? kClientUnroll16 : kClientUnroll;
+    static constexpr int G = MODE == AGG_LOB ? kLoWGC : 1;       // chunks per workgroup
+    static constexpr int LDS = MODE == AGG_LOB ? kLoDynLds : MODE == AGG_LO ? kLoLds : 0;   // a residency cap
+};
+
+template <typename SRC>
+inline int launch_agg(const char* who, int dtype, unsigned flags, const SRC& src, int32_t n_segs, int32_t n_clients,
+                      int64_t n_chunks, void* stream) {
+    constexpr bool kArg = std::is_same<SRC, AggArgMeta>::value;
+    const int mode = pick_agg(dtype, n_clients, n_chunks, kArg);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bool known = false;
+    dispatch<AGG_LOB, AGG_LO, AGG_FULL>(mode, [&](auto md) {
+        known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64, FLAME_I64, FLAME_I32>(dtype, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value, MODE = decltype(md)::value;
+            if constexpr (agg_exists(DT, MODE, kArg)) {
+                using I = AggInst<DT, MODE>;
+                const dim3 grid(static_cast<unsigned>((n_chunks + I::G - 1) / I::G)), block(kBlock);
+                if constexpr (kArg)
+                    hipLaunchKernelGGL((agg_reduce_kernel_argmeta<DT, I::CU, I::G>), grid, block, I::LDS, st, *src.m,
+                                       n_segs, n_clients, src.oc, src.o32, src.o64, flags, n_chunks);
+                else
+                    hipLaunchKernelGGL((agg_reduce_kernel<DT, I::CU, I::G>), grid, block, I::LDS, st, src.segs, n_segs,
+                                       src.clients, n_clients, src.r32, src.r64, flags, n_chunks);
+            }
+        });
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "%s: unsupported dtype %d", who, dtype);
+    return launched(agg_branch(mode, kArg) + dtype, who);
+}
+
+// ---------------------------------------------------------------- flame_fedopt_reduce_adapt[_argmeta]
+struct Hyper32 { float b1, omb1, b2, omb2, eta, tau; };
+struct OptTables { const flame_segment* segs; const uint64_t* clients; const float* r32; };
+struct OptArgMeta { const ArgMeta* m; int oc, o32; };
+constexpr unsigned kOptFlags = FLAME_OPT_STATE_ZERO | FLAME_OPT_XCD_MAP;
+
+// kOptWGC chunks per workgroup (outputs held in LDS) for fp32 launches big enough to fill the
+// GPU several times over; one chunk per workgroup otherwise
+bool pick_opt(int dtype, int64_t n_chunks) { return dtype == FLAME_F32 && n_chunks >= 8ll * 256 * kOptWGC; }
+template <int DT, bool MULTI> struct OptInst {
+    static constexpr int CU = MULTI ? kOptUnroll : is16(DT) ? kClientUnroll16 : kClientUnroll;
+    static constexpr int G = MULTI ? kOptWGC : 1;
+};
+
+// the caller has checked the variant
+template <typename SRC>
+inline int launch_opt(const char* who, int dtype, int variant, unsigned flags, const SRC& src, int32_t n_segs,
+                      int32_t n_clients, int64_t n_chunks, const Hyper32& h, void* stream) {
+    constexpr bool kArg = std::is_same<SRC, OptArgMeta>::value;
+    const bool multi = pick_opt(dtype, n_chunks);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) {
+        dispatch<1, 0>(multi, [&](auto mu) {
+            dispatch_variant(variant, [&](auto vr) {
+                constexpr int DT = decltype(dt)::value, V = decltype(vr)::value;
+                constexpr bool MULTI = decltype(mu)::value != 0;
+                if constexpr (!MULTI || DT == FLAME_F32) {
+                    using I = OptInst<DT, MULTI>;
+                    const dim3 grid(static_cast<unsigned>((n_chunks + I::G - 1) / I::G)), block(kBlock);
+                    if constexpr (kArg)
+                        hipLaunchKernelGGL((fedopt_kernel_argmeta<DT, V, I::CU, I::G>), grid, block, 0, st, *src.m, n_segs,
+                                           n_clients, src.oc, src.o32, flags, h.b1, h.omb1, h.b2, h.omb2, h.eta, h.tau,
+                                           n_chunks);
+                    else
+                        hipLaunchKernelGGL((fedopt_kernel<DT, V, I::CU, I::G>), grid, block, 0, st, src.segs, n_segs,
+                                           src.clients, n_clients, src.r32, flags, h.b1, h.omb1, h.b2, h.omb2, h.eta,
+                                           h.tau, n_chunks);
+                }
+            });
+        });
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "%s: dtype %d not supported (f32, bf16, f16)", who, dtype);
+    if (multi) return launched((kArg ? BR_OPT_ARG_MULTI : BR_OPT_MULTI) + variant, who);
+    return launched((kArg ? BR_OPT_ARG : BR_OPT) + dtype * 3 + variant, who);
+}
+
+// ---------------------------------------------------------------- flame_hier_fedbuff[_argmeta]
+struct HierTables {
+    const flame_hier_segment* segs;
+    const uint64_t *mid_w, *mid_delta, *clients;
+    const float *mid_rates, *mid_goal, *top_rates;
+};
+struct HierArgMeta { const ArgMeta* m; int ow, od, oc, orr, og, ot; };
+
+int check_hier_flags(const char* who, unsigned flags, float top_goal) {
+    if (int rc = check_flags(who, flags, FLAME_HIER_TOP_ACCUM | FLAME_HIER_TOP_APPLY | FLAME_HIER_MID_READONLY | FLAME_HIER_SYNC))
+        return rc;
+    if ((flags & FLAME_HIER_SYNC) && ((flags & FLAME_HIER_TOP_APPLY) || !(flags & FLAME_HIER_TOP_ACCUM)))
+        return set_err(FLAME_EINVAL, "%s: FLAME_HIER_SYNC needs FLAME_HIER_TOP_ACCUM (the top's FedAvg starts from "
+                                     "its weights) and no FLAME_HIER_TOP_APPLY", who);
+    if ((flags & FLAME_HIER_TOP_APPLY) && top_goal == 0.f) return set_err(FLAME_EINVAL, "top agg_goal must be nonzero");
+    return FLAME_OK;
+}
+
+// Many middles (config 5: 64 per GPU): LDS-held store groups.  One middle over a long launch
+// (a FedBuff aggregator's fused scale_add / a middle's scale_add + delta over >= 64 queued
+// arrivals): fewer workgroups per CU, fewer loads in flight -- fp32 2 per CU, 16-bit 3 per CU,
+// unroll 3 (64 x 25M: 1.058 -> 0.989 ms fp32, 0.533 -> 0.509 ms bf16; tools/fedbuff_sweep.py,
+// profiles/r03zv_fedbuff_*.log).  Otherwise (small hierarchies): register groups, full residency.
+struct HierPick { bool lds, lo, sync; };
+HierPick pick_hier(unsigned flags, int32_t n_mids, int32_t n_clients, int64_t n_chunks) {
+    HierPick p;
+    p.sync = (flags & FLAME_HIER_SYNC) != 0;
+    p.lds = n_mids >= kHLdsMinMids;
+    p.lo = !p.lds && !p.sync && n_mids == 1 && n_clients >= kHLoMinClients && n_chunks >= kHLoMinChunks;
+    return p;
+}
+int hier_branch(const HierPick& p, bool argmeta, int dtype) {
+    if (p.lo) return (argmeta ? BR_HIER_ARG_LO : BR_HIER_LO) + dtype;
+    const int base = p.lds ? (argmeta ? BR_HIER_ARG_LDS : BR_HIER_LDS) : (argmeta ? BR_HIER_ARG : BR_HIER_REG);
+    return base + dtype * 2 + p.sync;
+}
+template <int DT_, bool LDS_, bool LO, bool SYNC_> struct HierInst {
+    static constexpr int DT = DT_;
+    static constexpr bool SYNC = SYNC_;
+    static constexpr int CU = LO ? kHLoUnroll : !is16(DT) ? kClientUnroll : LDS_ ? kHierLdsUnroll16 : kHierUnroll16;
+    static constexpr int HB = LDS_ ? kHBL : kHB;        // middles per store group
+    static constexpr bool HL = LDS_;                    // store groups held in LDS
+    static constexpr int LDS = !LO ? 0 : is16(DT) ? kHLoLds16 : kHLoLdsF32;   // a residency cap
+};
+// Calls f(HierInst<...>{}) for the instantiation p selects; false for a dtype without kernels
+template <typename F>
+inline bool dispatch_hier(int dtype, const HierPick& p, F&& f) {
+    return dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (p.lds) {
+            if (p.sync) f(HierInst<DT, true, false, true>{});
+            else f(HierInst<DT, true, false, false>{});
+        } else if (p.lo) {
+            f(HierInst<DT, false, true, false>{});
+        } else {
+            if (p.sync) f(HierInst<DT, false, false, true>{});
+            else f(HierInst<DT, false, false, false>{});
+        }
+    });
+}
+
+template <typename SRC>
+inline int launch_hier(const char* who, int dtype, unsigned flags, const SRC& src, int32_t n_segs, int64_t n_chunks,
+                       int32_t n_mids, int32_t n_clients, float top_goal, void* stream) {
+    constexpr bool kArg = std::is_same<SRC, HierArgMeta>::value;
+    const HierPick p = pick_hier(flags, n_mids, n_clients, n_chunks);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    const bool known = dispatch_hier(dtype, p, [&](auto inst) {
+        using I = decltype(inst);
+        if constexpr (kArg)
+            hipLaunchKernelGGL((hier_fedbuff_kernel_argmeta<I::DT, I::CU, I::SYNC, I::HB, I::HL>), grid, block, I::LDS, st,
+                               *src.m, n_segs, n_mids, n_clients, src.ow, src.od, src.oc, src.orr, src.og, src.ot,
+                               top_goal, flags);
+        else
+            hipLaunchKernelGGL((hier_fedbuff_kernel<I::DT, I::CU, I::SYNC, I::HB, I::HL>), grid, block, I::LDS, st,
+                               src.segs, n_segs, n_mids, n_clients, src.mid_w, src.mid_delta, src.clients, src.mid_rates,
+                               src.mid_goal, src.top_rates, top_goal, flags);
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "%s: dtype %d not supported (f32, bf16, f16)", who, dtype);
+    return launched(hier_branch(p, kArg, dtype), who);
 }
 
 }  // namespace
@@ -2426,133 +2684,49 @@ int flame_abi_version(void) { return FLAME_ABI_VERSION; }
 const char* flame_last_error(void) { return g_err; }
 
 int64_t flame_chunk_elems(int dtype) {
-    switch (dtype) {
-    case FLAME_F32: return chunk_elems<FLAME_F32>();
-    case FLAME_BF16: return chunk_elems<FLAME_BF16>();
-    case FLAME_F16: return chunk_elems<FLAME_F16>();
-    case FLAME_F64: return chunk_elems<FLAME_F64>();
-    case FLAME_I64: return chunk_elems<FLAME_I64>();
-    case FLAME_I32: return chunk_elems<FLAME_I32>();
-    default: return 0;
-    }
+    int64_t n = 0;
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64, FLAME_I64, FLAME_I32>(
+        dtype, [&](auto dt) { n = chunk_elems<decltype(dt)::value>(); });
+    return n;
 }
 
 int64_t flame_scale_add_chunk_elems(int dtype) {
-    switch (dtype) {
-    case FLAME_F32: return kEwBlock * SA<FLAME_F32>::EPT;
-    case FLAME_F64: return kEwBlock * SA<FLAME_F64>::EPT;
-    case FLAME_BF16: return kEwBlock * SA<FLAME_BF16>::EPT;
-    case FLAME_F16: return kEwBlock * SA<FLAME_F16>::EPT;
-    default: return 0;
-    }
+    int64_t n = 0;
+    dispatch<FLAME_F32, FLAME_F64, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) { n = kEwBlock * SA<decltype(dt)::value>::EPT; });
+    return n;
 }
 
 int flame_agg_reduce(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
                      const void* const* clients, int32_t n_clients, const float* rates32, const double* rates64,
                      void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
-    if (rc) return rc;
-    if ((flags & FLAME_AGG_INIT_FIRST) && n_clients < 1)
-        return set_err(FLAME_EINVAL, "FLAME_AGG_INIT_FIRST needs at least one client");
-    if (flags & ~(FLAME_AGG_INIT_FIRST | FLAME_AGG_SEG_RATES | FLAME_AGG_XCD_MAP))
-        return set_err(FLAME_EINVAL, "flame_agg_reduce: unknown flags 0x%x", flags);
+    const char* const who = "flame_agg_reduce";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
+    if (int rc = check_agg_flags(who, flags, n_clients)) return rc;
     if (dtype == FLAME_F64 ? (n_clients > 0 && !rates64) : (n_clients > 0 && !rates32))
         return set_err(FLAME_EINVAL, "rate array is NULL");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 block(kBlock);
-    auto cl = reinterpret_cast<const uint64_t*>(clients);
-#define FLAME_AGG_LAUNCH(DT, CUV, G, LDS, BR)                                                                   \
-    hipLaunchKernelGGL((agg_reduce_kernel<DT, CUV, G>), dim3(static_cast<unsigned>((n_chunks + G - 1) / G)),    \
-                       block, LDS, st, segs, n_segs, cl, n_clients, rates32, rates64, flags, n_chunks);         \
-    return launched(BR, "flame_agg_reduce");
-    // long-lived workgroups over many chunks: two per CU, fewer loads in flight per lane; below
-    // kLoBurstMaxClients clients with their outputs held in LDS and stored in bursts
-    if (n_clients >= kLoMinClients && n_chunks >= kLoMinChunks) {
-        if (n_clients < kLoBurstMaxClients) {
-            switch (dtype) {
-            case FLAME_F32: FLAME_AGG_LAUNCH(FLAME_F32, kLoUnroll, kLoWGC, kLoDynLds, BR_AGG_LOB + FLAME_F32)
-            case FLAME_BF16: FLAME_AGG_LAUNCH(FLAME_BF16, kLoUnroll16, kLoWGC, kLoDynLds, BR_AGG_LOB + FLAME_BF16)
-            case FLAME_F16: FLAME_AGG_LAUNCH(FLAME_F16, kLoUnroll16, kLoWGC, kLoDynLds, BR_AGG_LOB + FLAME_F16)
-            default: break;      // f64 / integers: the general launch below
-            }
-        }
-        switch (dtype) {
-        case FLAME_F32: FLAME_AGG_LAUNCH(FLAME_F32, kLoUnroll, 1, kLoLds, BR_AGG_LO + FLAME_F32)
-        case FLAME_BF16: FLAME_AGG_LAUNCH(FLAME_BF16, kLoUnroll16, 1, kLoLds, BR_AGG_LO + FLAME_BF16)
-        case FLAME_F16: FLAME_AGG_LAUNCH(FLAME_F16, kLoUnroll16, 1, kLoLds, BR_AGG_LO + FLAME_F16)
-        default: break;      // f64 / integers: the general launch below
-        }
-    }
-    switch (dtype) {
-    case FLAME_F32: FLAME_AGG_LAUNCH(FLAME_F32, kClientUnroll, 1, 0, BR_AGG + FLAME_F32)
-    case FLAME_BF16: FLAME_AGG_LAUNCH(FLAME_BF16, kClientUnroll16, 1, 0, BR_AGG + FLAME_BF16)
-    case FLAME_F16: FLAME_AGG_LAUNCH(FLAME_F16, kClientUnroll16, 1, 0, BR_AGG + FLAME_F16)
-    case FLAME_F64: FLAME_AGG_LAUNCH(FLAME_F64, kClientUnroll, 1, 0, BR_AGG + FLAME_F64)
-    case FLAME_I64: FLAME_AGG_LAUNCH(FLAME_I64, 4, 1, 0, BR_AGG + FLAME_I64)
-    case FLAME_I32: FLAME_AGG_LAUNCH(FLAME_I32, 4, 1, 0, BR_AGG + FLAME_I32)
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_agg_reduce: unsupported dtype %d", dtype);
-    }
-#undef FLAME_AGG_LAUNCH
+    const AggTables src{segs, reinterpret_cast<const uint64_t*>(clients), rates32, rates64};
+    return launch_agg(who, dtype, flags, src, n_segs, n_clients, n_chunks, stream);
 }
 
 int flame_agg_reduce_argmeta(int dtype, unsigned flags, const void* host_meta, int64_t meta_bytes, int32_t n_segs,
                              int64_t n_chunks, int32_t n_clients, int64_t off_clients, int64_t off_r32,
                              int64_t off_r64, void* stream) {
-    if (!host_meta || meta_bytes <= 0 || meta_bytes % 8 || meta_bytes > static_cast<int64_t>(sizeof(ArgMeta)))
-        return set_err(FLAME_EINVAL, "flame_agg_reduce_argmeta: metadata block must be 8..%d bytes, a multiple of 8",
-                       static_cast<int>(sizeof(ArgMeta)));
-    if (n_segs <= 0 || n_clients < 0) return set_err(FLAME_EINVAL, "flame_agg_reduce_argmeta: n_segs <= 0 or n_clients < 0");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
-    if ((flags & FLAME_AGG_INIT_FIRST) && n_clients < 1)
-        return set_err(FLAME_EINVAL, "FLAME_AGG_INIT_FIRST needs at least one client");
-    if (flags & ~(FLAME_AGG_INIT_FIRST | FLAME_AGG_SEG_RATES | FLAME_AGG_XCD_MAP))
-        return set_err(FLAME_EINVAL, "flame_agg_reduce_argmeta: unknown flags 0x%x", flags);
-    const int64_t rows = (flags & FLAME_AGG_SEG_RATES) ? n_segs : 1;
-    auto inside = [&](int64_t off, int64_t bytes) { return off >= 0 && off % 8 == 0 && off + bytes <= meta_bytes; };
-    if (static_cast<int64_t>(n_segs) * static_cast<int64_t>(sizeof(flame_segment)) > meta_bytes ||
-        !inside(off_clients, static_cast<int64_t>(n_segs) * n_clients * 8))
-        return set_err(FLAME_EINVAL, "flame_agg_reduce_argmeta: segment / client table outside the metadata block");
-    const bool f64 = dtype == FLAME_F64;
-    if (n_clients > 0 && (f64 ? !inside(off_r64, rows * n_clients * 8) : !inside(off_r32, rows * n_clients * 4)))
-        return set_err(FLAME_EINVAL, "flame_agg_reduce_argmeta: rate array outside the metadata block");
+    const char* const who = "flame_agg_reduce_argmeta";
     ArgMeta m;
-    std::memcpy(m.w, host_meta, static_cast<size_t>(meta_bytes));
-    const int oc = static_cast<int>(off_clients / 8);
-    const int o32 = (!f64 && n_clients > 0) ? static_cast<int>(off_r32 / 8) : -1;
-    const int o64 = (f64 && n_clients > 0) ? static_cast<int>(off_r64 / 8) : -1;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
-#define FLAME_ARGMETA_LAUNCH(DT, CUV) \
-    hipLaunchKernelGGL((agg_reduce_kernel_argmeta<DT, CUV, 1>), grid, block, 0, st, m, n_segs, n_clients, \
-                       oc, o32, o64, flags, n_chunks)
-    // a long launch with few segments (its table fits the kernel arguments): the same low-residency
-    // instantiation as flame_agg_reduce's
-    if (n_clients >= kLoMinClients && n_chunks >= kLoMinChunks &&
-        (dtype == FLAME_F32 || dtype == FLAME_BF16 || dtype == FLAME_F16)) {
-#define FLAME_ARGMETA_LO(DT, CUV, G, LDS)                                                                      \
-        hipLaunchKernelGGL((agg_reduce_kernel_argmeta<DT, CUV, G>), dim3(static_cast<unsigned>((n_chunks + G - 1) / G)), \
-                           block, LDS, st, m, n_segs, n_clients, oc, o32, o64, flags, n_chunks)
-        static_assert((kArgMetaWords - 10) < kLoBurstMaxClients,
-                      "a kernel-argument launch can hold kLoBurstMaxClients clients: it needs the plain instantiation too");
-        if (dtype == FLAME_F32) FLAME_ARGMETA_LO(FLAME_F32, kLoUnroll, kLoWGC, kLoDynLds);
-        else if (dtype == FLAME_BF16) FLAME_ARGMETA_LO(FLAME_BF16, kLoUnroll16, kLoWGC, kLoDynLds);
-        else FLAME_ARGMETA_LO(FLAME_F16, kLoUnroll16, kLoWGC, kLoDynLds);
-#undef FLAME_ARGMETA_LO
-        return launched(BR_AGG_ARG_LO + dtype, "flame_agg_reduce_argmeta");
-    }
-    switch (dtype) {
-    case FLAME_F32: FLAME_ARGMETA_LAUNCH(FLAME_F32, kClientUnroll); break;
-    case FLAME_BF16: FLAME_ARGMETA_LAUNCH(FLAME_BF16, kClientUnroll16); break;
-    case FLAME_F16: FLAME_ARGMETA_LAUNCH(FLAME_F16, kClientUnroll16); break;
-    case FLAME_F64: FLAME_ARGMETA_LAUNCH(FLAME_F64, kClientUnroll); break;
-    case FLAME_I64: FLAME_ARGMETA_LAUNCH(FLAME_I64, 4); break;
-    case FLAME_I32: FLAME_ARGMETA_LAUNCH(FLAME_I32, 4); break;
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_agg_reduce_argmeta: unsupported dtype %d", dtype);
-    }
-#undef FLAME_ARGMETA_LAUNCH
-    return launched(BR_AGG_ARG + dtype, "flame_agg_reduce_argmeta");
+    if (int rc = load_argmeta(who, host_meta, meta_bytes, m)) return rc;
+    if (n_segs <= 0 || n_clients < 0) return set_err(FLAME_EINVAL, "%s: n_segs <= 0 or n_clients < 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (int rc = check_agg_flags(who, flags, n_clients)) return rc;
+    const int64_t rows = (flags & FLAME_AGG_SEG_RATES) ? n_segs : 1;
+    if (static_cast<int64_t>(n_segs) * static_cast<int64_t>(sizeof(flame_segment)) > meta_bytes ||
+        !inside(meta_bytes, off_clients, static_cast<int64_t>(n_segs) * n_clients * 8))
+        return set_err(FLAME_EINVAL, "%s: segment / client table outside the metadata block", who);
+    const bool f64 = dtype == FLAME_F64;
+    if (n_clients > 0 && !(f64 ? inside(meta_bytes, off_r64, rows * n_clients * 8) : inside(meta_bytes, off_r32, rows * n_clients * 4)))
+        return set_err(FLAME_EINVAL, "%s: rate array outside the metadata block", who);
+    const AggArgMeta src{&m, static_cast<int>(off_clients / 8), (!f64 && n_clients > 0) ? static_cast<int>(off_r32 / 8) : -1,
+                         (f64 && n_clients > 0) ? static_cast<int>(off_r64 / 8) : -1};
+    return launch_agg(who, dtype, flags, src, n_segs, n_clients, n_chunks, stream);
 }
 
 int64_t flame_agg_argmeta_max_bytes(void) { return static_cast<int64_t>(sizeof(ArgMeta)); }
@@ -2561,206 +2735,115 @@ int flame_fedopt_reduce_adapt(int dtype, int variant, unsigned flags, const flam
                               int64_t n_chunks, const void* const* clients, int32_t n_clients,
                               const float* rates32, float b1, float omb1, float b2, float omb2, float eta,
                               float tau, void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
-    if (rc) return rc;
+    const char* const who = "flame_fedopt_reduce_adapt";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
     if (n_clients > 0 && !rates32) return set_err(FLAME_EINVAL, "rate array is NULL");
-    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt: unknown variant %d", variant);
-    if (flags & ~(FLAME_OPT_STATE_ZERO | FLAME_OPT_XCD_MAP))
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt: unknown flags 0x%x", flags);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // kOptWGC chunks per workgroup (outputs held in LDS) for fp32 launches big enough to fill
-    // the GPU several times over; one chunk per workgroup otherwise
-    const bool multi = dtype == FLAME_F32 && n_chunks >= 8ll * 256 * kOptWGC;
-    const dim3 grid(static_cast<unsigned>(multi ? (n_chunks + kOptWGC - 1) / kOptWGC : n_chunks)), block(kBlock);
-    auto cl = reinterpret_cast<const uint64_t*>(clients);
-#define FLAME_OPT_LAUNCH1(DT, CUV, G)                                                                          \
-    switch (variant) {                                                                                         \
-    case FLAME_FEDADAM:                                                                                        \
-        hipLaunchKernelGGL((fedopt_kernel<DT, FLAME_FEDADAM, CUV, G>), grid, block, 0, st, segs, n_segs, cl,    \
-                           n_clients, rates32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                 \
-        break;                                                                                                 \
-    case FLAME_FEDYOGI:                                                                                        \
-        hipLaunchKernelGGL((fedopt_kernel<DT, FLAME_FEDYOGI, CUV, G>), grid, block, 0, st, segs, n_segs, cl,    \
-                           n_clients, rates32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                 \
-        break;                                                                                                 \
-    default:                                                                                                   \
-        hipLaunchKernelGGL((fedopt_kernel<DT, FLAME_FEDADAGRAD, CUV, G>), grid, block, 0, st, segs, n_segs, cl, \
-                           n_clients, rates32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                 \
-        break;                                                                                                 \
-    }
-    switch (dtype) {
-    case FLAME_F32:
-        if (multi) { FLAME_OPT_LAUNCH1(FLAME_F32, kOptUnroll, kOptWGC) }
-        else { FLAME_OPT_LAUNCH1(FLAME_F32, kClientUnroll, 1) }
-        break;
-    case FLAME_BF16: FLAME_OPT_LAUNCH1(FLAME_BF16, kClientUnroll16, 1) break;
-    case FLAME_F16: FLAME_OPT_LAUNCH1(FLAME_F16, kClientUnroll16, 1) break;
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt: dtype %d not supported (f32, bf16, f16)", dtype);
-    }
-#undef FLAME_OPT_LAUNCH1
-    return launched(multi ? BR_OPT_MULTI + variant : BR_OPT + dtype * 3 + variant, "flame_fedopt_reduce_adapt");
+    if (int rc = check_variant(who, variant)) return rc;
+    if (int rc = check_flags(who, flags, kOptFlags)) return rc;
+    const OptTables src{segs, reinterpret_cast<const uint64_t*>(clients), rates32};
+    return launch_opt(who, dtype, variant, flags, src, n_segs, n_clients, n_chunks, Hyper32{b1, omb1, b2, omb2, eta, tau},
+                      stream);
 }
 
 int flame_fedopt_chain(int dtype, int variant, unsigned flags, const flame_segment* segs, int32_t n_segs,
                        int64_t n_chunks, const void* const* clients, int32_t n_clients, const float* rates32,
                        const uint8_t* step_end, float b1, float omb1, float b2, float omb2, float eta, float tau,
                        void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
-    if (rc) return rc;
+    const char* const who = "flame_fedopt_chain";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
     if (n_clients < 1 || !rates32 || !step_end)
-        return set_err(FLAME_EINVAL, "flame_fedopt_chain: needs >= 1 client, a rate array and a step_end array");
-    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_chain: unknown variant %d", variant);
-    if (flags & ~FLAME_OPT_STATE_ZERO) return set_err(FLAME_EINVAL, "flame_fedopt_chain: unknown flags 0x%x", flags);
-    if (dtype != FLAME_F32 && dtype != FLAME_BF16 && dtype != FLAME_F16)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_chain: dtype %d not supported (f32, bf16, f16)", dtype);
+        return set_err(FLAME_EINVAL, "%s: needs >= 1 client, a rate array and a step_end array", who);
+    if (int rc = check_variant(who, variant)) return rc;
+    if (int rc = check_flags(who, flags, FLAME_OPT_STATE_ZERO)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
     auto cl = reinterpret_cast<const uint64_t*>(clients);
-#define FLAME_CHAIN_LAUNCH(DT, V, CUV)                                                                              \
-    hipLaunchKernelGGL((fedopt_chain_kernel<DT, V, CUV>), grid, block, DT == FLAME_F32 ? kChainLds : 0, st, segs,   \
-                       n_segs, cl, n_clients,                                                                       \
-                       rates32,                                                                                     \
-                       step_end, flags, b1, omb1, b2, omb2, eta, tau)
-#define FLAME_CHAIN_VARIANTS(DT, CUV)                                                  \
-    if (variant == FLAME_FEDADAM) FLAME_CHAIN_LAUNCH(DT, FLAME_FEDADAM, CUV);          \
-    else if (variant == FLAME_FEDYOGI) FLAME_CHAIN_LAUNCH(DT, FLAME_FEDYOGI, CUV);     \
-    else FLAME_CHAIN_LAUNCH(DT, FLAME_FEDADAGRAD, CUV);
-    if (dtype == FLAME_F32) { FLAME_CHAIN_VARIANTS(FLAME_F32, kChainUnroll) }
-    else if (dtype == FLAME_BF16) { FLAME_CHAIN_VARIANTS(FLAME_BF16, kChainUnroll16) }
-    else { FLAME_CHAIN_VARIANTS(FLAME_F16, kChainUnroll16) }
-#undef FLAME_CHAIN_VARIANTS
-#undef FLAME_CHAIN_LAUNCH
-    return launched(BR_CHAIN + dtype * 3 + variant, "flame_fedopt_chain");
+    const bool known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) {
+        dispatch_variant(variant, [&](auto vr) {
+            constexpr int DT = decltype(dt)::value, V = decltype(vr)::value;
+            constexpr int CU = is16(DT) ? kChainUnroll16 : kChainUnroll;
+            hipLaunchKernelGGL((fedopt_chain_kernel<DT, V, CU>), grid, block, DT == FLAME_F32 ? kChainLds : 0, st, segs,
+                               n_segs, cl, n_clients, rates32, step_end, flags, b1, omb1, b2, omb2, eta, tau);
+        });
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "%s: dtype %d not supported (f32, bf16, f16)", who, dtype);
+    return launched(BR_CHAIN + dtype * 3 + variant, who);
 }
 
 int flame_fedopt_reduce_adapt_f64(int variant, unsigned flags, const flame_segment* segs, int32_t n_segs,
                                   int64_t n_chunks, const void* const* clients, int32_t n_clients,
                                   const double* rates64, double b1, double omb1, double b2, double omb2, double eta,
                                   double tau, void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
-    if (rc) return rc;
+    const char* const who = "flame_fedopt_reduce_adapt_f64";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
     if (n_clients > 0 && !rates64) return set_err(FLAME_EINVAL, "rate array is NULL");
-    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt_f64: unknown variant %d", variant);
-    if (flags & ~(FLAME_OPT_STATE_ZERO | FLAME_OPT_XCD_MAP))
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_f64: unknown flags 0x%x", flags);
+    if (int rc = check_variant(who, variant)) return rc;
+    if (int rc = check_flags(who, flags, kOptFlags)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
     auto cl = reinterpret_cast<const uint64_t*>(clients);
     const Hyper64 h{b1, omb1, b2, omb2, eta, tau};
-#define FLAME_OPT64_LAUNCH(V)                                                                                   \
-    hipLaunchKernelGGL((fedopt_kernel_f64<V, kClientUnroll>), grid, block, 0, st, segs, n_segs, cl, n_clients,  \
-                       rates64, flags, h, n_chunks)
-    if (variant == FLAME_FEDADAM) FLAME_OPT64_LAUNCH(FLAME_FEDADAM);
-    else if (variant == FLAME_FEDYOGI) FLAME_OPT64_LAUNCH(FLAME_FEDYOGI);
-    else FLAME_OPT64_LAUNCH(FLAME_FEDADAGRAD);
-#undef FLAME_OPT64_LAUNCH
-    return launched(BR_OPT_F64 + variant, "flame_fedopt_reduce_adapt_f64");
+    dispatch_variant(variant, [&](auto vr) {
+        hipLaunchKernelGGL((fedopt_kernel_f64<decltype(vr)::value, kClientUnroll>), grid, block, 0, st, segs, n_segs, cl,
+                           n_clients, rates64, flags, h, n_chunks);
+    });
+    return launched(BR_OPT_F64 + variant, who);
 }
 
 int flame_fedopt_chain_f64(int variant, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
                            const void* const* clients, int32_t n_clients, const double* rates64,
                            const uint8_t* step_end, double b1, double omb1, double b2, double omb2, double eta,
                            double tau, void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, n_clients, clients);
-    if (rc) return rc;
+    const char* const who = "flame_fedopt_chain_f64";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
     if (n_clients < 1 || !rates64 || !step_end)
-        return set_err(FLAME_EINVAL, "flame_fedopt_chain_f64: needs >= 1 client, a rate array and a step_end array");
-    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_chain_f64: unknown variant %d", variant);
-    if (flags & ~FLAME_OPT_STATE_ZERO)
-        return set_err(FLAME_EINVAL, "flame_fedopt_chain_f64: unknown flags 0x%x", flags);
+        return set_err(FLAME_EINVAL, "%s: needs >= 1 client, a rate array and a step_end array", who);
+    if (int rc = check_variant(who, variant)) return rc;
+    if (int rc = check_flags(who, flags, FLAME_OPT_STATE_ZERO)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
     auto cl = reinterpret_cast<const uint64_t*>(clients);
     const Hyper64 h{b1, omb1, b2, omb2, eta, tau};
-#define FLAME_CHAIN64_LAUNCH(V)                                                                                     \
-    hipLaunchKernelGGL((fedopt_chain_kernel_f64<V, kClientUnroll>), grid, block, 0, st, segs, n_segs, cl, n_clients, \
-                       rates64, step_end, flags, h)
-    if (variant == FLAME_FEDADAM) FLAME_CHAIN64_LAUNCH(FLAME_FEDADAM);
-    else if (variant == FLAME_FEDYOGI) FLAME_CHAIN64_LAUNCH(FLAME_FEDYOGI);
-    else FLAME_CHAIN64_LAUNCH(FLAME_FEDADAGRAD);
-#undef FLAME_CHAIN64_LAUNCH
-    return launched(BR_CHAIN_F64 + variant, "flame_fedopt_chain_f64");
+    dispatch_variant(variant, [&](auto vr) {
+        hipLaunchKernelGGL((fedopt_chain_kernel_f64<decltype(vr)::value, kClientUnroll>), grid, block, 0, st, segs, n_segs,
+                           cl, n_clients, rates64, step_end, flags, h);
+    });
+    return launched(BR_CHAIN_F64 + variant, who);
 }
 
 int flame_fedopt_reduce_adapt_argmeta(int dtype, int variant, unsigned flags, const void* host_meta,
                                       int64_t meta_bytes, int32_t n_segs, int64_t n_chunks, int32_t n_clients,
                                       int64_t off_clients, int64_t off_r32, float b1, float omb1, float b2,
                                       float omb2, float eta, float tau, void* stream) {
-    if (!host_meta || meta_bytes <= 0 || meta_bytes % 8 || meta_bytes > static_cast<int64_t>(sizeof(ArgMeta)))
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_argmeta: metadata block must be 8..%d bytes, a multiple of 8",
-                       static_cast<int>(sizeof(ArgMeta)));
-    if (n_segs <= 0 || n_clients < 0)
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_argmeta: n_segs <= 0 or n_clients < 0");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
-    if (flags & ~(FLAME_OPT_STATE_ZERO | FLAME_OPT_XCD_MAP))
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_argmeta: unknown flags 0x%x", flags);
-    if (variant < FLAME_FEDADAM || variant > FLAME_FEDADAGRAD)
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt_argmeta: unknown variant %d", variant);
-    auto inside = [&](int64_t off, int64_t bytes) { return off >= 0 && off % 8 == 0 && off + bytes <= meta_bytes; };
-    if (static_cast<int64_t>(n_segs) * static_cast<int64_t>(sizeof(flame_segment)) > meta_bytes ||
-        !inside(off_clients, static_cast<int64_t>(n_segs) * n_clients * 8) ||
-        (n_clients > 0 && !inside(off_r32, static_cast<int64_t>(n_clients) * 4)))
-        return set_err(FLAME_EINVAL, "flame_fedopt_reduce_adapt_argmeta: a table lies outside the metadata block");
+    const char* const who = "flame_fedopt_reduce_adapt_argmeta";
     ArgMeta m;
-    std::memcpy(m.w, host_meta, static_cast<size_t>(meta_bytes));
-    const int oc = static_cast<int>(off_clients / 8);
-    const int o32 = n_clients > 0 ? static_cast<int>(off_r32 / 8) : -1;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    // the instantiation flame_fedopt_reduce_adapt picks for the same launch
-    const bool multi = dtype == FLAME_F32 && n_chunks >= 8ll * 256 * kOptWGC;
-    const dim3 grid(static_cast<unsigned>(multi ? (n_chunks + kOptWGC - 1) / kOptWGC : n_chunks)), block(kBlock);
-#define FLAME_OPT_ARGMETA_LAUNCH(DT, CUV, G)                                                                     \
-    switch (variant) {                                                                                           \
-    case FLAME_FEDADAM:                                                                                          \
-        hipLaunchKernelGGL((fedopt_kernel_argmeta<DT, FLAME_FEDADAM, CUV, G>), grid, block, 0, st, m, n_segs,     \
-                           n_clients, oc, o32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                   \
-        break;                                                                                                   \
-    case FLAME_FEDYOGI:                                                                                          \
-        hipLaunchKernelGGL((fedopt_kernel_argmeta<DT, FLAME_FEDYOGI, CUV, G>), grid, block, 0, st, m, n_segs,     \
-                           n_clients, oc, o32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                   \
-        break;                                                                                                   \
-    default:                                                                                                     \
-        hipLaunchKernelGGL((fedopt_kernel_argmeta<DT, FLAME_FEDADAGRAD, CUV, G>), grid, block, 0, st, m, n_segs,  \
-                           n_clients, oc, o32, flags, b1, omb1, b2, omb2, eta, tau, n_chunks);                   \
-        break;                                                                                                   \
-    }
-    switch (dtype) {
-    case FLAME_F32:
-        if (multi) { FLAME_OPT_ARGMETA_LAUNCH(FLAME_F32, kOptUnroll, kOptWGC) }
-        else { FLAME_OPT_ARGMETA_LAUNCH(FLAME_F32, kClientUnroll, 1) }
-        break;
-    case FLAME_BF16: FLAME_OPT_ARGMETA_LAUNCH(FLAME_BF16, kClientUnroll16, 1) break;
-    case FLAME_F16: FLAME_OPT_ARGMETA_LAUNCH(FLAME_F16, kClientUnroll16, 1) break;
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_fedopt_reduce_adapt_argmeta: dtype %d not supported (f32, bf16, f16)", dtype);
-    }
-#undef FLAME_OPT_ARGMETA_LAUNCH
-    if (multi) return launched(BR_OPT_ARG_MULTI + variant, "flame_fedopt_reduce_adapt_argmeta");
-    return launched(BR_OPT_ARG + dtype * 3 + variant, "flame_fedopt_reduce_adapt_argmeta");
+    if (int rc = load_argmeta(who, host_meta, meta_bytes, m)) return rc;
+    if (n_segs <= 0 || n_clients < 0) return set_err(FLAME_EINVAL, "%s: n_segs <= 0 or n_clients < 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (int rc = check_flags(who, flags, kOptFlags)) return rc;
+    if (int rc = check_variant(who, variant)) return rc;
+    if (static_cast<int64_t>(n_segs) * static_cast<int64_t>(sizeof(flame_segment)) > meta_bytes ||
+        !inside(meta_bytes, off_clients, static_cast<int64_t>(n_segs) * n_clients * 8) ||
+        (n_clients > 0 && !inside(meta_bytes, off_r32, static_cast<int64_t>(n_clients) * 4)))
+        return set_err(FLAME_EINVAL, "%s: a table lies outside the metadata block", who);
+    const OptArgMeta src{&m, static_cast<int>(off_clients / 8), n_clients > 0 ? static_cast<int>(off_r32 / 8) : -1};
+    return launch_opt(who, dtype, variant, flags, src, n_segs, n_clients, n_chunks, Hyper32{b1, omb1, b2, omb2, eta, tau},
+                      stream);
 }
 
 int flame_fedbuff_scale_add(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks, int64_t goal,
                             void* stream) {
-    int rc = validate(segs, n_segs, n_chunks, 0, nullptr);
-    if (rc) return rc;
+    if (int rc = validate(segs, n_segs, n_chunks, 0, nullptr)) return rc;
     if (goal == 0) return set_err(FLAME_EINVAL, "agg_goal must be nonzero");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(static_cast<unsigned>(n_chunks)), block(kEwBlock);
     const float gf = static_cast<float>(goal);
     const double gd = static_cast<double>(goal);
-    switch (dtype) {
-    case FLAME_F32: hipLaunchKernelGGL((scale_add_kernel<FLAME_F32>), grid, block, 0, st, segs, n_segs, gf, gd); break;
-    case FLAME_F64: hipLaunchKernelGGL((scale_add_kernel<FLAME_F64>), grid, block, 0, st, segs, n_segs, gf, gd); break;
-    case FLAME_BF16: hipLaunchKernelGGL((scale_add_kernel<FLAME_BF16>), grid, block, 0, st, segs, n_segs, gf, gd); break;
-    case FLAME_F16: hipLaunchKernelGGL((scale_add_kernel<FLAME_F16>), grid, block, 0, st, segs, n_segs, gf, gd); break;
-    default:
+    const bool known = dispatch<FLAME_F32, FLAME_F64, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((scale_add_kernel<decltype(dt)::value>), grid, block, 0, st, segs, n_segs, gf, gd);
+    });
+    if (!known)
         return set_err(FLAME_ENOTSUP, "flame_fedbuff_scale_add: dtype %d not supported (integer tensors raise in the reference)", dtype);
-    }
     return launched(BR_SA + dtype, "flame_fedbuff_scale_add");
 }
 
@@ -2768,142 +2851,52 @@ int flame_hier_fedbuff(int dtype, unsigned flags, const flame_hier_segment* segs
                        int32_t n_mids, int32_t n_clients, const void* const* mid_w, const void* const* mid_delta,
                        const void* const* clients, const float* mid_rates, const float* mid_goal,
                        const float* top_rates, float top_goal, void* stream) {
+    const char* const who = "flame_hier_fedbuff";
     if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is NULL or n_segs <= 0");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
-    if (n_mids < 1 || n_clients < 1) return set_err(FLAME_EINVAL, "flame_hier_fedbuff: need >= 1 middle and >= 1 arrival per middle");
-    if (!mid_w || !clients || !mid_rates || !mid_goal || !top_rates)
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff: NULL table");
-    if (flags & ~(FLAME_HIER_TOP_ACCUM | FLAME_HIER_TOP_APPLY | FLAME_HIER_MID_READONLY | FLAME_HIER_SYNC))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff: unknown flags 0x%x", flags);
-    if ((flags & FLAME_HIER_SYNC) && ((flags & FLAME_HIER_TOP_APPLY) || !(flags & FLAME_HIER_TOP_ACCUM)))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff: FLAME_HIER_SYNC needs FLAME_HIER_TOP_ACCUM (the top's "
-                                     "FedAvg starts from its weights) and no FLAME_HIER_TOP_APPLY");
-    if ((flags & FLAME_HIER_TOP_APPLY) && top_goal == 0.f) return set_err(FLAME_EINVAL, "top agg_goal must be nonzero");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
-    auto w = reinterpret_cast<const uint64_t*>(mid_w);
-    auto d = reinterpret_cast<const uint64_t*>(mid_delta);
-    auto cl = reinterpret_cast<const uint64_t*>(clients);
-    const bool sync = (flags & FLAME_HIER_SYNC) != 0;
-    // many middles (config 5: 64 per GPU): LDS-held store groups.  One middle over a long launch
-    // (a FedBuff aggregator's fused scale_add / a middle's scale_add + delta over >= 64 queued
-    // arrivals): fewer workgroups per CU, fewer loads in flight -- fp32 2 per CU, 16-bit 3 per CU,
-    // unroll 3 (64 x 25M: 1.058 -> 0.989 ms fp32, 0.533 -> 0.509 ms bf16; tools/fedbuff_sweep.py,
-    // profiles/r03zv_fedbuff_*.log).  Otherwise (small hierarchies): register groups, full residency.
-    const bool lds = n_mids >= kHLdsMinMids;
-    const bool lo = !lds && !sync && n_mids == 1 && n_clients >= kHLoMinClients && n_chunks >= kHLoMinChunks;
-#define FLAME_HIER_GO(DT, CUV, SY, HB, HL, LDSB)                                                              \
-    hipLaunchKernelGGL((hier_fedbuff_kernel<DT, CUV, SY, HB, HL>), grid, block, LDSB, st, segs, n_segs, n_mids, \
-                       n_clients, w, d, cl, mid_rates, mid_goal, top_rates, top_goal, flags)
-#define FLAME_HIER_LAUNCH(DT, CUV, CUL, LOLDS)                                                                  \
-    if (lds) {                                                                                                 \
-        if (sync) FLAME_HIER_GO(DT, CUL, true, kHBL, true, 0);                                                 \
-        else FLAME_HIER_GO(DT, CUL, false, kHBL, true, 0);                                                     \
-        br = BR_HIER_LDS + DT * 2 + sync;                                                                      \
-    } else if (lo) {                                                                                           \
-        FLAME_HIER_GO(DT, kHLoUnroll, false, kHB, false, LOLDS);                                               \
-        br = BR_HIER_LO + DT;                                                                                  \
-    } else {                                                                                                   \
-        if (sync) FLAME_HIER_GO(DT, CUV, true, kHB, false, 0);                                                 \
-        else FLAME_HIER_GO(DT, CUV, false, kHB, false, 0);                                                     \
-        br = BR_HIER_REG + DT * 2 + sync;                                                                      \
-    }
-    int br = 0;
-    switch (dtype) {
-    case FLAME_F32: FLAME_HIER_LAUNCH(FLAME_F32, kClientUnroll, kClientUnroll, kHLoLdsF32) break;
-    case FLAME_BF16: FLAME_HIER_LAUNCH(FLAME_BF16, kHierUnroll16, kHierLdsUnroll16, kHLoLds16) break;
-    case FLAME_F16: FLAME_HIER_LAUNCH(FLAME_F16, kHierUnroll16, kHierLdsUnroll16, kHLoLds16) break;
-#undef FLAME_HIER_GO
-#undef FLAME_HIER_LAUNCH
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_hier_fedbuff: dtype %d not supported (f32, bf16, f16)", dtype);
-    }
-    return launched(br, "flame_hier_fedbuff");
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (n_mids < 1 || n_clients < 1) return set_err(FLAME_EINVAL, "%s: need >= 1 middle and >= 1 arrival per middle", who);
+    if (!mid_w || !clients || !mid_rates || !mid_goal || !top_rates) return set_err(FLAME_EINVAL, "%s: NULL table", who);
+    if (int rc = check_hier_flags(who, flags, top_goal)) return rc;
+    const HierTables src{segs, reinterpret_cast<const uint64_t*>(mid_w), reinterpret_cast<const uint64_t*>(mid_delta),
+                         reinterpret_cast<const uint64_t*>(clients), mid_rates, mid_goal, top_rates};
+    return launch_hier(who, dtype, flags, src, n_segs, n_chunks, n_mids, n_clients, top_goal, stream);
 }
 
 int flame_hier_fedbuff_argmeta(int dtype, unsigned flags, const void* host_meta, int64_t meta_bytes, int32_t n_segs,
                                int64_t n_chunks, int32_t n_mids, int32_t n_clients, int64_t off_mid_w,
                                int64_t off_mid_delta, int64_t off_clients, int64_t off_mid_rates,
                                int64_t off_mid_goal, int64_t off_top_rates, float top_goal, void* stream) {
-    if (!host_meta || meta_bytes <= 0 || meta_bytes % 8 || meta_bytes > static_cast<int64_t>(sizeof(ArgMeta)))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff_argmeta: metadata block must be 8..%d bytes, a multiple of 8",
-                       static_cast<int>(sizeof(ArgMeta)));
-    if (n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is empty");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
-    if (n_mids < 1 || n_clients < 1) return set_err(FLAME_EINVAL, "flame_hier_fedbuff_argmeta: need >= 1 middle and >= 1 arrival per middle");
-    if (flags & ~(FLAME_HIER_TOP_ACCUM | FLAME_HIER_TOP_APPLY | FLAME_HIER_MID_READONLY | FLAME_HIER_SYNC))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff_argmeta: unknown flags 0x%x", flags);
-    if ((flags & FLAME_HIER_SYNC) && ((flags & FLAME_HIER_TOP_APPLY) || !(flags & FLAME_HIER_TOP_ACCUM)))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff_argmeta: FLAME_HIER_SYNC needs FLAME_HIER_TOP_ACCUM and no FLAME_HIER_TOP_APPLY");
-    if ((flags & FLAME_HIER_TOP_APPLY) && top_goal == 0.f) return set_err(FLAME_EINVAL, "top agg_goal must be nonzero");
-    auto inside = [&](int64_t off, int64_t bytes) { return off >= 0 && off % 8 == 0 && off + bytes <= meta_bytes; };
-    const int64_t S = n_segs, M = n_mids, C = n_clients;
-    if (S * static_cast<int64_t>(sizeof(flame_hier_segment)) > meta_bytes || !inside(off_mid_w, S * M * 8) ||
-        (off_mid_delta >= 0 && !inside(off_mid_delta, S * M * 8)) || !inside(off_clients, S * M * C * 8) ||
-        !inside(off_mid_rates, M * C * 4) || !inside(off_mid_goal, M * 4) || !inside(off_top_rates, M * 4))
-        return set_err(FLAME_EINVAL, "flame_hier_fedbuff_argmeta: a table lies outside the metadata block");
+    const char* const who = "flame_hier_fedbuff_argmeta";
     ArgMeta m;
-    std::memcpy(m.w, host_meta, static_cast<size_t>(meta_bytes));
-    const int ow = static_cast<int>(off_mid_w / 8), od = off_mid_delta >= 0 ? static_cast<int>(off_mid_delta / 8) : -1;
-    const int oc = static_cast<int>(off_clients / 8), orr = static_cast<int>(off_mid_rates / 8);
-    const int og = static_cast<int>(off_mid_goal / 8), ot = static_cast<int>(off_top_rates / 8);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
-    const bool sync = (flags & FLAME_HIER_SYNC) != 0;
-    // the instantiation flame_hier_fedbuff picks for the same launch shape: LDS store groups for
-    // many middles, the low-residency one for one middle over a long launch (a FedBuff
-    // aggregator's fused scale_add of >= 64 arrivals into a model of a few keys), else register groups
-    const bool lds = n_mids >= kHLdsMinMids;
-    const bool lo = !lds && !sync && n_mids == 1 && n_clients >= kHLoMinClients && n_chunks >= kHLoMinChunks;
-#define FLAME_HIER_ARG_GO(DT, CUV, SY, HB, HL, LDSB)                                                            \
-    hipLaunchKernelGGL((hier_fedbuff_kernel_argmeta<DT, CUV, SY, HB, HL>), grid, block, LDSB, st, m, n_segs, n_mids, \
-                       n_clients, ow, od, oc, orr, og, ot, top_goal, flags)
-#define FLAME_HIER_ARG_LAUNCH(DT, CUV, CUL, LOLDS)                                                              \
-    if (lds) {                                                                                                 \
-        if (sync) FLAME_HIER_ARG_GO(DT, CUL, true, kHBL, true, 0);                                             \
-        else FLAME_HIER_ARG_GO(DT, CUL, false, kHBL, true, 0);                                                 \
-        br = BR_HIER_ARG_LDS + DT * 2 + sync;                                                                  \
-    } else if (lo) {                                                                                           \
-        FLAME_HIER_ARG_GO(DT, kHLoUnroll, false, kHB, false, LOLDS);                                           \
-        br = BR_HIER_ARG_LO + DT;                                                                              \
-    } else {                                                                                                   \
-        if (sync) FLAME_HIER_ARG_GO(DT, CUV, true, kHB, false, 0);                                             \
-        else FLAME_HIER_ARG_GO(DT, CUV, false, kHB, false, 0);                                                 \
-        br = BR_HIER_ARG + DT * 2 + sync;                                                                      \
-    }
-    int br = 0;
-    switch (dtype) {
-    case FLAME_F32: FLAME_HIER_ARG_LAUNCH(FLAME_F32, kClientUnroll, kClientUnroll, kHLoLdsF32) break;
-    case FLAME_BF16: FLAME_HIER_ARG_LAUNCH(FLAME_BF16, kHierUnroll16, kHierLdsUnroll16, kHLoLds16) break;
-    case FLAME_F16: FLAME_HIER_ARG_LAUNCH(FLAME_F16, kHierUnroll16, kHierLdsUnroll16, kHLoLds16) break;
-#undef FLAME_HIER_ARG_GO
-#undef FLAME_HIER_ARG_LAUNCH
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_hier_fedbuff_argmeta: dtype %d not supported (f32, bf16, f16)", dtype);
-    }
-    return launched(br, "flame_hier_fedbuff_argmeta");
+    if (int rc = load_argmeta(who, host_meta, meta_bytes, m)) return rc;
+    if (n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is empty");
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (n_mids < 1 || n_clients < 1) return set_err(FLAME_EINVAL, "%s: need >= 1 middle and >= 1 arrival per middle", who);
+    if (int rc = check_hier_flags(who, flags, top_goal)) return rc;
+    const int64_t S = n_segs, M = n_mids, C = n_clients;
+    if (S * static_cast<int64_t>(sizeof(flame_hier_segment)) > meta_bytes || !inside(meta_bytes, off_mid_w, S * M * 8) ||
+        (off_mid_delta >= 0 && !inside(meta_bytes, off_mid_delta, S * M * 8)) ||
+        !inside(meta_bytes, off_clients, S * M * C * 8) || !inside(meta_bytes, off_mid_rates, M * C * 4) ||
+        !inside(meta_bytes, off_mid_goal, M * 4) || !inside(meta_bytes, off_top_rates, M * 4))
+        return set_err(FLAME_EINVAL, "%s: a table lies outside the metadata block", who);
+    const HierArgMeta src{&m, static_cast<int>(off_mid_w / 8), off_mid_delta >= 0 ? static_cast<int>(off_mid_delta / 8) : -1,
+                          static_cast<int>(off_clients / 8), static_cast<int>(off_mid_rates / 8),
+                          static_cast<int>(off_mid_goal / 8), static_cast<int>(off_top_rates / 8)};
+    return launch_hier(who, dtype, flags, src, n_segs, n_chunks, n_mids, n_clients, top_goal, stream);
 }
 
 int flame_hier_resident_per_cu(int dtype, unsigned flags, int32_t n_mids) {
     if (n_mids < 1) return -set_err(FLAME_EINVAL, "flame_hier_resident_per_cu: n_mids < 1");
-    const bool sync = (flags & FLAME_HIER_SYNC) != 0;
-    const bool lds = n_mids >= kHLdsMinMids;
+    // the one-middle low-residency launch aside, which depends on the launch size
+    HierPick p = pick_hier(flags, n_mids, 0, 0);
+    p.lo = false;
     const void* f = nullptr;
-    // the instantiation flame_hier_fedbuff picks for these arguments (the one-middle low-residency
-    // launch aside, which depends on the launch size)
-#define FLAME_HIER_PICK(DT, CUV, CUL)                                                                          \
-    if (lds) f = sync ? reinterpret_cast<const void*>(hier_fedbuff_kernel<DT, CUL, true, kHBL, true>)          \
-                      : reinterpret_cast<const void*>(hier_fedbuff_kernel<DT, CUL, false, kHBL, true>);        \
-    else f = sync ? reinterpret_cast<const void*>(hier_fedbuff_kernel<DT, CUV, true, kHB, false>)              \
-                  : reinterpret_cast<const void*>(hier_fedbuff_kernel<DT, CUV, false, kHB, false>);
-    switch (dtype) {
-    case FLAME_F32: FLAME_HIER_PICK(FLAME_F32, kClientUnroll, kClientUnroll) break;
-    case FLAME_BF16: FLAME_HIER_PICK(FLAME_BF16, kHierUnroll16, kHierLdsUnroll16) break;
-    case FLAME_F16: FLAME_HIER_PICK(FLAME_F16, kHierUnroll16, kHierLdsUnroll16) break;
-#undef FLAME_HIER_PICK
-    default:
+    const bool known = dispatch_hier(dtype, p, [&](auto inst) {
+        using I = decltype(inst);
+        f = reinterpret_cast<const void*>(hier_fedbuff_kernel<I::DT, I::CU, I::SYNC, I::HB, I::HL>);
+    });
+    if (!known)
         return -set_err(FLAME_ENOTSUP, "flame_hier_resident_per_cu: dtype %d not supported (f32, bf16, f16)", dtype);
-    }
     int blocks = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, f, kBlock, 0);
     if (e != hipSuccess) return -set_err(FLAME_EHIP, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
@@ -2914,7 +2907,7 @@ int flame_feddyn_round(int dtype, const flame_dyn_segment* segs, int32_t n_segs,
                        const void* const* steps, const uint32_t* step_flags, int32_t n_steps, int32_t n_phase1,
                        double rate_avg, double rate_mean, void* stream) {
     if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is NULL or n_segs <= 0");
-    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return set_err(FLAME_EINVAL, "n_chunks out of range: %lld", (long long)n_chunks);
+    if (int rc = check_chunks(n_chunks)) return rc;
     if (n_steps < 1 || !steps) return set_err(FLAME_EINVAL, "flame_feddyn_round: empty step program");
     if (n_steps > 0 && !step_flags) return set_err(FLAME_EINVAL, "flame_feddyn_round: step flag array is NULL");
     if (n_phase1 < 0 || n_phase1 > n_steps)
@@ -2924,26 +2917,11 @@ int flame_feddyn_round(int dtype, const flame_dyn_segment* segs, int32_t n_segs,
     auto sp = reinterpret_cast<const uint64_t*>(steps);
     // torch rounds the Python-float rates to the tensor's opmath type: fp32, fp64 for f64 tensors
     const float ra32 = static_cast<float>(rate_avg), rm32 = static_cast<float>(rate_mean);
-    switch (dtype) {
-    case FLAME_F32:
-        hipLaunchKernelGGL((feddyn_kernel<FLAME_F32, kDynUnroll>), grid, block, 0, st, segs, n_segs, sp, step_flags, n_steps,
-                           n_phase1, ra32, rm32, rate_avg, rate_mean);
-        break;
-    case FLAME_BF16:
-        hipLaunchKernelGGL((feddyn_kernel<FLAME_BF16, kDynUnroll>), grid, block, 0, st, segs, n_segs, sp, step_flags, n_steps,
-                           n_phase1, ra32, rm32, rate_avg, rate_mean);
-        break;
-    case FLAME_F16:
-        hipLaunchKernelGGL((feddyn_kernel<FLAME_F16, kDynUnroll>), grid, block, 0, st, segs, n_segs, sp, step_flags, n_steps,
-                           n_phase1, ra32, rm32, rate_avg, rate_mean);
-        break;
-    case FLAME_F64:
-        hipLaunchKernelGGL((feddyn_kernel<FLAME_F64, kDynUnroll>), grid, block, 0, st, segs, n_segs, sp, step_flags, n_steps,
-                           n_phase1, ra32, rm32, rate_avg, rate_mean);
-        break;
-    default:
-        return set_err(FLAME_ENOTSUP, "flame_feddyn_round: dtype %d not supported (f32, bf16, f16, f64)", dtype);
-    }
+    const bool known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((feddyn_kernel<decltype(dt)::value, kDynUnroll>), grid, block, 0, st, segs, n_segs, sp, step_flags,
+                           n_steps, n_phase1, ra32, rm32, rate_avg, rate_mean);
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "flame_feddyn_round: dtype %d not supported (f32, bf16, f16, f64)", dtype);
     return launched(BR_DYN + dtype, "flame_feddyn_round");
 }
 
@@ -2977,12 +2955,10 @@ int flame_synth_fill(int dtype, void* out, int64_t numel, uint64_t seed, uint64_
     int64_t blocks = (numel + kEwBlock - 1) / kEwBlock;
     if (blocks > 8192) blocks = 8192;
     const dim3 grid(static_cast<unsigned>(blocks)), block(kEwBlock);
-    switch (dtype) {
-    case FLAME_F32: hipLaunchKernelGGL(synth_kernel<FLAME_F32>, grid, block, 0, st, out, numel, ck, start, scale); break;
-    case FLAME_BF16: hipLaunchKernelGGL(synth_kernel<FLAME_BF16>, grid, block, 0, st, out, numel, ck, start, scale); break;
-    case FLAME_F16: hipLaunchKernelGGL(synth_kernel<FLAME_F16>, grid, block, 0, st, out, numel, ck, start, scale); break;
-    default: return set_err(FLAME_ENOTSUP, "flame_synth_fill: dtype %d not supported", dtype);
-    }
+    const bool known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL(synth_kernel<decltype(dt)::value>, grid, block, 0, st, out, numel, ck, start, scale);
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "flame_synth_fill: dtype %d not supported", dtype);
     return check_launch("flame_synth_fill");
 }
 

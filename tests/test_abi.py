@@ -145,6 +145,36 @@ def test_fedopt_argmeta_validates_without_gpu():
     assert L.flame_fedopt_reduce_adapt_argmeta(0, 7, 0, blk, 512, 1, 1, 2, 504, 96, *hyper, None) == _native.FLAME_ENOTSUP
 
 
+def _call_pair(L, family, dtype=0, flags=0, n_chunks=1, variant=0):
+    """One launch (one segment, one chunk, two clients; one middle) through the device-table entry
+    point and through the kernel-argument one: the two return codes."""
+    fake = ctypes.c_void_p(4096)   # never dereferenced: every caller passes one invalid argument
+    blk = (ctypes.c_uint64 * 64)()
+    hyper = [0.9, 0.1, 0.99, 0.01, 0.01, 0.001]
+    if family == "agg":
+        return (L.flame_agg_reduce(dtype, flags, fake, 1, n_chunks, fake, 2, fake, fake, None),
+                L.flame_agg_reduce_argmeta(dtype, flags, blk, 512, 1, n_chunks, 2, 80, 96, 104, None))
+    if family == "fedopt":
+        return (L.flame_fedopt_reduce_adapt(dtype, variant, flags, fake, 1, n_chunks, fake, 2, fake, *hyper, None),
+                L.flame_fedopt_reduce_adapt_argmeta(dtype, variant, flags, blk, 512, 1, n_chunks, 2, 80, 96, *hyper, None))
+    return (L.flame_hier_fedbuff(dtype, flags, fake, 1, n_chunks, 1, 2, fake, None, fake, fake, fake, fake, 0.0, None),
+            L.flame_hier_fedbuff_argmeta(dtype, flags, blk, 512, 1, n_chunks, 1, 2, 64, -1, 72, 88, 96, 104, 0.0, None))
+
+
+@pytest.mark.parametrize("family,unknown_flag", [("agg", 8), ("fedopt", 4), ("hier", 16)])
+def test_table_and_argmeta_entry_points_refuse_alike(family, unknown_flag):
+    """Both entry points of a family refuse the invalid arguments they share with the same code."""
+    from flame_amd import _native
+    L = _native.lib()
+    einval, enotsup = (_native.FLAME_EINVAL,) * 2, (_native.FLAME_ENOTSUP,) * 2
+    assert _call_pair(L, family, n_chunks=0) == einval
+    assert _call_pair(L, family, n_chunks=2 ** 31) == einval
+    assert _call_pair(L, family, flags=unknown_flag) == einval
+    if family == "fedopt":
+        assert _call_pair(L, family, variant=7) == enotsup
+    assert _call_pair(L, family, dtype=99) == enotsup
+
+
 def test_elementwise_validates_programs_without_gpu():
     """flame_elementwise checks a program on the host before any launch: registers defined
     before they are read and of the dtype the reading op says, buffers present, known ops."""
