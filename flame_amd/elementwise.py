@@ -14,7 +14,13 @@ fp16 -> fp32, a 0-dim operand's lower priority, ...) and the errors (bool subtra
 torch's own.  The kernel then computes what torch-CPU computes for that dtype: operands cast to
 the op's result dtype first, fp32 / fp64 ops rounded once, bf16 / fp16 ops in fp32 rounded once
 to the dtype (a Python scalar used in fp32 by ``*`` and rounded to the dtype before ``+``),
-integer ops wrapped to their width.
+integer ops wrapped to their width (an integer scalar too; one that the op's double or an int64
+cannot hold exactly, ``2**53 + 1``, is refused when the statement is recorded).
+
+A float -> integer cast is defined for finite values whose truncation toward zero fits the target
+type (a negative value does not fit uint8); for a NaN, an infinity or a value outside that range
+the result is unspecified, as it is in the reference (C++ undefined behaviour: torch-CPU returns
+the x86 "indefinite" value there, the kernel saturates at int64 and wraps).
 
 Reference statements (paths relative to /root/reference/lib/python/flame/):
   optimizer/fedopt.py:102-129 (+ fedadam.py:33-35, fedyogi.py:34-36, fedadagrad.py:33-35),
@@ -72,6 +78,16 @@ def _scalar(x):
     return isinstance(x, (int, float)) and not isinstance(x, bool)
 
 
+def _op_scalar(dt, s):
+    """The scalar as the op carries it (a double).  An integer dtype applies it as an int64
+    (wrapped to the dtype's width, as torch-CPU wraps it): one that a double or an int64 cannot
+    hold exactly would be silently rounded, so it is refused."""
+    if not dt.is_floating_point and not (-2 ** 63 <= s < 2 ** 63 and int(float(s)) == s):
+        raise NotImplementedError(f"flame_amd elementwise: the integer scalar {s} in {dt} is not exact in the "
+                                  "op's double / int64")
+    return s
+
+
 class Lazy:
     """One tensor-valued node of a recorded statement (a leaf tensor or an op on nodes)."""
 
@@ -101,6 +117,10 @@ class Lazy:
         return self.to(dtype)
 
     def _binary(self, other, kind, fn, rfn=None):
+        # (torch-CPU refuses every subtraction with a bool tensor; the meta replay below refuses
+        # only bool - bool)
+        if kind == "sub" and (self.dtype == torch.bool or getattr(other, "dtype", None) == torch.bool):
+            raise RuntimeError("Subtraction, the `-` operator, with a bool tensor is not supported.")
         if isinstance(other, Lazy):
             dt, shape = _replay(fn, self, other, kind=kind)
             self._same_shape(shape, kind)
@@ -112,11 +132,13 @@ class Lazy:
             return NotImplemented
         dt, shape = _replay(rfn or fn, self, other, kind=(kind, rfn is not None))
         if kind == "add":
-            return Lazy(dt, shape, "add_s", (self._cast(dt),), scalar=other)
+            return Lazy(dt, shape, "add_s", (self._cast(dt),), scalar=_op_scalar(dt, other))
         if kind == "sub":            # x - s == x + (-s) exactly (round-to-nearest is symmetric)
-            return Lazy(dt, shape, "add_s", (self._cast(dt),), scalar=-other)
+            # (a float dtype negates the scalar as a float: -0.0 - 0 is -0.0 + -0.0, not -0.0 + 0)
+            return Lazy(dt, shape, "add_s", (self._cast(dt),),
+                        scalar=-float(other) if dt.is_floating_point else _op_scalar(dt, -other))
         if kind == "mul":
-            return Lazy(dt, shape, "mul_s", (self._cast(dt),), scalar=other)
+            return Lazy(dt, shape, "mul_s", (self._cast(dt),), scalar=_op_scalar(dt, other))
         raise NotImplementedError(f"flame_amd elementwise: {kind} by a scalar")
 
     def __add__(self, o):
@@ -128,10 +150,19 @@ class Lazy:
     def __sub__(self, o):
         return self._binary(o, "sub", lambda a, b: a - b)
 
-    def __rsub__(self, o):       # s - x == (-x) + s exactly
+    def __rsub__(self, o):       # s - x == (-x) + s exactly, x negated in the RESULT's dtype
         if isinstance(o, Lazy):
             return o - self
-        return (-self)._binary(o, "add", lambda a, b: b - (-a), lambda a, b: b - (-a))
+        if isinstance(o, torch.Tensor):
+            return Lazy.of(o) - self
+        if not _scalar(o):
+            return NotImplemented
+        if self.dtype == torch.bool:
+            raise RuntimeError("Subtraction, the `-` operator, with a bool tensor is not supported.")
+        # (an int tensor under a float scalar is cast first: -x in int8 / uint8 would wrap)
+        dt, shape = _replay(lambda a, b: b - a, self, o, kind="rsub")
+        neg = Lazy(dt, shape, "mul_s", (self._cast(dt),), scalar=-1.0)
+        return Lazy(dt, shape, "add_s", (neg,), scalar=_op_scalar(dt, o))
 
     def __mul__(self, o):
         return self._binary(o, "mul", lambda a, b: a * b)
@@ -350,6 +381,8 @@ class Program:
         written)."""
         import numpy as np
         from . import engine
+        if not rows:
+            return []
         if len(rows) == 1 and into is None:
             return [self(*rows[0], device=device)]
         ins = []

@@ -373,6 +373,11 @@ int flame_feddyn_round(int dtype, const flame_dyn_segment *segs, int32_t n_segs,
  *     is used in fp32 by MUL_S and rounded to the dtype first by ADD_S (torch-CPU's behaviour);
  *   integers: two's-complement arithmetic wrapped to the dtype's width (bool: + is a logical
  *     or, * a logical and, - is refused as torch refuses it).
+ * A float -> integer FLAME_EW_CAST is defined for finite values whose truncation toward zero fits
+ * the target type (a negative value does not fit FLAME_U8); for a NaN, an infinity or a value
+ * outside that range the result is unspecified, as in the reference (C++ undefined behaviour).
+ * An integer dtype applies ADD_S / MUL_S's scalar as an int64 wrapped to the dtype's width, so
+ * the scalar must be an integer that a double and an int64 hold exactly.
  * Per element i of [0, numel): registers r[0..FLAME_EW_MAX_REGS) start undefined; ops run in
  * order.  prog (n_ops <= FLAME_EW_MAX_OPS) and bufs (n_bufs <= FLAME_EW_MAX_BUFS) are HOST
  * arrays, copied into the launch; every buffer is a contiguous DEVICE array of numel elements.

@@ -64,6 +64,22 @@ def assert_bitwise(label, got, exp):
                                  f"{ga.reshape(-1)[bad[:5]]} vs {ea.reshape(-1)[bad[:5]]}")
 
 
+def same_bits(label, got, exp):
+    """Every key of ``exp`` bitwise in ``got`` (a device or CPU dict): dtype, shape, the sign of a
+    zero; a NaN equals a NaN whatever its payload."""
+    for k in exp:
+        g, e = got[k].detach().cpu(), exp[k]
+        assert g.dtype == e.dtype and g.shape == e.shape, (label, k, g.dtype, e.dtype, g.shape, e.shape)
+        if g.dtype.is_floating_point:
+            both_nan = torch.isnan(g) & torch.isnan(e)
+            bad = ((g.view(-1) != e.view(-1)) | (torch.signbit(g.view(-1)) != torch.signbit(e.view(-1)))) & ~both_nan.view(-1)
+        else:
+            bad = g.view(-1) != e.view(-1)
+        idx = bad.nonzero().flatten()
+        assert idx.numel() == 0, (f"{label}/{k} ({g.dtype}): {idx.numel()} of {g.numel()} differ, first at "
+                                  f"{idx[:4].tolist()}: {g.view(-1)[idx[:4]].tolist()} vs {e.view(-1)[idx[:4]].tolist()}")
+
+
 def assert_close_fedopt(label, got, exp, rtol=1e-6, elementwise=True):
     """SURVEY §8(c) FedOPT contract: per round from identical state, elementwise rel err <= rtol
     where |ref| >= rtol*max|ref|, and rel-L2 <= rtol; across rounds (state already differs by

@@ -36,18 +36,7 @@ def _tensor(g, dt, shape, scale, r, i):
     return torch.randint(0, hi, shape, generator=g).to(dt) + (r * 10 + i if dt != torch.uint8 else 0)
 
 
-def _same(label, got, exp):
-    for k in exp:
-        g, e = got[k].detach().cpu(), exp[k]
-        assert g.dtype == e.dtype and g.shape == e.shape, (label, k, g.dtype, e.dtype, g.shape, e.shape)
-        if g.dtype.is_floating_point:
-            both_nan = torch.isnan(g) & torch.isnan(e)
-            bad = ((g.view(-1) != e.view(-1)) | (torch.signbit(g.view(-1)) != torch.signbit(e.view(-1)))) & ~both_nan.view(-1)
-        else:
-            bad = g.view(-1) != e.view(-1)
-        idx = bad.nonzero().flatten()
-        assert idx.numel() == 0, (f"{label}/{k} ({g.dtype}): {idx.numel()} of {g.numel()} differ, first at "
-                                  f"{idx[:4].tolist()}: {g.view(-1)[idx[:4]].tolist()} vs {e.view(-1)[idx[:4]].tolist()}")
+_same = S.same_bits
 
 
 @pytest.mark.parametrize("sort", SORTS)
