@@ -365,7 +365,9 @@ __device__ __forceinline__ h2 sign_h2(h2 x) {
 
 // ---------------------------------------------------------------- dtype traits
 // T: storage type; A: register accumulator type; EPT: elements per 16-byte lane vector.
-// tmp(v, r) = the reference's `tmp = (v * rate).to(v.dtype)`; add(a, t) = `agg += tmp`.
+// tmp(v, r) = the reference's `tmp = (v * rate).to(v.dtype)`; add(a, t) = `agg += tmp`;
+// mulr(a, r) = one more product on a value already in the dtype (the float dtypes; the scaled
+// reduction's `torch.mul(d_w, scale)` followed by the rate).
 template <int DT> struct Tr;
 
 template <> struct Tr<FLAME_F32> {
@@ -373,6 +375,7 @@ template <> struct Tr<FLAME_F32> {
     __device__ static A ld(T x) { return x; }
     __device__ static T st(A a) { return a; }
     __device__ static A tmp(T v, float r, double) { return __fmul_rn(v, r); }
+    __device__ static A mulr(A a, float r, double) { return __fmul_rn(a, r); }
     __device__ static A add(A a, A t) { return __fadd_rn(a, t); }
 };
 template <> struct Tr<FLAME_BF16> {
@@ -380,6 +383,7 @@ template <> struct Tr<FLAME_BF16> {
     __device__ static A ld(T x) { return bf16_to_f32(x); }
     __device__ static T st(A a) { return f32_to_bf16_exact(a); }
     __device__ static A tmp(T v, float r, double) { return bf16_round(__fmul_rn(bf16_to_f32(v), r)); }
+    __device__ static A mulr(A a, float r, double) { return bf16_round(__fmul_rn(a, r)); }
     __device__ static A add(A a, A t) { return bf16_round(__fadd_rn(a, t)); }
 };
 template <> struct Tr<FLAME_F16> {
@@ -387,6 +391,7 @@ template <> struct Tr<FLAME_F16> {
     __device__ static A ld(T x) { return f16_to_f32(x); }
     __device__ static T st(A a) { return f32_to_f16_bits(a); }
     __device__ static A tmp(T v, float r, double) { return f16_round(__fmul_rn(f16_to_f32(v), r)); }
+    __device__ static A mulr(A a, float r, double) { return f16_round(__fmul_rn(a, r)); }
     __device__ static A add(A a, A t) { return f16_round(__fadd_rn(a, t)); }
 };
 template <> struct Tr<FLAME_F64> {
@@ -394,6 +399,7 @@ template <> struct Tr<FLAME_F64> {
     __device__ static A ld(T x) { return x; }
     __device__ static T st(A a) { return a; }
     __device__ static A tmp(T v, float, double r) { return __dmul_rn(v, r); }
+    __device__ static A mulr(A a, float, double r) { return __dmul_rn(a, r); }
     __device__ static A add(A a, A t) { return __dadd_rn(a, t); }
 };
 // int tensors: torch promotes int * python-float to fp32, then .to(int) truncates (fedavg.py:93-102)
@@ -490,12 +496,16 @@ __device__ __forceinline__ int64_t client_offset(const SEG& sg, int64_t chunk) {
 // ---------------------------------------------------------------- reduction core
 // A lane owns VPT 16-byte vectors of the chunk, at elements e0 + v*kBlock*EPT.
 // Reduce clients [0, n) into acc for those slots.  VEC: every vector whole and
-// aligned; else element-wise with bounds (tails / unaligned views).
-template <int DT, int CU, bool VEC>
+// aligned; else element-wise with bounds (tails / unaligned views).  SCALED (flame_agg_reduce_scaled
+// only; a template parameter, so no other kernel carries the branch): client i's value is first
+// multiplied by its clip scale, tmp = round(round(v * scale_i) * rate_i).
+template <int DT, int CU, bool VEC, bool SCALED = false>
 __device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][Tr<DT>::EPT], bool init_first,
                                                const uint64_t* __restrict__ cp, int n,
                                                const float* __restrict__ r32, const double* __restrict__ r64,
-                                               int64_t e0, int64_t numel, int64_t coff) {
+                                               int64_t e0, int64_t numel, int64_t coff,
+                                               const float* __restrict__ s32 = nullptr,
+                                               const double* __restrict__ s64 = nullptr) {
     using X = Tr<DT>;
     using T = typename X::T;
     constexpr int EPT = X::EPT;
@@ -515,13 +525,24 @@ __device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][T
             }
         }
     };
-    auto combine_r = [&](const float r, const double rd, const T (&x)[kVPT][EPT]) {
+    // tmp of client c's element: the rate product, after the scale product when SCALED
+    auto tmp_of = [&](int c, const float r, const double rd, T xv) {
+        if constexpr (SCALED) {
+            if constexpr (DT == FLAME_F64) return X::mulr(X::tmp(xv, 0.f, s64[c]), r, rd);
+            else return X::mulr(X::tmp(xv, s32[c], 0.0), r, rd);
+        } else {
+            (void)c;
+            return X::tmp(xv, r, rd);
+        }
+    };
+    auto combine = [&](int c, const T (&x)[kVPT][EPT]) {
+        const float r = rate32(c);
+        const double rd = rate64(c);
 #pragma unroll
         for (int v = 0; v < kVPT; ++v)
 #pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = X::add(acc[v][j], X::tmp(x[v][j], r, rd));
+            for (int j = 0; j < EPT; ++j) acc[v][j] = X::add(acc[v][j], tmp_of(c, r, rd, x[v][j]));
     };
-    auto combine = [&](int c, const T (&x)[kVPT][EPT]) { combine_r(rate32(c), rate64(c), x); };
     if (init_first && n > 0) {
         T x[kVPT][EPT];
         load_client(0, x);
@@ -530,7 +551,7 @@ __device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][T
 #pragma unroll
         for (int v = 0; v < kVPT; ++v)
 #pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = X::tmp(x[v][j], r, rd);
+            for (int j = 0; j < EPT; ++j) acc[v][j] = tmp_of(0, r, rd, x[v][j]);
         i = 1;
     }
     for (; i + CU <= n; i += CU) {
@@ -550,12 +571,13 @@ __device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][T
 // One chunk of one segment: acc = base (or client 0), reduce every client in order.
 // Full, aligned chunks hand their output vectors back (ov / op) so the caller can
 // store them; tails and misaligned views store element-wise here.
-template <int DT, int CU>
+template <int DT, int CU, bool SCALED = false>
 __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ segs, int n_segs,
                                              const uint64_t* __restrict__ clients, int n_clients,
                                              const float* __restrict__ r32, const double* __restrict__ r64,
                                              unsigned flags, int64_t chunk, V16 (&ov)[kVPT],
-                                             typename Tr<DT>::T*& op) {
+                                             typename Tr<DT>::T*& op, const float* __restrict__ s32 = nullptr,
+                                             const double* __restrict__ s64 = nullptr) {
     using X = Tr<DT>;
     using T = typename X::T;
     using A = typename X::A;
@@ -586,7 +608,7 @@ __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ s
                 for (int j = 0; j < EPT; ++j) acc[v][j] = X::ld(b[j]);
             }
         }
-        reduce_clients<DT, CU, true>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff);
+        reduce_clients<DT, CU, true, SCALED>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff, s32, s64);
 #pragma unroll
         for (int v = 0; v < kVPT; ++v) {
             T o[EPT];
@@ -603,7 +625,7 @@ __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ s
             for (int j = 0; j < EPT; ++j)
                 acc[v][j] = X::ld((e0 + v * VS + j < sg.numel) ? ld1(bp + v * VS + j) : T(0));
     }
-    reduce_clients<DT, 1, false>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff);
+    reduce_clients<DT, 1, false, SCALED>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff, s32, s64);
 #pragma unroll
     for (int v = 0; v < kVPT; ++v)
 #pragma unroll
@@ -699,6 +721,223 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_kernel_argmeta(const ArgMet
     agg_reduce_body<DT, CU, G>(reinterpret_cast<const flame_segment*>(w), n_segs, w + off_clients, n_clients,
                             off_r32 >= 0 ? reinterpret_cast<const float*>(w + off_r32) : nullptr,
                             off_r64 >= 0 ? reinterpret_cast<const double*>(w + off_r64) : nullptr, flags, n_chunks);
+}
+
+// ---------------------------------------------------------------- scaled reduction (update guard)
+// flame_agg_reduce with a per-client clip scale in front of the rate (differential_privacy.py:79-82
+// then fedavg.py:93-104).  Its own kernel family, one chunk per workgroup at full residency: the
+// SCALED template argument keeps the extra product out of every other instantiation.
+template <int DT, int CU>
+__global__ __launch_bounds__(kBlock) void agg_reduce_scaled_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                   const uint64_t* __restrict__ clients, int n_clients,
+                                                                   const float* __restrict__ r32,
+                                                                   const double* __restrict__ r64,
+                                                                   const float* __restrict__ s32,
+                                                                   const double* __restrict__ s64, unsigned flags,
+                                                                   int64_t n_chunks) {
+    using T = typename Tr<DT>::T;
+    const int64_t slot = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (slot >= n_chunks) return;
+    V16 ov[kVPT];
+    T* op;
+    if (reduce_chunk<DT, CU, true>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op, s32, s64))
+        store_chunk(op, ov);
+}
+
+// ---------------------------------------------------------------- update statistics (update guard)
+// Per client: the sum of squares of its finite elements and the count of its non-finite ones, over
+// every segment (differential_privacy.py:68-76 is the norm this feeds).  The only kernel that
+// reduces ALONG an update.  A workgroup owns kStatR consecutive chunks; clients are the outer loop,
+// so a lane carries one fp64 accumulator per client across its kStatR x 16 bytes and the workgroup
+// reduces once per client: lane partials, a wave reduction (lanes 32, 16, .. 1 apart), the four
+// wave sums added in wave order, one partial per (client, workgroup) into the caller's scratch.
+// update_stats_finish_kernel adds a client's partials in a fixed order.  No floating-point atomic
+// anywhere, so equal launches give equal bits.  Every element is widened to fp64 before the square
+// (exact for f32 / bf16 / f16, so their square-and-add is one fma without changing a bit; fp64
+// squares round once, then add).
+#ifndef FLAME_T_STAT_R
+#define FLAME_T_STAT_R 8
+#endif
+constexpr int kStatR = FLAME_T_STAT_R;           // consecutive chunks per workgroup
+#ifndef FLAME_T_STAT_UNROLL
+#define FLAME_T_STAT_UNROLL 8
+#endif
+constexpr int kStatUnroll = FLAME_T_STAT_UNROLL; // chunk loads in flight per lane
+#ifndef FLAME_T_STAT_CB
+#define FLAME_T_STAT_CB 8
+#endif
+constexpr int kStatCB = FLAME_T_STAT_CB;         // clients a lane accumulates side by side (their loads issued together)
+constexpr int kStatBatch = 64;                   // clients whose wave sums share the LDS block
+static_assert(kStatCB >= 1 && kStatBatch % kStatCB == 0, "the LDS block holds whole client groups");
+constexpr int kWaves = kBlock / 64;
+constexpr int64_t kChunkBytes = 4096;            // one chunk of every dtype (= FLAME_TILE_BYTES)
+static_assert(kWaves == 4, "the statistics kernels add four wave sums");
+
+template <int DT>
+__device__ __forceinline__ void stat_elem(typename Tr<DT>::T x, double& acc, unsigned& bad) {
+    if constexpr (DT == FLAME_F64) {
+        const bool nf = !__builtin_isfinite(x);
+        acc = __dadd_rn(acc, nf ? 0.0 : __dmul_rn(x, x));
+        bad += nf;
+    } else {
+        const float f = Tr<DT>::ld(x);
+        const bool nf = !__builtin_isfinite(f);
+        const double d = static_cast<double>(nf ? 0.0f : f);
+        acc = __builtin_fma(d, d, acc);      // d * d is exact in fp64: the same bits as multiply, then add
+        bad += nf;
+    }
+}
+template <int DT>
+__device__ __forceinline__ void stat_vec(const V16& v, double& acc, unsigned& bad) {
+    using T = typename Tr<DT>::T;
+    T x[Tr<DT>::EPT];
+    unpack<T, Tr<DT>::EPT>(v, x);
+#pragma unroll
+    for (int j = 0; j < Tr<DT>::EPT; ++j) stat_elem<DT>(x[j], acc, bad);
+}
+// lane 0 receives the wave's sum, always added in the same order
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x = __dadd_rn(x, __shfl_down(x, d, 64));
+    return x;
+}
+
+// One pass of a workgroup over its chunks [c0, c1) for NC clients (cfirst ..): per chunk the NC
+// clients' vectors are loaded together (on a tiled slab they are one contiguous NC x 4 KiB run),
+// CU chunks per step.  All bounds are workgroup-uniform.
+template <int DT, int NC, int CU>
+__device__ __forceinline__ void stat_pass(const flame_segment* __restrict__ segs, int n_segs, int s0, int64_t c0,
+                                          int64_t c1, const uint64_t* __restrict__ clients, int n_clients, int cfirst,
+                                          double (&acc)[NC], unsigned (&bad)[NC]) {
+    using T = typename Tr<DT>::T;
+    constexpr int EPT = Tr<DT>::EPT;
+    constexpr int64_t CE = chunk_elems<DT>();
+    static_assert(CE * sizeof(T) == kChunkBytes, "a chunk is 4 KiB of every dtype");
+    const int64_t lane_elem = static_cast<int64_t>(threadIdx.x) * EPT;
+    int64_t chunk = c0;
+    // the segments that meet [c0, c1), in order
+#pragma unroll 1
+    for (int s = s0; s < n_segs && chunk < c1; ++s) {
+        const int64_t numel = segs[s].numel, begin = segs[s].chunk_begin;
+        if (numel <= 0) continue;
+        int64_t end = begin + (numel + CE - 1) / CE;
+        if (end > c1) end = c1;
+        if (chunk < begin) chunk = begin;
+        if (chunk >= end) continue;
+        const int64_t tstride = segs[s].client_tile_stride;
+        const int64_t step = tstride ? tstride : kChunkBytes;
+        int64_t cl = chunk - begin;
+        const int64_t cle = end - begin;
+        // whole, aligned chunks take the vector path; the tail chunk and misaligned views go
+        // element by element with bounds
+        int64_t clf = (segs[s].flags & FLAME_SEG_UNALIGNED) ? cl : numel / CE;
+        if (clf > cle) clf = cle;
+        const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients + cfirst;
+        const int64_t loff = lane_elem * static_cast<int64_t>(sizeof(T));
+        const char* q[NC];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) q[k] = reinterpret_cast<const char*>(cp[k]) + cl * step + loff;
+        int64_t off = 0;
+        for (; cl + CU <= clf; cl += CU, off += CU * step) {
+            V16 x[CU][NC];
+#pragma unroll
+            for (int u = 0; u < CU; ++u)
+#pragma unroll
+                for (int k = 0; k < NC; ++k) x[u][k] = ld_nt(q[k] + off + u * step);
+#pragma unroll
+            for (int u = 0; u < CU; ++u)
+#pragma unroll
+                for (int k = 0; k < NC; ++k) stat_vec<DT>(x[u][k], acc[k], bad[k]);
+        }
+        for (; cl < clf; ++cl, off += step) {
+            V16 x[NC];
+#pragma unroll
+            for (int k = 0; k < NC; ++k) x[k] = ld_nt(q[k] + off);
+#pragma unroll
+            for (int k = 0; k < NC; ++k) stat_vec<DT>(x[k], acc[k], bad[k]);
+        }
+        for (; cl < cle; ++cl, off += step) {
+            const int64_t e = cl * CE + lane_elem;
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+#pragma unroll
+                for (int j = 0; j < EPT; ++j)
+                    if (e + j < numel) stat_elem<DT>(ld1(reinterpret_cast<const T*>(q[k] + off) + j), acc[k], bad[k]);
+        }
+        chunk = end;
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kBlock) void update_stats_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                              const uint64_t* __restrict__ clients, int n_clients,
+                                                              int64_t n_chunks, int64_t n_wg,
+                                                              double* __restrict__ scratch,
+                                                              unsigned long long* __restrict__ nonfinite) {
+    __shared__ double wsum[kWaves][kStatBatch];
+    const int64_t c0 = static_cast<int64_t>(blockIdx.x) * kStatR;
+    const int64_t c1 = c0 + kStatR < n_chunks ? c0 + kStatR : n_chunks;
+    const int s0 = find_segment(segs, n_segs, c0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // one client's lane partials -> its wave sums in LDS, its non-finite count added to the output
+    auto commit = [&](int ci, int c, double acc, unsigned bad) {
+        acc = wave_sum(acc);
+        if (lane == 0) wsum[wave][ci] = acc;
+        if (__any(bad != 0)) {          // rare: integer counts may use an atomic
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) bad += __shfl_down(bad, d, 64);
+            if (lane == 0) atomicAdd(nonfinite + c, static_cast<unsigned long long>(bad));
+        }
+    };
+#pragma unroll 1
+    for (int cb = 0; cb < n_clients; cb += kStatBatch) {
+        const int nb = n_clients - cb < kStatBatch ? n_clients - cb : kStatBatch;
+        int ci = 0;
+        if constexpr (kStatCB > 1) {
+#pragma unroll 1
+            for (; ci + kStatCB <= nb; ci += kStatCB) {
+                double acc[kStatCB];
+                unsigned bad[kStatCB];
+#pragma unroll
+                for (int k = 0; k < kStatCB; ++k) acc[k] = 0.0, bad[k] = 0;
+                stat_pass<DT, kStatCB, (kStatUnroll / kStatCB > 1 ? kStatUnroll / kStatCB : 1)>(
+                    segs, n_segs, s0, c0, c1, clients, n_clients, cb + ci, acc, bad);
+#pragma unroll
+                for (int k = 0; k < kStatCB; ++k) commit(ci + k, cb + ci + k, acc[k], bad[k]);
+            }
+        }
+#pragma unroll 1
+        for (; ci < nb; ++ci) {         // the clients left over, one at a time
+            double acc[1] = {0.0};
+            unsigned bad[1] = {0};
+            stat_pass<DT, 1, kStatUnroll>(segs, n_segs, s0, c0, c1, clients, n_clients, cb + ci, acc, bad);
+            commit(ci, cb + ci, acc[0], bad[0]);
+        }
+        __syncthreads();
+        if (static_cast<int>(threadIdx.x) < nb) {
+            const int t_ci = threadIdx.x;
+            const double t = __dadd_rn(__dadd_rn(__dadd_rn(wsum[0][t_ci], wsum[1][t_ci]), wsum[2][t_ci]), wsum[3][t_ci]);
+            st1(scratch + static_cast<int64_t>(cb + t_ci) * n_wg + blockIdx.x, t);
+        }
+        __syncthreads();
+    }
+}
+
+// sumsq[c] += the n_wg partials of client c: lane t adds partials t, t + 256, .. in index order,
+// then the same wave and workgroup order as above
+__global__ __launch_bounds__(kBlock) void update_stats_finish_kernel(const double* __restrict__ scratch, int64_t n_wg,
+                                                                     double* __restrict__ sumsq) {
+    __shared__ double wsum[kWaves];
+    const double* row = scratch + static_cast<int64_t>(blockIdx.x) * n_wg;
+    double acc = 0.0;
+    for (int64_t w = threadIdx.x; w < n_wg; w += kBlock) acc = __dadd_rn(acc, ld1(row + w));
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double t = __dadd_rn(__dadd_rn(__dadd_rn(wsum[0], wsum[1]), wsum[2]), wsum[3]);
+        st1(sumsq + blockIdx.x, __dadd_rn(ld1(sumsq + blockIdx.x), t));
+    }
 }
 
 // ---------------------------------------------------------------- fused FedOPT (fp32)
@@ -2730,6 +2969,66 @@ int flame_agg_reduce_argmeta(int dtype, unsigned flags, const void* host_meta, i
 }
 
 int64_t flame_agg_argmeta_max_bytes(void) { return static_cast<int64_t>(sizeof(ArgMeta)); }
+
+// The update guard's two entry points stand outside the launch-branch table, as flame_slab_write
+// and flame_synth_fill do: one instantiation per dtype, nothing to pick.
+int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                            const void* const* clients, int32_t n_clients, const float* rates32,
+                            const double* rates64, const float* scales32, const double* scales64, void* stream) {
+    const char* const who = "flame_agg_reduce_scaled";
+    if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
+    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = check_agg_flags(who, flags, n_clients)) return rc;
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    const bool f64 = dtype == FLAME_F64;
+    if (n_clients > 0 && !(f64 ? rates64 : static_cast<const void*>(rates32))) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if (n_clients > 0 && !(f64 ? scales64 : static_cast<const void*>(scales32))) return set_err(FLAME_EINVAL, "%s: scale array is NULL", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool known = dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        constexpr int CU = is16(DT) ? kClientUnroll16 : kClientUnroll;
+        hipLaunchKernelGGL((agg_reduce_scaled_kernel<DT, CU>), dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0, st, segs,
+                           n_segs, reinterpret_cast<const uint64_t*>(clients), n_clients, rates32, rates64, scales32,
+                           scales64, flags, n_chunks);
+    });
+    if (!known) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    return check_launch(who);
+}
+
+int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
+    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll || n_clients <= 0) return 0;
+    return (n_chunks + kStatR - 1) / kStatR * static_cast<int64_t>(n_clients) * static_cast<int64_t>(sizeof(double));
+}
+
+int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                       const void* const* clients, int32_t n_clients, double* sumsq, int64_t* nonfinite,
+                       void* scratch, int64_t scratch_bytes, void* stream) {
+    const char* const who = "flame_update_stats";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (n_clients <= 0) return set_err(FLAME_EINVAL, "%s: n_clients <= 0", who);
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (!sumsq || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
+    const int64_t need = flame_update_stats_scratch_bytes(n_chunks, n_clients);
+    if (!scratch || scratch_bytes < need)
+        return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
+                       static_cast<long long>(scratch_bytes), static_cast<long long>(need));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t n_wg = (n_chunks + kStatR - 1) / kStatR;
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((update_stats_kernel<decltype(dt)::value>), dim3(static_cast<unsigned>(n_wg)), dim3(kBlock), 0, st,
+                           segs, n_segs, reinterpret_cast<const uint64_t*>(clients), n_clients, n_chunks, n_wg,
+                           static_cast<double*>(scratch), reinterpret_cast<unsigned long long*>(nonfinite));
+    });
+    if (int rc = check_launch(who)) return rc;
+    hipLaunchKernelGGL(update_stats_finish_kernel, dim3(static_cast<unsigned>(n_clients)), dim3(kBlock), 0, st,
+                       static_cast<const double*>(scratch), n_wg, sumsq);
+    return check_launch(who);
+}
 
 int flame_fedopt_reduce_adapt(int dtype, int variant, unsigned flags, const flame_segment* segs, int32_t n_segs,
                               int64_t n_chunks, const void* const* clients, int32_t n_clients,

@@ -95,15 +95,19 @@ class Plan:
     off_clients: int      # byte offsets into the device copy of ``meta``
     off_r32: int
     off_r64: int
+    off_s32: int = -1     # the per-client clip scales (flame_agg_reduce_scaled), -1 without them
+    off_s64: int = -1
 
 
 def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] = None,
-         seg_rates: bool = False, compact: bool = False) -> Plan:
+         seg_rates: bool = False, compact: bool = False, scales: Optional[Sequence] = None) -> Plan:
     """Build the device metadata block for one launch (no GPU needed).
 
     ``rates`` holds one rate per client, or with ``seg_rates`` one row of rates per
     segment (FLAME_AGG_SEG_RATES).  ``compact`` keeps only the rate array the dtype
-    reads (its other offset is -1) -- the kernel-argument launch path."""
+    reads (its other offset is -1) -- the kernel-argument launch path.  ``scales`` (one
+    per client, flame_agg_reduce_scaled) ride behind the rates, rounded as the rates are:
+    fp32 RNE for f32 / bf16 / f16, the doubles themselves for f64."""
     n_segs = len(segs)
     if n_segs == 0:
         raise ValueError("empty segment list")
@@ -146,7 +150,18 @@ def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] =
     else:
         off_r64 = off_r32 + r32.size * 4
         parts += [r32.view(np.int64), r64.view(np.int64)]
-    return Plan(code, np.concatenate(parts), n_segs, begin, n, off_clients, off_r32, off_r64)
+    off_s32 = off_s64 = -1
+    if scales is not None:
+        if seg_rates or compact or len(scales) != n:
+            raise ValueError("scales: one per client, device-table plans with one rate per client only")
+        s64 = np.asarray(scales, dtype=np.float64).reshape(-1)
+        s32 = s64.astype(np.float32)
+        if s32.size % 2:
+            s32 = np.concatenate([s32, np.zeros(1, np.float32)])
+        off_s32 = sum(x.size for x in parts) * 8
+        off_s64 = off_s32 + s32.size * 4
+        parts += [s32.view(np.int64), s64.view(np.int64)]
+    return Plan(code, np.concatenate(parts), n_segs, begin, n, off_clients, off_r32, off_r64, off_s32, off_s64)
 
 
 # ------------------------------------------------------------------ device staging
@@ -367,13 +382,17 @@ def host_device_pointer(host_ptr: int) -> int:
 
 def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients: List[List[torch.Tensor]],
             rates: Optional[Sequence[float]], *, init_first: bool = False,
-            seg_rates: Optional[Sequence[Sequence[float]]] = None) -> None:
+            seg_rates: Optional[Sequence[Sequence[float]]] = None,
+            scales: Optional[Sequence[float]] = None) -> None:
     """outs[s] = ins[s] (+)= Σ_i round(clients[s][i] * rates[i]) in order (kernel: flame_agg_reduce).
 
     ``outs`` are written in place (they must be contiguous device tensors);
     ``ins`` may be the same tensors (FedAvg mutates base_weights in place).
     ``seg_rates`` (instead of ``rates``) gives every segment its own rate row:
     independent reductions with equal client counts share one launch.
+    ``scales`` (one per client; float dtypes, not with ``seg_rates``): each client's value is
+    first multiplied by its clip scale, ``round(round(v * scale) * rate)`` (kernel:
+    flame_agg_reduce_scaled).
     """
     if not outs:
         return
@@ -397,18 +416,33 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
                 inp = i_t.data_ptr()
             segs.append(Seg(o.numel(), out=o.data_ptr(), inp=inp, clients=row, tile_stride=tstride))
         _launch_reduce(code, segs, rates if seg_rates is None else [seg_rates[s] for s in idx], device, keep,
-                       init_first=init_first, seg_rates=seg_rates is not None)
+                       init_first=init_first, seg_rates=seg_rates is not None, scales=scales)
     _keepalive(keep, device)
 
 
-def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rates=False) -> None:
-    """One flame_agg_reduce launch over prepared segments (``keep`` holds what must outlive it)."""
+def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rates=False, scales=None) -> None:
+    """One flame_agg_reduce launch over prepared segments (``keep`` holds what must outlive it);
+    with ``scales`` one flame_agg_reduce_scaled launch (device tables only)."""
     L = N.lib()
     flags = N.FLAME_AGG_INIT_FIRST if init_first else 0
     if seg_rates:
         flags |= N.FLAME_AGG_SEG_RATES
     n_cl = _n_clients(rates, seg_rates)
     nbytes = sum(s.numel for s in segs) * ITEMSIZE[code] * (n_cl + (1 if init_first else 2))
+    if scales is not None:
+        if seg_rates or code not in FLOAT_CODES:
+            raise NotImplementedError("flame_amd: a scaled reduction takes float tensors and one rate per client")
+        p = plan(code, segs, rates, scales=scales)
+        if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs):
+            flags |= N.FLAME_AGG_XCD_MAP
+        dm = _staging.upload(p.meta, device)
+        segp, clp, r32p, r64p = _device_ptrs(dm, p)
+        with _timed("flame_agg_reduce_scaled", device, nbytes):
+            N.check(L.flame_agg_reduce_scaled(code, flags, segp, p.n_segs, p.n_chunks, clp, p.n_clients, r32p, r64p,
+                                              dm.data_ptr() + p.off_s32, dm.data_ptr() + p.off_s64,
+                                              _stream_ptr(device)))
+        keep.append(dm)
+        return
     est = compact_meta_bytes(code, len(segs), n_cl, seg_rates)
     if ARGMETA and est <= argmeta_max_bytes():
         # small launch: the metadata block goes with the dispatch as a kernel argument (no H2D blit)
@@ -946,8 +980,14 @@ class _Target:
             self.orig.copy_(self.dev)
 
 
-def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=None) -> None:
+def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=None, scales=None) -> None:
     """agg[k] += round(v_i[k] * rate_i) for entries (weights, rate) in order, in place.
+
+    ``scales`` (one per entry, the update guard's clip scales): every FLOAT update tensor is
+    first multiplied by its entry's scale, ``round(v * scale)`` in v's dtype
+    (differential_privacy.py:79-82) -- same-dtype float keys inside the reduction
+    (flame_agg_reduce_scaled), float tensors on the mixed / promoted path pre-scaled per entry
+    with :func:`tmp_of`; integer and bool tensors are never scaled.
 
     Restates the per-client / per-key loop of fedavg.py:79-104 and fedbuff.py:89-97,
     136-157 (agg not None) as one launch per dtype over all keys and clients.
@@ -962,7 +1002,9 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     if device is None:   # the aggregate's own device first (no per-entry list for the common case)
         device = next((t.device for t in agg.values() if isinstance(t, torch.Tensor) and t.is_cuda), None) \
             or pick_device(*[w for w, _ in entries])
-    if _accumulate_slab(agg, entries, device, key_groups, after_group):
+    if scales is not None and len(scales) != len(entries):
+        raise ValueError("accumulate: one scale per entry")
+    if _accumulate_slab(agg, entries, device, key_groups, after_group, scales):
         return
     if key_groups is not None:
         for w, _ in entries:
@@ -971,7 +1013,7 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
                     raise KeyError(k)
         for gi, g in enumerate(key_groups):
             accumulate({k: agg[k] for k in g}, [({k: w[k] for k in g if k in w}, r) for w, r in entries],
-                       device=device)
+                       device=device, scales=scales)
             if after_group is not None:
                 after_group(gi)
         return
@@ -991,14 +1033,141 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         same = [k for k in ks if agg[k].dtype in DTYPE_CODE
                 and all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)]
         mixed = [k for k in ks if k not in same]
-        if same:
-            targets = [_Target(agg[k], device) for k in same]
+        # with clip scales the float keys take the scaled kernel; integer keys are never scaled
+        parts = [(same, None)] if scales is None else [
+            ([k for k in same if agg[k].is_floating_point()], [scales[ci] for ci in cis]),
+            ([k for k in same if not agg[k].is_floating_point()], None)]
+        for part, sc in parts:
+            if not part:
+                continue
+            targets = [_Target(agg[k], device) for k in part]
             outs = [t.dev for t in targets]
-            clients = [[entries[ci][0][k] for ci in cis] for k in same]
-            reduce_(outs, outs, clients, [entries[ci][1] for ci in cis])
+            clients = [[entries[ci][0][k] for ci in cis] for k in part]
+            reduce_(outs, outs, clients, [entries[ci][1] for ci in cis], scales=sc)
             for t in targets:
                 t.writeback()
-        _accumulate_mixed(agg, mixed, [entries[ci] for ci in cis], device)
+        sub = [entries[ci] for ci in cis]
+        if scales is not None and mixed:
+            sub = _prescaled(sub, [scales[ci] for ci in cis], mixed, device)
+        _accumulate_mixed(agg, mixed, sub, device)
+
+
+def _prescaled(entries, scales, keys, device):
+    """``entries`` restricted to ``keys`` with every float tensor replaced by
+    ``round(v * scale)`` in its own dtype (:func:`tmp_of`, the same statement the scaled
+    kernel fuses); integer and bool tensors pass through."""
+    out = []
+    for (w, r), sc in zip(entries, scales):
+        d = {}
+        for k in keys:
+            if k not in w:
+                continue
+            v = w[k]
+            d[k] = tmp_of(v, sc, device, logical_shape(w, k)) if v.is_floating_point() else v
+        out.append((d, r))
+    return out
+
+
+class _KeyLike:
+    """What :func:`_client_row` reads of an aggregate tensor, for a key that has none here."""
+
+    def __init__(self, numel, dtype):
+        self._numel, self.dtype = numel, dtype
+
+    def numel(self):
+        return self._numel
+
+    def element_size(self):
+        return torch.empty((), dtype=self.dtype).element_size()
+
+
+def _numel_of(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def update_stats(weights_list, device=None):
+    """Per update: the sum of squares of its finite float elements and the count of its
+    non-finite ones (kernel: flame_update_stats; differential_privacy.py:68-76 takes the square
+    root of the former).  Returns ``(sumsq: np.float64[n], nonfinite: np.int64[n])`` in the
+    order of ``weights_list``.
+
+    Each update's FLOAT tensors (f32 / bf16 / f16 / f64) are grouped by their own dtype -- slots
+    of one UpdateSlab through :func:`slab_rows`, without touching a view -- and every dtype is one
+    launch into the shared outputs.  Integer and bool tensors take no part (BatchNorm's
+    ``num_batches_tracked`` is not part of the norm).  The call ends with one device-to-host copy
+    of 16 bytes per update, which waits for the stream: this is a synchronisation point."""
+    ws = list(weights_list)
+    n = len(ws)
+    if n == 0:
+        return np.zeros(0, np.float64), np.zeros(0, np.int64)
+    device = torch.device(device) if device is not None else pick_device(*ws)
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.update_stats: needs a HIP device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    keep = []
+    groups = collections.OrderedDict()          # (dtype code, client indices) -> [Seg]
+    all_cis = tuple(range(n))
+    w0 = ws[0]
+    rows = None
+    if getattr(w0, "slab", None) is not None:
+        fkeys = [k for k in w0.keys() if weight_dtype(w0, k).is_floating_point and weight_dtype(w0, k) in DTYPE_CODE]
+        numels = {k: _numel_of(logical_shape(w0, k)) for k in fkeys}
+        dts = {k: weight_dtype(w0, k) for k in fkeys}
+        rows = slab_rows(ws, fkeys, numels, dts, device) if fkeys else None
+        if rows is not None:
+            for k in fkeys:
+                ptrs, tile_bytes = rows[k]
+                groups.setdefault((dtype_code(dts[k]), all_cis), []).append(
+                    Seg(numels[k], clients=ptrs, tile_stride=tile_bytes))
+    if rows is None:
+        per = collections.OrderedDict()         # (key, dtype) -> client indices, in first-seen order
+        for ci, w in enumerate(ws):
+            for k in w.keys():
+                dt = weight_dtype(w, k)
+                if dt.is_floating_point:
+                    dtype_code(dt)              # an unsupported float dtype raises
+                    per.setdefault((k, dt), []).append(ci)
+        for (k, dt), cis in per.items():
+            numel = _numel_of(logical_shape(ws[cis[0]], k))
+            row, tstride = _client_row([ws[ci][k] for ci in cis], _KeyLike(numel, dt), device, keep)
+            groups.setdefault((dtype_code(dt), tuple(cis)), []).append(Seg(numel, clients=row, tile_stride=tstride))
+    # one output block per distinct client set (normally one: every update has every key)
+    slots, total = collections.OrderedDict(), 0
+    for (_, cis) in groups:
+        if cis not in slots:
+            slots[cis] = total
+            total += len(cis)
+    if total == 0:
+        return np.zeros(n, np.float64), np.zeros(n, np.int64)
+    out = torch.zeros(2 * total, dtype=torch.int64, device=device)      # [sumsq as doubles | counts]
+    L = N.lib()
+    plans = [(code, cis, plan(code, segs, [0.0] * len(cis)), sum(s.numel for s in segs))
+             for (code, cis), segs in groups.items()]
+    sbytes = max(int(L.flame_update_stats_scratch_bytes(p.n_chunks, p.n_clients)) for _, _, p, _ in plans)
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
+    for code, cis, p, elems in plans:
+        dm = _staging.upload(p.meta, device)
+        segp, clp, _, _ = _device_ptrs(dm, p)
+        nbytes = elems * ITEMSIZE[code] * len(cis)
+        with _timed("flame_update_stats", device, nbytes):
+            N.check(L.flame_update_stats(code, segp, p.n_segs, p.n_chunks, clp, p.n_clients,
+                                         out.data_ptr() + 8 * slots[cis], out.data_ptr() + 8 * (total + slots[cis]),
+                                         scratch.data_ptr(), sbytes, _stream_ptr(device)))
+        keep.append(dm)
+    keep.append(scratch)
+    _keepalive(keep, device)
+    host = out.cpu().numpy()                    # the one D2H; waits for the launches above
+    sq, nf = host[:total].view(np.float64), host[total:]
+    sumsq, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int64)
+    for cis, o in slots.items():
+        idx = np.asarray(cis, dtype=np.int64)
+        sumsq[idx] += sq[o:o + len(cis)]
+        nonfinite[idx] += nf[o:o + len(cis)]
+    return sumsq, nonfinite
 
 
 def weight_dtype(weights, k) -> torch.dtype:
@@ -1073,7 +1242,7 @@ def slot_rows(slab, ranges, slots, keys, numels, dtypes, device):
     return rows
 
 
-def _accumulate_slab(agg: dict, entries, device, key_groups=None, after_group=None) -> bool:
+def _accumulate_slab(agg: dict, entries, device, key_groups=None, after_group=None, scales=None) -> bool:
     """Fast path: every entry lives in ONE UpdateSlab (whole slots, or :class:`SlabRef`
     ranges sharing one table) and carries exactly agg's keys in agg's dtypes.  Pointer rows
     are computed from slot numbers (numpy), without touching the per-client views; returns
@@ -1098,7 +1267,7 @@ def _accumulate_slab(agg: dict, entries, device, key_groups=None, after_group=No
                 ptrs, tile_bytes = rows[k]
                 o = targets[k].dev
                 segs.append(Seg(o.numel(), out=o.data_ptr(), inp=o.data_ptr(), clients=ptrs, tile_stride=tile_bytes))
-            _launch_reduce(code, segs, rates, device, keep)
+            _launch_reduce(code, segs, rates, device, keep, scales=scales if code in FLOAT_CODES else None)
         if after_group is not None:
             after_group(gi)
     _keepalive(keep, device)

@@ -23,6 +23,13 @@ anything reads the result (``w[k]``, ``items()``, ``load_state_dict``, ``deepcop
 ``do()`` arrives with another base dict, an empty ``do()`` returns ``None``, or
 ``max_pending`` arrivals / ``max_pending_bytes`` are queued.  ``base_weights`` itself
 (a plain dict) lags until then: read the returned object, as flame's roles do.
+
+Server-side update guard (opt-in, ``FedAvg(clip_threshold=C, nonfinite="skip")``, see
+``flame_amd/optimizer/guard.py``): ``do()`` measures every popped update once
+(``engine.update_stats``: its norm over the float tensors and its non-finite count), applies
+the ``nonfinite`` policy, forms the rates from the remaining ``total`` and reduces with the
+clip scales (``flame_agg_reduce_scaled``).  ``update_stats`` holds the round's records.
+With both kwargs at their defaults none of this runs.
 """
 import collections
 import collections.abc
@@ -33,6 +40,7 @@ import weakref
 import torch
 
 from .. import engine, metrics
+from . import guard
 from .abstract import AbstractOptimizer
 from .fedbuff import _own_shm_views
 from .regularizer import Regularizer
@@ -117,22 +125,60 @@ class DeferredWeights(collections.abc.Mapping):
 class FedAvg(AbstractOptimizer):
     """FedAvg class."""
 
-    def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30):
+    def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
+                 clip_threshold=None, nonfinite: str = "keep"):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
         self.max_pending = max_pending
         self.max_pending_bytes = max_pending_bytes
         self._deferred = None      # the DeferredWeights the last deferred do() returned
+        self._init_guard(clip_threshold, nonfinite, defer)
+
+    def _init_guard(self, clip_threshold, nonfinite, defer):
+        self.clip_threshold, self.nonfinite = guard.check_kwargs(clip_threshold, nonfinite)
+        self.update_stats = []     # the last do()'s UpdateRecords, in cache order (empty: nothing measured)
+        if defer or getattr(self, "chain_defer", False):     # FedAvg's queue or FedOPT's chain
+            guard.refuse(f"{type(self).__name__}(defer=True)", self.clip_threshold, self.nonfinite,
+                         "a deferred queue fixes each arrival's rate when it arrives, before the guard "
+                         "could measure it; use defer=False")
+
+    @property
+    def guarded(self) -> bool:
+        return guard.is_set(self.clip_threshold, self.nonfinite)
 
     def _pop_entries(self, cache, total):
         # after popping, the item is removed from the cache (fedavg.py:80-82); rate = count / total
         return [(tres.weights, tres.count / total) for tres in map(cache.pop, list(cache.iterkeys()))]
 
+    def _pop_guarded(self, cache, total):
+        """_pop_entries under the update guard: pop, measure every update once, apply the
+        ``nonfinite`` policy, and only then form the rates from what is left of ``total``.
+        Returns ``(entries, scales)``; ``entries`` is empty when every update was skipped,
+        ``scales`` None when no update is clipped (the plain reduction then runs)."""
+        ends = list(cache.iterkeys())
+        popped = [cache.pop(e) for e in ends]
+        sumsq, nonfinite = engine.update_stats([t.weights for t in popped])
+        try:
+            records, kept, total = guard.apply_policy(ends, [t.count for t in popped], sumsq, nonfinite, total,
+                                                      self.clip_threshold, self.nonfinite)
+        except guard.NonFiniteUpdate as e:      # "raise": the records still say which ends were bad
+            self.update_stats = e.records
+            guard.save_metrics(self, e.records)
+            raise
+        self.update_stats = records
+        guard.save_metrics(self, records)
+        if not kept or total == 0:
+            return [], None
+        entries = [(popped[i].weights, popped[i].count / total) for i in kept]
+        scales = [records[i].scale for i in kept]
+        return entries, (scales if any(s != 1.0 for s in scales) else None)
+
     def do(self, base_weights, cache, *, total: int = 0, version: int = 0, **kwargs):
         """Aggregate the cached trainer updates into ``base_weights`` (in place)."""
         logger.debug("calling fedavg (flame_amd)")
         assert base_weights is not None
+        self.update_stats = []     # this call's records only (an empty round measures nothing)
         if isinstance(base_weights, DeferredWeights):
             base_weights = base_weights.materialize()
         pend = self._deferred
@@ -145,7 +191,13 @@ class FedAvg(AbstractOptimizer):
         self.agg_weights = base_weights
         if len(cache) == 0 or total == 0:
             return None
-        entries = self._pop_entries(cache, total)
+        scales = None
+        if self.guarded:
+            entries, scales = self._pop_guarded(cache, total)
+            if not entries:            # every update skipped: as for an empty cache
+                return None
+        else:
+            entries = self._pop_entries(cache, total)
         if self.defer and "flame_amd_key_groups" not in kwargs:
             if pend is None:
                 self._deferred = pend = DeferredWeights(base_weights, self.max_pending, self.max_pending_bytes,
@@ -154,6 +206,7 @@ class FedAvg(AbstractOptimizer):
             return pend
         # flame_amd.shard passes its plan's waves: one launch per wave, its all-gather started
         # right behind it (callers from flame pass no such kwargs)
+        extra = {} if scales is None else {"scales": scales}     # only a clipped round names them
         engine.accumulate(self.agg_weights, entries, key_groups=kwargs.get("flame_amd_key_groups"),
-                          after_group=kwargs.get("flame_amd_after_group"))
+                          after_group=kwargs.get("flame_amd_after_group"), **extra)
         return self.agg_weights

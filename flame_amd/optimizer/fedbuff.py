@@ -183,7 +183,11 @@ class FedBuff(AbstractOptimizer):
     """FedBuff class."""
 
     def __init__(self, defer: bool = True, max_pending: int = 256, fuse_scale_add: bool = True,
-                 max_pending_bytes: int = 16 << 30):
+                 max_pending_bytes: int = 16 << 30, *, clip_threshold=None, nonfinite: str = "keep"):
+        from . import guard
+        guard.refuse("FedBuff", *guard.check_kwargs(clip_threshold, nonfinite),
+                     "its arrivals are weighted by staleness, not by count / total, and its aggregate is "
+                     "queued; a follow-up")
         self.agg_goal_weights = None
         self.is_agg_weights_none = True
         self.regularizer = Regularizer()

@@ -163,7 +163,10 @@ class _StoredHistory(collections.abc.MutableMapping):
 class FedDyn(FedAvg):
     """FedDyn class."""
 
-    def __init__(self, alpha, history: str = "rows"):
+    def __init__(self, alpha, history: str = "rows", *, clip_threshold=None, nonfinite: str = "keep"):
+        from . import guard
+        guard.refuse("FedDyn", *guard.check_kwargs(clip_threshold, nonfinite),
+                     "its histories add every arrival unscaled (feddyn.py:125-139); a follow-up")
         super().__init__()
         if history not in ("rows", "pingpong", "pingpong_rows"):
             raise ValueError("history must be 'rows', 'pingpong' or 'pingpong_rows'")

@@ -79,15 +79,16 @@ class FedOPT(FedAvg):
     max_chain_entries = 256
     max_chain_bytes = 16 << 30
 
-    def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False):
+    def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
+                 nonfinite: str = "keep"):
         self._poisoned = None
         self._chain = None
         self._current = None
         self._m = None
         self._v = None
         self._agg = None
-        super().__init__()
-        self.chain_defer = defer
+        self.chain_defer = defer        # before FedAvg's constructor: the guard refuses either defer
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite)
         self.current_weights = None
         self._d_t = None
         self._prev_current = None
@@ -153,6 +154,7 @@ class FedOPT(FedAvg):
     def do(self, base_weights, cache, *, total: int = 0, version: int = 0, **kwargs):
         logger.debug("calling fedopt (flame_amd)")
         self._check_poisoned()
+        self.update_stats = []
         if self.chain_defer and not kwargs.keys() & _SHARD_KWARGS:
             ch = self._chain
             if ch is not None and ch.base is base_weights and (len(cache) == 0 or total == 0):
@@ -186,7 +188,14 @@ class FedOPT(FedAvg):
     # ------------------------------------------------------------------ fused round
     def _do_fused(self, base_weights, cache, total, key_groups=None, after_group=None, alloc=None):
         self.agg_weights = base_weights
-        entries = self._pop_entries(cache, total)
+        scales = None
+        if self.guarded:
+            entries, scales = self._pop_guarded(cache, total)
+            if not entries:     # every update skipped: FedAvg.do returns None (fedopt.py:80-85)
+                self.agg_weights = None
+                return self.current_weights
+        else:
+            entries = self._pop_entries(cache, total)
         current = self.current_weights
         device = engine.pick_device(base_weights, current, *[w for w, _ in entries])
         keys = list(base_weights.keys())
@@ -218,7 +227,8 @@ class FedOPT(FedAvg):
         new_cur = {}
         if generic:       # first, so every key of a group is final when its group is handed on
             sub = {k: base_weights[k] for k in generic}
-            engine.accumulate(sub, [({k: w[k] for k in generic if k in w}, r) for w, r in entries], device=device)
+            engine.accumulate(sub, [({k: w[k] for k in generic if k in w}, r) for w, r in entries], device=device,
+                              **({} if scales is None else {"scales": scales}))
             res = self._adapt_generic(generic, base_weights, current, state_zero)
             if alloc is not None:
                 for k, v in res.items():
@@ -229,7 +239,8 @@ class FedOPT(FedAvg):
         for gi, group in enumerate(key_groups if key_groups is not None else [keys]):
             ks = [k for k in group if k in in_fused]
             if ks:
-                self._launch_fused(ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur)
+                self._launch_fused(ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur,
+                                   scales)
             if after_group is not None:
                 after_group(gi)
         self._prev_current = current
@@ -237,8 +248,11 @@ class FedOPT(FedAvg):
         self.current_weights = OrderedDict((k, new_cur[k]) for k in current.keys() if k in new_cur)
         return self.current_weights
 
-    def _launch_fused(self, ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur):
-        """One flame_fedopt_reduce_adapt launch per dtype over keys ``ks``."""
+    def _launch_fused(self, ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur,
+                      scales=None):
+        """One flame_fedopt_reduce_adapt launch per dtype over keys ``ks``.  A round with clip
+        ``scales`` (the update guard) takes the split path: the scaled reduction, then the
+        adaptive step with no clients."""
         targets = [engine._Target(base_weights[k], device) for k in ks]
         alias = [_same_storage(current[k], base_weights[k]) for k in ks]
         # an aliased key's current is the FedAvg result itself: the kernel takes cur = avg
@@ -258,7 +272,11 @@ class FedOPT(FedAvg):
         avgs = [t.dev for t in targets]
         clients = [[w[k] for w, _ in entries] for k in ks]
         rates = [r for _, r in entries]
-        if self.split_launch:
+        if scales is not None:
+            engine.reduce_(avgs, avgs, clients, rates, scales=scales)
+            engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
+                                        [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
+        elif self.split_launch:
             engine.reduce_(avgs, avgs, clients, rates)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)

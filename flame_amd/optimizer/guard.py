@@ -1,0 +1,108 @@
+"""Server-side update guard: what the aggregator does with the norm and the non-finite count
+of every update it received, before rates are formed.
+
+flame clips on the trainer (``privacy/differential_privacy.py:63-84``, applied to the delta the
+trainer itself reports, ``syncfl/trainer.py:178-185``), so the aggregator takes it on trust.
+Here the same statement runs on the aggregator over the updates as they arrived:
+
+    total_norm = sqrt(sum of squares of every float element)     (:68-76)
+    scale      = clip / (total_norm + 1e-6)  if total_norm > clip (:78-82), else the update as is
+
+``clip_threshold`` has the name and meaning of the job's ``privacy.kwargs.clip_threshold``.
+The scale is host arithmetic in Python floats from the kernel's fp64 sum of squares; it reaches
+the reduction as fp64 and is rounded to fp32 for f32 / bf16 / f16 tensors exactly as rates are.
+
+``nonfinite`` says what happens to an update that holds a NaN or an infinity:
+``"keep"`` (the reference: it poisons every element it touches), ``"raise"`` (ValueError naming
+the ends, before anything is written; the entries have been popped, as the reference's own
+mid-loop raises leave them) or ``"skip"`` (the update is dropped and ``total`` loses its
+``count``).  Non-finite elements add nothing to the norm.
+
+Integer and bool tensors take no part in the norm and are never scaled (the reference's
+``torch.norm`` raises on them).
+
+Known limit: the eager role's running ``total`` is the role's own, so ``"skip"`` there only
+corrects the call that skips; later calls of the round use the role's uncorrected total.
+"""
+import collections
+import math
+
+NONFINITE_POLICIES = ("keep", "raise", "skip")
+NORM_EPS = 1e-6          # differential_privacy.py:80
+
+UpdateRecord = collections.namedtuple("UpdateRecord", "end count norm nonfinite scale skipped")
+
+
+class NonFiniteUpdate(ValueError):
+    """``nonfinite="raise"``: some update holds a NaN or an infinity.  ``records`` holds every
+    update's :class:`UpdateRecord` (nothing skipped, nothing aggregated)."""
+
+    def __init__(self, msg, records):
+        super().__init__(msg)
+        self.records = records
+
+
+def check_kwargs(clip_threshold, nonfinite):
+    """Validate the two constructor kwargs; returns (clip_threshold as float or None, nonfinite)."""
+    if nonfinite not in NONFINITE_POLICIES:
+        raise ValueError(f"nonfinite must be one of {NONFINITE_POLICIES}, not {nonfinite!r}")
+    if clip_threshold is not None:
+        if isinstance(clip_threshold, bool) or not isinstance(clip_threshold, (int, float)):
+            raise TypeError(f"clip_threshold must be a number or None, not {type(clip_threshold).__name__}")
+        clip_threshold = float(clip_threshold)
+        if not (clip_threshold >= 0.0) or math.isinf(clip_threshold):
+            raise ValueError(f"clip_threshold must be a finite number >= 0, not {clip_threshold!r}")
+    return clip_threshold, nonfinite
+
+
+def is_set(clip_threshold, nonfinite) -> bool:
+    return clip_threshold is not None or nonfinite != "keep"
+
+
+def refuse(who: str, clip_threshold, nonfinite, why: str) -> None:
+    """Raise if a class or combination that is out of the guard's scope is asked to guard."""
+    if is_set(clip_threshold, nonfinite):
+        raise NotImplementedError(f"flame_amd {who}: clip_threshold / nonfinite (the server-side update guard) "
+                                  f"are not supported here: {why}")
+
+
+def clip_scale(norm: float, clip_threshold) -> float:
+    """differential_privacy.py:78-82 in Python floats."""
+    if clip_threshold is not None and norm > clip_threshold:
+        return clip_threshold / (norm + NORM_EPS)
+    return 1.0
+
+
+def apply_policy(ends, counts, sumsq, nonfinite, total, clip_threshold, policy):
+    """The guard's decision for one round.  ``ends`` / ``counts`` in cache order, ``sumsq`` /
+    ``nonfinite`` from engine.update_stats.  Returns ``(records, kept, total)``: one
+    :class:`UpdateRecord` per end, the indices that stay, and ``total`` less the skipped counts.
+    Raises :class:`NonFiniteUpdate` (a ValueError carrying the records) under ``"raise"``."""
+    records = []
+    kept = []
+    for i, (end, count, sq, nf) in enumerate(zip(ends, counts, sumsq, nonfinite)):
+        nf = int(nf)
+        norm = math.sqrt(float(sq))
+        skipped = policy == "skip" and nf > 0
+        scale = 1.0 if skipped else clip_scale(norm, clip_threshold)
+        if skipped:
+            total -= count
+        else:
+            kept.append(i)
+        records.append(UpdateRecord(end, count, norm, nf, scale, skipped))
+    bad = [r.end for r in records if r.nonfinite > 0]
+    if policy == "raise" and bad:
+        raise NonFiniteUpdate(f"flame_amd update guard: non-finite values in the update(s) from {bad!r} "
+                              "(nonfinite='raise'); nothing was aggregated", records)
+    return records, kept, total
+
+
+def save_metrics(owner, records) -> None:
+    """``update_norm_max`` / ``updates_clipped`` / ``updates_skipped`` beside the kernel metrics."""
+    mc = getattr(owner, "metric_collector", None)
+    if mc is None or not records:
+        return
+    alias = getattr(owner, "metric_alias", None) or type(owner).__name__.lower()
+    mc.save("update_norm_max", alias, max(r.norm for r in records))
+    mc.save("updates_clipped", alias, sum(1 for r in records if r.scale != 1.0))
+    mc.save("updates_skipped", alias, sum(1 for r in records if r.skipped))

@@ -40,7 +40,10 @@ def _is_pre(state) -> bool:
 class Scaffold(FedAvg):
     """SCAFFOLD class."""
 
-    def __init__(self, k):
+    def __init__(self, k, *, clip_threshold=None, nonfinite: str = "keep"):
+        from . import guard
+        guard.refuse("Scaffold", *guard.check_kwargs(clip_threshold, nonfinite),
+                     "its control variates are summed beside the weights (scaffold.py:141-150); a follow-up")
         super().__init__()
         self.c_glob = None
         if ScaffoldRegularizer is not None:

@@ -599,6 +599,11 @@ class ShardedOptimizer:
     def __init__(self, inner, group=None, device: Optional[torch.device] = None, accumulate_only: bool = False,
                  *, waves: Optional[bool] = None, fracs=DEFAULT_FRACS, align: int = ALIGN_ELEMS,
                  plan: Optional[ShardPlan] = None, gather: bool = True):
+        if getattr(inner, "guarded", False):
+            raise NotImplementedError(
+                "flame_amd ShardedOptimizer: the wrapped optimizer's clip_threshold / nonfinite (the server-side "
+                "update guard) are not supported under sharding: each rank sees only its slices, so the global "
+                "norm needs an all-reduce of the per-update sums of squares (a follow-up)")
         self.inner = inner
         # gather=False (FedAvg / FedProx): no all-gathers -- each rank's base_weights is current on its
         # owned ranges (and the replicated tails) only, one launch over them; for a caller whose next

@@ -29,6 +29,10 @@
  *   flame_elementwise           the same statements for the keys the fused kernels do not take
  *                               (int and mixed-dtype keys; fp64 outside FedOPT): optimizer/fedopt.py:102-129,
  *                               scaffold.py:141-150, feddyn.py:90-113,125-139
+ *   flame_update_stats          privacy/differential_privacy.py:68-76 (the update's total norm), as
+ *                               per-update sums of squares and non-finite counts on the aggregator
+ *   flame_agg_reduce_scaled     privacy/differential_privacy.py:79-82 (torch.mul(d_w, scale)) followed
+ *                               by optimizer/fedavg.py:93-104, in one pass
  *   flame_synth_fill            (bench/test plumbing: counter-based synthetic updates)
  *   flame_hier_resident_per_cu  (no reference counterpart: occupancy query the parameter
  *                               shard uses to size its waves, flame_amd/shard.py)
@@ -166,6 +170,47 @@ int flame_agg_reduce_argmeta(int dtype, unsigned flags, const void *host_meta, i
                              int32_t n_segs, int64_t n_chunks, int32_t n_clients, int64_t off_clients,
                              int64_t off_r32, int64_t off_r64, void *stream);
 int64_t flame_agg_argmeta_max_bytes(void);
+
+/*
+ * Server-side update guard, part 1: per-update statistics.  Restates the norm of
+ * privacy/differential_privacy.py:68-76 (torch.norm of every tensor's norm = the square root of
+ * the sum of squares of all elements) on the aggregator, over the updates it actually received.
+ *   segs, clients : the tables flame_agg_reduce takes; only numel, chunk_begin, flags
+ *                   (FLAME_SEG_UNALIGNED) and client_tile_stride of a segment are read, so one
+ *                   launch covers tensors, tiled UpdateSlab slots and misaligned views alike.
+ *   sumsq         : device double [n_clients];  sumsq[i] += sum of x*x over client i's FINITE
+ *                   elements of every segment (each x widened to fp64 first, every add in fp64).
+ *   nonfinite     : device int64 [n_clients];   nonfinite[i] += number of NaN / +-inf elements
+ *                   (they add nothing to sumsq).
+ *   scratch       : device buffer of >= flame_update_stats_scratch_bytes(n_chunks, n_clients)
+ *                   bytes (scratch_bytes: its size), overwritten.
+ * Both outputs are accumulated into: zero them, then launch once per dtype of a model on one
+ * stream.  No floating-point atomics: partial sums are combined in a fixed order, so the same
+ * launch on the same data gives the same bits.  dtype FLAME_F32, FLAME_BF16, FLAME_F16 or
+ * FLAME_F64 (integer dtypes: FLAME_ENOTSUP); n_clients >= 1.  Not a launch branch of
+ * flame_launch_branches() (one instantiation per dtype).
+ */
+int flame_update_stats(int dtype, const flame_segment *segs, int32_t n_segs, int64_t n_chunks,
+                       const void *const *clients, int32_t n_clients, double *sumsq, int64_t *nonfinite,
+                       void *scratch, int64_t scratch_bytes, void *stream);
+int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients);
+
+/*
+ * Server-side update guard, part 2: flame_agg_reduce with a per-client clip scale.
+ *   scales32 : device [n_clients] fp32 scales (f32 / bf16 / f16); scales64: device [n_clients]
+ *              fp64 scales (FLAME_F64; either may be NULL when the dtype does not use it).
+ * Per element, clients in order, every op rounded once in the tensor's dtype:
+ *   t1  = round(v_i[e] * scale_i)     torch.mul(d_w, scale), differential_privacy.py:79-82
+ *   tmp = round(t1 * rate_i)          fedavg.py:93-104
+ *   acc = round(acc + tmp)
+ * scale_i == 1 reproduces flame_agg_reduce bit for bit.  Float dtypes only (FLAME_ENOTSUP
+ * otherwise); flags FLAME_AGG_INIT_FIRST and FLAME_AGG_XCD_MAP (FLAME_AGG_SEG_RATES:
+ * FLAME_ENOTSUP); device tables only.  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                            int64_t n_chunks, const void *const *clients, int32_t n_clients,
+                            const float *rates32, const double *rates64, const float *scales32,
+                            const double *scales64, void *stream);
 
 /*
  * Fused FedAvg + FedOPT adaptive step (dtype FLAME_F32, FLAME_BF16 or FLAME_F16; base,
