@@ -314,8 +314,9 @@ def materialize(*outs, device=None, into=None):
     ops = (EwOp * len(prog))(*prog)
     ptrs = (ctypes.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
     nbytes = sum(b.numel() * b.element_size() for b in bufs)
-    with engine._timed("flame_elementwise", device, nbytes):
-        N.check(N.lib().flame_elementwise(ops, len(prog), ptrs, len(bufs), numel, engine._stream_ptr(device)))
+    engine._launch("flame_elementwise", nbytes, device, bufs, None,
+                   lambda _: N.lib().flame_elementwise(ops, len(prog), ptrs, len(bufs), numel,
+                                                       engine._stream_ptr(device)))
     engine._keepalive(bufs, device)
     return targets
 
@@ -365,9 +366,9 @@ class Program:
         bufs = ins + outs
         ptrs = (ctypes.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
         numel = ins[0].numel()
-        with engine._timed("flame_elementwise", device, sum(b.numel() * b.element_size() for b in bufs)):
-            N.check(N.lib().flame_elementwise(self.ops, self.n_ops, ptrs, len(bufs), numel,
-                                              engine._stream_ptr(device)))
+        engine._launch("flame_elementwise", sum(b.numel() * b.element_size() for b in bufs), device, bufs, None,
+                       lambda _: N.lib().flame_elementwise(self.ops, self.n_ops, ptrs, len(bufs), numel,
+                                                           engine._stream_ptr(device)))
         engine._keepalive(bufs, device)
         return outs
 
@@ -413,13 +414,13 @@ class Program:
         table = np.asarray([[t.data_ptr() for t in row] + [o.data_ptr() for o in orow] for row, orow in zip(ins, outs)],
                            dtype=np.uint64).reshape(len(rows), n_bufs)
         meta = np.concatenate([table.view(np.int64).reshape(-1), ends])
-        dm = engine._staging.upload(meta, device)
-        base = dm.data_ptr()
-        nbytes = sum(t.numel() * t.element_size() for row in ins + outs for t in row)
-        with engine._timed("flame_elementwise_segments", device, nbytes):
-            N.check(N.lib().flame_elementwise_segments(self.ops, self.n_ops, base, n_bufs, base + table.nbytes,
-                                                       len(rows), total, engine._stream_ptr(device)))
-        engine._keepalive([t for row in ins + outs for t in row] + [dm], device)
+        keep = [t for row in ins + outs for t in row]
+        nbytes = sum(t.numel() * t.element_size() for t in keep)
+        engine._launch("flame_elementwise_segments", nbytes, device, keep, meta,
+                       lambda base: N.lib().flame_elementwise_segments(self.ops, self.n_ops, base, n_bufs,
+                                                                       base + table.nbytes, len(rows), total,
+                                                                       engine._stream_ptr(device)))
+        engine._keepalive(keep, device)
         return outs
 
 

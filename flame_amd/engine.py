@@ -1,9 +1,17 @@
 """Host side of the drop-in path: turns state_dict tensors into segment tables
 and launches the native kernels (``include/flame_amd.h``) on torch's current stream.
 
-Pure-Python planning (``plan``, ``rate32``, ``chunk_elems``) needs no GPU and is
-unit-tested on CPU; the launchers (``reduce_``, ``fedopt_reduce_adapt_``,
-``scale_add_``, ``synth_fill_``) need the native library and a HIP device.
+Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
+``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
+``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
+``feddyn_round_``, ``update_stats``, ``synth_fill_``) need the native library and a HIP device.
+
+Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
+segments, a metadata block from one of the plan functions (all built on ``_Block``), then
+``_launch``.  ``_launch`` alone decides whether the block rides in the kernel arguments or is
+uploaded as a device table, runs the entry point under the timing hooks and checks its status;
+the caller only says how each entry point is called.  What reaches the library this way is
+pinned without a GPU by tests/test_engine_launch_trace.py.
 
 A *segment* is one contiguous tensor (one state_dict entry).  For a reduction,
 row ``s`` of the client table holds, in cache.iterkeys() order, the device
@@ -99,6 +107,48 @@ class Plan:
     off_s64: int = -1
 
 
+class _Block:
+    """A launch's metadata block under construction: the chunk cursor of its segments, the
+    unaligned test of a segment's pointers, and the parts (arrays of 64-bit words, 32-bit arrays
+    padded to 8 bytes) with the byte offset each one starts at."""
+
+    def __init__(self, chunk: int):
+        self.chunk, self.n_chunks = chunk, 0
+        self.parts, self.offs, self.nbytes = [], {}, 0
+
+    def chunk_begin(self, numel: int) -> int:
+        """First chunk of a segment of ``numel`` elements; the cursor moves past it."""
+        begin = self.n_chunks
+        self.n_chunks += -(-numel // self.chunk) if numel > 0 else 0
+        return begin
+
+    @staticmethod
+    def unaligned(fixed, *rows) -> int:
+        """FLAME_SEG_UNALIGNED if a segment's fixed pointer or table row misses 16 bytes."""
+        for r in rows:
+            if (r % VEC_BYTES).any():
+                return N.FLAME_SEG_UNALIGNED
+        return N.FLAME_SEG_UNALIGNED if any(p % VEC_BYTES for p in fixed) else 0
+
+    def add(self, name: str, a: np.ndarray) -> int:
+        """Append a part; returns (and keeps under ``name``) its byte offset."""
+        a = a.reshape(-1)
+        if a.itemsize == 4 and a.size % 2:
+            a = np.concatenate([a, np.zeros(1, a.dtype)])
+        off = self.offs[name] = self.nbytes
+        self.parts.append(a.view(np.int64))
+        self.nbytes += a.nbytes
+        return off
+
+    def finish(self):
+        """(int64 words of the block, chunks of the launch: all segments empty keeps one idle chunk)."""
+        return np.concatenate(self.parts), max(self.n_chunks, 1)
+
+
+def _f32(x) -> np.ndarray:
+    return np.asarray(x, dtype=np.float64).reshape(-1).astype(np.float32)   # RNE, as torch rounds scalars
+
+
 def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] = None,
          seg_rates: bool = False, compact: bool = False, scales: Optional[Sequence] = None) -> Plan:
     """Build the device metadata block for one launch (no GPU needed).
@@ -118,50 +168,30 @@ def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] =
         rates = [r for row in rates for r in row]
     else:
         n = len(rates)
-    chunk = chunk or chunk_elems(code)
+    b = _Block(chunk or chunk_elems(code))
     head = np.zeros((n_segs, SEG_WORDS), dtype=np.uint64)
     table = np.empty((n_segs, n), dtype=np.uint64)
-    begin = 0
     for i, s in enumerate(segs):
         if len(s.clients) != n:
             raise ValueError("every segment needs one pointer per client")
-        row = table[i]
-        row[:] = s.clients
+        table[i] = s.clients
         fixed = (s.out, s.inp, s.cur, s.cur_out, s.m, s.v)
-        unaligned = bool(np.any(row % VEC_BYTES)) or any(p % VEC_BYTES for p in fixed if p)
-        head[i] = (*fixed, s.numel, begin, s.flags | (N.FLAME_SEG_UNALIGNED if unaligned else 0), s.tile_stride)
-        begin += -(-s.numel // chunk) if s.numel > 0 else 0
-    if begin == 0:
-        begin = 1  # all segments empty: one (idle) chunk keeps the launch valid
-    off_clients = head.size * 8
-    off_r32 = off_clients + table.size * 8
+        head[i] = (*fixed, s.numel, b.chunk_begin(s.numel), s.flags | b.unaligned(fixed, table[i]), s.tile_stride)
+    b.add("segs", head)
+    off_clients = b.add("clients", table)
     r64 = np.asarray(rates, dtype=np.float64).reshape(-1)
-    r32 = r64.astype(np.float32)            # RNE, as torch rounds a Python float scalar
-    if r32.size % 2:
-        r32 = np.concatenate([r32, np.zeros(1, np.float32)])
-    parts = [head.view(np.int64).reshape(-1), table.view(np.int64).reshape(-1)]
-    if compact:    # only the rate array the dtype reads (f64 tensors use the fp64 rates)
-        if code == N.FLAME_F64:
-            off_r64, off_r32 = off_r32, -1
-            parts.append(r64.view(np.int64))
-        else:
-            off_r64 = -1
-            parts.append(r32.view(np.int64))
-    else:
-        off_r64 = off_r32 + r32.size * 4
-        parts += [r32.view(np.int64), r64.view(np.int64)]
+    f64 = code == N.FLAME_F64       # compact: only the rate array the dtype reads (f64 tensors the fp64 rates)
+    off_r32 = b.add("r32", _f32(r64)) if not (compact and f64) else -1
+    off_r64 = b.add("r64", r64) if not compact or f64 else -1
     off_s32 = off_s64 = -1
     if scales is not None:
         if seg_rates or compact or len(scales) != n:
             raise ValueError("scales: one per client, device-table plans with one rate per client only")
         s64 = np.asarray(scales, dtype=np.float64).reshape(-1)
-        s32 = s64.astype(np.float32)
-        if s32.size % 2:
-            s32 = np.concatenate([s32, np.zeros(1, np.float32)])
-        off_s32 = sum(x.size for x in parts) * 8
-        off_s64 = off_s32 + s32.size * 4
-        parts += [s32.view(np.int64), s64.view(np.int64)]
-    return Plan(code, np.concatenate(parts), n_segs, begin, n, off_clients, off_r32, off_r64, off_s32, off_s64)
+        off_s32 = b.add("s32", _f32(s64))
+        off_s64 = b.add("s64", s64)
+    meta, n_chunks = b.finish()
+    return Plan(code, meta, n_segs, n_chunks, n, off_clients, off_r32, off_r64, off_s32, off_s64)
 
 
 # ------------------------------------------------------------------ device staging
@@ -294,9 +324,43 @@ def _keepalive(tensors, device):
             _staging.hold(t, device)
 
 
-def _device_ptrs(dev_meta: torch.Tensor, p: Plan):
-    base = dev_meta.data_ptr()
-    return base, base + p.off_clients, base + p.off_r32, base + p.off_r64
+def _stage(meta: np.ndarray, device, keep) -> torch.Tensor:
+    """The device copy of a metadata block, kept in ``keep`` (a caller that must stage every
+    block before its first launch hands the copy to :func:`_launch` instead of the block)."""
+    dm = _staging.upload(meta, device)
+    keep.append(dm)
+    return dm
+
+
+def _launch(name, nbytes, device, keep, meta, table, argmeta=None) -> None:
+    """THE path of every native launch: ``name`` and ``nbytes`` (algorithmic bytes) go to the
+    timing hooks, the entry point's status to ``N.check``.
+
+    ``meta`` is the launch's metadata block.  It rides in the kernel arguments --
+    ``argmeta(host address, bytes)`` -- when ARGMETA is on, the caller offers that entry point and
+    the block fits :func:`argmeta_max_bytes`; otherwise it is uploaded (the device copy joins
+    ``keep``) and ``table(device base address)`` runs.  ``meta`` may be a copy :func:`_stage` made
+    earlier, or None for a launch without a block (``table(None)``)."""
+    if argmeta is not None and ARGMETA and meta.nbytes <= argmeta_max_bytes():
+        with _timed(name, device, nbytes):
+            N.check(argmeta(meta.ctypes.data, meta.nbytes))
+        return
+    if isinstance(meta, np.ndarray):
+        meta = _stage(meta, device, keep)
+    base = meta.data_ptr() if meta is not None else None
+    with _timed(name, device, nbytes):
+        N.check(table(base))
+
+
+def by_dtype(items, dtype_of, also=None) -> "collections.OrderedDict":
+    """``items`` grouped by the kernel dtype code of ``dtype_of(item)``: code -> items, codes and
+    items in first-seen order (one launch per dtype).  With ``also`` the key is
+    ``(code, also(item))``."""
+    groups = collections.OrderedDict()
+    for x in items:
+        code = dtype_code(dtype_of(x))
+        groups.setdefault(code if also is None else (code, also(x)), []).append(x)
+    return groups
 
 
 # ------------------------------------------------------------------ launches
@@ -373,6 +437,21 @@ def _client_row(cs, o: torch.Tensor, device, keep):
     return row, 0
 
 
+def _middle_rows(per_middle, o, device, keep):
+    """One key's arrival pointers of a hierarchy, middle-major (``per_middle``: each middle's
+    client tensors in arrival order; ``o`` as for :func:`_client_row`) with the one tile stride
+    every middle's row has: ``(uint64 pointers, stride)``, or None when the strides differ."""
+    ptrs, stride = [], None
+    for cs in per_middle:
+        row, ts = _client_row(cs, o, device, keep)
+        if stride is None:
+            stride = ts
+        elif ts != stride:
+            return None
+        ptrs.extend(row)
+    return np.asarray(ptrs, dtype=np.uint64), stride
+
+
 def host_device_pointer(host_ptr: int) -> int:
     """Device address of a pinned / hipHostRegister-ed host address (zero-copy reads)."""
     out = ctypes.c_void_p()
@@ -399,11 +478,8 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
     device = outs[0].device
     if device.type != "cuda":
         raise RuntimeError("flame_amd.reduce_: output tensors must live on the GPU (no CPU fallback)")
-    groups = collections.OrderedDict()
-    for s, o in enumerate(outs):
-        groups.setdefault(dtype_code(o.dtype), []).append(s)
     keep = []
-    for code, idx in groups.items():
+    for code, idx in by_dtype(range(len(outs)), lambda s: outs[s].dtype).items():
         segs = []
         for s in idx:
             o = outs[s]
@@ -429,41 +505,32 @@ def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rat
         flags |= N.FLAME_AGG_SEG_RATES
     n_cl = _n_clients(rates, seg_rates)
     nbytes = sum(s.numel for s in segs) * ITEMSIZE[code] * (n_cl + (1 if init_first else 2))
-    if scales is not None:
-        if seg_rates or code not in FLOAT_CODES:
-            raise NotImplementedError("flame_amd: a scaled reduction takes float tensors and one rate per client")
-        p = plan(code, segs, rates, scales=scales)
-        if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs):
-            flags |= N.FLAME_AGG_XCD_MAP
-        dm = _staging.upload(p.meta, device)
-        segp, clp, r32p, r64p = _device_ptrs(dm, p)
-        with _timed("flame_agg_reduce_scaled", device, nbytes):
-            N.check(L.flame_agg_reduce_scaled(code, flags, segp, p.n_segs, p.n_chunks, clp, p.n_clients, r32p, r64p,
-                                              dm.data_ptr() + p.off_s32, dm.data_ptr() + p.off_s64,
-                                              _stream_ptr(device)))
-        keep.append(dm)
-        return
+    if scales is not None and (seg_rates or code not in FLOAT_CODES):
+        raise NotImplementedError("flame_amd: a scaled reduction takes float tensors and one rate per client")
+    # the compact block's size is known before anything is built: a big launch builds one plan, not two
     est = compact_meta_bytes(code, len(segs), n_cl, seg_rates)
-    if ARGMETA and est <= argmeta_max_bytes():
+    if scales is None and ARGMETA and est <= argmeta_max_bytes():
         # small launch: the metadata block goes with the dispatch as a kernel argument (no H2D blit)
         p = plan(code, segs, rates, seg_rates=seg_rates, compact=True)
         assert p.meta.nbytes == est
-        with _timed("flame_agg_reduce", device, nbytes):
-            N.check(L.flame_agg_reduce_argmeta(code, flags, p.meta.ctypes.data, p.meta.nbytes, p.n_segs,
-                                               p.n_chunks, p.n_clients, p.off_clients, p.off_r32, p.off_r64,
-                                               _stream_ptr(device)))
+        _launch("flame_agg_reduce", nbytes, device, keep, p.meta, None,
+                lambda host, n: L.flame_agg_reduce_argmeta(code, flags, host, n, p.n_segs, p.n_chunks, p.n_clients,
+                                                           p.off_clients, p.off_r32, p.off_r64, _stream_ptr(device)))
         return
-    p = plan(code, segs, rates, seg_rates=seg_rates)
+    p = plan(code, segs, rates, seg_rates=seg_rates, scales=scales)
     if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs):
         # clients as separate tensors: each XCD streams a contiguous eighth of the chunks
         # (C3 rows 16.25 -> 15.89 ms; a tiled slab loses with it)
         flags |= N.FLAME_AGG_XCD_MAP
-    dm = _staging.upload(p.meta, device)
-    segp, clp, r32p, r64p = _device_ptrs(dm, p)
-    with _timed("flame_agg_reduce", device, nbytes):
-        N.check(L.flame_agg_reduce(code, flags, segp, p.n_segs, p.n_chunks, clp, p.n_clients, r32p, r64p,
-                                   _stream_ptr(device)))
-    keep.append(dm)
+    if scales is None:
+        _launch("flame_agg_reduce", nbytes, device, keep, p.meta,
+                lambda b: L.flame_agg_reduce(code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+                                             b + p.off_r32, b + p.off_r64, _stream_ptr(device)))
+    else:
+        _launch("flame_agg_reduce_scaled", nbytes, device, keep, p.meta,
+                lambda b: L.flame_agg_reduce_scaled(code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients,
+                                                    p.n_clients, b + p.off_r32, b + p.off_r64, b + p.off_s32,
+                                                    b + p.off_s64, _stream_ptr(device)))
 
 
 # Row-layout launches of at least this many chunks take the XCD-contiguous chunk map.
@@ -508,62 +575,70 @@ def fedopt_reduce_adapt_(variant: str, avg_out: List[Optional[torch.Tensor]], ba
         return
     device = base[0].device
     L = N.lib()
-    groups = collections.OrderedDict()
-    for s_, b in enumerate(base):
-        groups.setdefault(dtype_code(b.dtype), []).append(s_)
-    h64 = _scalars64(hyper) if N.FLAME_F64 in groups else None
+    groups = by_dtype(range(len(base)), lambda s: base[s].dtype)
+    scalars = {code: _fedopt_group_scalars(code, hyper, base[idx[0]].dtype) for code, idx in groups.items()}
+    aliased = cur_is_avg if cur_is_avg is not None else [False] * len(base)
+    opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
     for code, idx in groups.items():
-        segs, keep = [], []
-        p_alias = 0
-        for s_ in idx:
-            alias = bool(cur_is_avg[s_]) if cur_is_avg is not None else False
-            for t in (base[s_], cur_out[s_], m[s_], v[s_]) + (() if alias else (cur[s_],)):
-                assert t.dtype == base[s_].dtype and t.is_contiguous() and t.device == device
-            row, tstride = _client_row(clients[s_], base[s_], device, keep)
-            segs.append(Seg(base[s_].numel(), out=avg_out[s_].data_ptr() if avg_out[s_] is not None else 0,
-                            inp=base[s_].data_ptr(), cur=0 if alias else cur[s_].data_ptr(),
-                            cur_out=cur_out[s_].data_ptr(), m=m[s_].data_ptr(), v=v[s_].data_ptr(), clients=row,
-                            tile_stride=tstride, flags=N.FLAME_SEG_CUR_IS_AVG if alias else 0))
-            p_alias += base[s_].numel() if alias else 0
-        P = sum(sg.numel for sg in segs)
-        isz = ITEMSIZE[code]
-        # clients + base + cur (+ m, v unless zero state) read; avg, m, v, cur_out written
-        nbytes = isz * (P * (len(rates) + 2 + (0 if state_zero else 2) + 4) - p_alias)
-        h = list(hyper)
-        if code in (N.FLAME_BF16, N.FLAME_F16):  # torch-CPU rounds the scalar of `sqrt(v) + tau`
-            h[5] = float(torch.tensor(float(h[5]), dtype=base[idx[0]].dtype))
-        opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
+        keep = []
+        segs, p_alias = _fedopt_segs(idx, avg_out, base, cur, cur_out, m, v, clients, aliased, device, keep)
+        nbytes = _fedopt_bytes(code, segs, len(rates), state_zero, p_alias)
+        h = scalars[code]
         if code == N.FLAME_F64:
             # fp64 rates, the unrounded scalars, always the device table (no kernel-argument variant)
             p = plan(code, segs, rates)
-            dm = _staging.upload(p.meta, device)
-            segp, clp, _, r64p = _device_ptrs(dm, p)
-            with _timed("flame_fedopt_reduce_adapt", device, nbytes):
-                N.check(L.flame_fedopt_reduce_adapt_f64(FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs,
-                                                        p.n_chunks, clp, p.n_clients, r64p, *h64,
-                                                        _stream_ptr(device)))
-            keep.append(dm)
-            _keepalive(keep, device)
-            continue
-        if ARGMETA and compact_meta_bytes(code, len(segs), len(rates)) <= argmeta_max_bytes():
+            _launch("flame_fedopt_reduce_adapt", nbytes, device, keep, p.meta,
+                    lambda b: L.flame_fedopt_reduce_adapt_f64(FEDOPT_VARIANT[variant], opt_flags, b, p.n_segs,
+                                                              p.n_chunks, b + p.off_clients, p.n_clients,
+                                                              b + p.off_r64, *h, _stream_ptr(device)))
+        elif ARGMETA and compact_meta_bytes(code, len(segs), len(rates)) <= argmeta_max_bytes():
             # small round: the metadata block rides in the kernel arguments (no H2D blit)
             p = plan(code, segs, rates, compact=True)
-            with _timed("flame_fedopt_reduce_adapt", device, nbytes):
-                N.check(L.flame_fedopt_reduce_adapt_argmeta(code, FEDOPT_VARIANT[variant], opt_flags,
-                                                            p.meta.ctypes.data, p.meta.nbytes, p.n_segs,
-                                                            p.n_chunks, p.n_clients, p.off_clients, p.off_r32,
-                                                            *[float(x) for x in h], _stream_ptr(device)))
-            _keepalive(keep, device)
-            continue
-        p = plan(code, segs, rates)
-        dm = _staging.upload(p.meta, device)
-        segp, clp, r32p, _ = _device_ptrs(dm, p)
-        with _timed("flame_fedopt_reduce_adapt", device, nbytes):
-            N.check(L.flame_fedopt_reduce_adapt(code, FEDOPT_VARIANT[variant], opt_flags,
-                                                segp, p.n_segs, p.n_chunks, clp, p.n_clients, r32p,
-                                                *[float(x) for x in h], _stream_ptr(device)))
-        keep.append(dm)
+            _launch("flame_fedopt_reduce_adapt", nbytes, device, keep, p.meta, None,
+                    lambda host, n: L.flame_fedopt_reduce_adapt_argmeta(
+                        code, FEDOPT_VARIANT[variant], opt_flags, host, n, p.n_segs, p.n_chunks, p.n_clients,
+                        p.off_clients, p.off_r32, *h, _stream_ptr(device)))
+        else:
+            p = plan(code, segs, rates)
+            _launch("flame_fedopt_reduce_adapt", nbytes, device, keep, p.meta,
+                    lambda b: L.flame_fedopt_reduce_adapt(code, FEDOPT_VARIANT[variant], opt_flags, b, p.n_segs,
+                                                          p.n_chunks, b + p.off_clients, p.n_clients, b + p.off_r32,
+                                                          *h, _stream_ptr(device)))
         _keepalive(keep, device)
+
+
+def _fedopt_segs(idx, outs, base, cur, cur_out, m, v, clients, aliased, device, keep):
+    """Segments ``idx`` (one dtype group) of a FedOPT launch, and how many of their elements have
+    no current to read.  ``outs[s]`` receives the FedAvg result (None: not written);
+    ``aliased[s]``: segment s's current IS that result (FLAME_SEG_CUR_IS_AVG, ``cur[s]`` unread)."""
+    segs, p_alias = [], 0
+    for s in idx:
+        b, alias = base[s], bool(aliased[s])
+        for t in (b, cur_out[s], m[s], v[s]) + (() if alias else (cur[s],)):
+            assert t.dtype == b.dtype and t.is_contiguous() and t.device == device
+        row, tstride = _client_row(clients[s], b, device, keep)
+        segs.append(Seg(b.numel(), out=outs[s].data_ptr() if outs[s] is not None else 0, inp=b.data_ptr(),
+                        cur=0 if alias else cur[s].data_ptr(), cur_out=cur_out[s].data_ptr(), m=m[s].data_ptr(),
+                        v=v[s].data_ptr(), clients=row, tile_stride=tstride,
+                        flags=N.FLAME_SEG_CUR_IS_AVG if alias else 0))
+        p_alias += b.numel() if alias else 0
+    return segs, p_alias
+
+
+def _fedopt_bytes(code, segs, n_clients, state_zero, p_alias) -> int:
+    """clients + base + cur (+ m, v unless zero state) read once; avg / base, m, v, cur_out written once."""
+    P = sum(sg.numel for sg in segs)
+    return ITEMSIZE[code] * (P * (n_clients + 2 + (0 if state_zero else 2) + 4) - p_alias)
+
+
+def _fedopt_group_scalars(code, hyper, dtype):
+    """The six scalars a dtype group's kernel takes: the doubles for fp64, else the fp32 values."""
+    if code == N.FLAME_F64:
+        return _scalars64(hyper)
+    h = [float(x) for x in hyper]
+    if code in (N.FLAME_BF16, N.FLAME_F16):  # torch-CPU rounds the scalar of `sqrt(v) + tau`
+        h[5] = float(torch.tensor(h[5], dtype=dtype))
+    return h
 
 
 def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[torch.Tensor]],
@@ -583,58 +658,40 @@ def fedopt_chain_(variant: str, base: List[torch.Tensor], cur: List[Optional[tor
     L = N.lib()
     if not step_end or not step_end[-1]:
         raise ValueError("fedopt_chain_: the last client must close a do() call")
-    ends_host = np.asarray([1 if e else 0 for e in step_end], dtype=np.uint8)
-    groups = collections.OrderedDict()
-    for s_, b in enumerate(base):
-        groups.setdefault(dtype_code(b.dtype), []).append(s_)
+    ends = np.zeros(-(-len(step_end) // 8) * 8, dtype=np.uint8)
+    ends[:len(step_end)] = [1 if e else 0 for e in step_end]
+    groups = by_dtype(range(len(base)), lambda s: base[s].dtype)
     for code, idx in groups.items():
         if code not in FLOAT_CODES:
             raise NotImplementedError(f"fedopt_chain_: dtype {base[idx[0]].dtype}")
-    h64 = _scalars64(hyper) if N.FLAME_F64 in groups else None
+    scalars = {code: _fedopt_group_scalars(code, hyper, base[idx[0]].dtype) for code, idx in groups.items()}
+    opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
     # every dtype group is planned and its tables uploaded BEFORE the first launch: a failure
     # there (a bad tensor, an allocation) leaves base / m / v untouched.  Only a
     # launch itself failing after another group's launch ran can leave the groups out of step;
     # that exception carries flame_partial = True (FedOPT then refuses further calls).
     launches = []
     for code, idx in groups.items():
-        segs, keep = [], []
-        p_alias = 0
-        for s_ in idx:
-            b = base[s_]
-            alias = bool(first_aliased[s_])
-            for t in (b, cur_out[s_], m[s_], v[s_]) + (() if alias else (cur[s_],)):
-                assert t.dtype == b.dtype and t.is_contiguous() and t.device == device
-            row, tstride = _client_row(clients[s_], b, device, keep)
-            segs.append(Seg(b.numel(), out=b.data_ptr(), inp=b.data_ptr(), cur=0 if alias else cur[s_].data_ptr(),
-                            cur_out=cur_out[s_].data_ptr(), m=m[s_].data_ptr(), v=v[s_].data_ptr(), clients=row,
-                            tile_stride=tstride, flags=N.FLAME_SEG_CUR_IS_AVG if alias else 0))
-            p_alias += b.numel() if alias else 0
-        P = sum(sg.numel for sg in segs)
-        # clients + base + cur (+ m, v unless zero state) read once; base, m, v, cur_out written once
-        nbytes = ITEMSIZE[code] * (P * (len(rates) + 2 + (0 if state_zero else 2) + 4) - p_alias)
-        h = list(hyper)
-        if code in (N.FLAME_BF16, N.FLAME_F16):  # torch-CPU rounds the scalar of `sqrt(v) + tau`
-            h[5] = float(torch.tensor(float(h[5]), dtype=base[idx[0]].dtype))
+        keep = []
+        segs, p_alias = _fedopt_segs(idx, base, base, cur, cur_out, m, v, clients, first_aliased, device, keep)
         p = plan(code, segs, rates)
         # the step_end bytes ride behind the plan's tables: one upload per launch
-        pad = np.zeros(-(-ends_host.size // 8) * 8, dtype=np.uint8)
-        pad[:ends_host.size] = ends_host
-        dm = _staging.upload(np.concatenate([p.meta, pad.view(np.int64)]), device)
-        keep.append(dm)
-        launches.append((code, p, dm, h, nbytes, keep))
-    for i, (code, p, dm, h, nbytes, keep) in enumerate(launches):
-        segp, clp, r32p, r64p = _device_ptrs(dm, p)
-        opt_flags = N.FLAME_OPT_STATE_ZERO if state_zero else 0
+        dm = _stage(np.concatenate([p.meta, ends.view(np.int64)]), device, keep)
+        launches.append((code, p, dm, _fedopt_bytes(code, segs, len(rates), state_zero, p_alias), keep))
+    for i, (code, p, dm, nbytes, keep) in enumerate(launches):
+        h = scalars[code]
+        if code == N.FLAME_F64:      # fp64 rates, the unrounded scalars
+            def call(b):
+                return L.flame_fedopt_chain_f64(FEDOPT_VARIANT[variant], opt_flags, b, p.n_segs, p.n_chunks,
+                                                b + p.off_clients, p.n_clients, b + p.off_r64, b + p.meta.nbytes,
+                                                *h, _stream_ptr(device))
+        else:
+            def call(b):
+                return L.flame_fedopt_chain(code, FEDOPT_VARIANT[variant], opt_flags, b, p.n_segs, p.n_chunks,
+                                            b + p.off_clients, p.n_clients, b + p.off_r32, b + p.meta.nbytes,
+                                            *h, _stream_ptr(device))
         try:
-            with _timed("flame_fedopt_chain", device, nbytes):
-                if code == N.FLAME_F64:      # fp64 rates, the unrounded scalars
-                    N.check(L.flame_fedopt_chain_f64(FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs, p.n_chunks,
-                                                     clp, p.n_clients, r64p, dm.data_ptr() + p.meta.nbytes,
-                                                     *h64, _stream_ptr(device)))
-                else:
-                    N.check(L.flame_fedopt_chain(code, FEDOPT_VARIANT[variant], opt_flags, segp, p.n_segs,
-                                                 p.n_chunks, clp, p.n_clients, r32p, dm.data_ptr() + p.meta.nbytes,
-                                                 *[float(x) for x in h], _stream_ptr(device)))
+            _launch("flame_fedopt_chain", nbytes, device, keep, dm, call)
         except Exception as e:
             if i:
                 e.flame_partial = True
@@ -679,16 +736,13 @@ def scale_add_(bases: List[torch.Tensor], aggs: List[torch.Tensor], goal: int,
         return
     device = bases[0].device
     L = N.lib()
-    groups = collections.OrderedDict()
-    for s, b in enumerate(bases):
-        code = dtype_code(b.dtype) if b.is_floating_point() else None
-        if code not in FLOAT_CODES:
+    for b in bases:
+        if not b.is_floating_point() or dtype_code(b.dtype) not in FLOAT_CODES:
             # torch: int_tensor / int -> float; in-place add into an int tensor raises
             raise RuntimeError(f"result type Float can't be cast to the desired output type "
                                f"{str(b.dtype).replace('torch.', '').capitalize()}")
-        groups.setdefault(code, []).append(s)
     keep = []
-    for code, idx in groups.items():
+    for code, idx in by_dtype(range(len(bases)), lambda s: bases[s].dtype).items():
         segs = []
         for s in idx:
             b = bases[s]
@@ -704,12 +758,9 @@ def scale_add_(bases: List[torch.Tensor], aggs: List[torch.Tensor], goal: int,
         if not segs:
             continue
         p = plan(code, segs, [], chunk=chunk_elems(code, scale_add=True))
-        dm = _staging.upload(p.meta, device)
         nbytes = sum(s.numel for s in segs) * ITEMSIZE[code] * (3 + (1 if deltas is not None else 0))
-        with _timed("flame_fedbuff_scale_add", device, nbytes):
-            N.check(L.flame_fedbuff_scale_add(code, dm.data_ptr(), p.n_segs, p.n_chunks, int(goal),
-                                              _stream_ptr(device)))
-        keep.append(dm)
+        _launch("flame_fedbuff_scale_add", nbytes, device, keep, p.meta,
+                lambda b: L.flame_fedbuff_scale_add(code, b, p.n_segs, p.n_chunks, int(goal), _stream_ptr(device)))
     _keepalive(keep, device)
 
 
@@ -768,13 +819,6 @@ class HierPlan:
     offs: dict            # byte offsets of the tables inside the device copy of ``meta``
 
 
-def _f32_words(x) -> np.ndarray:
-    a = np.asarray(x, dtype=np.float64).reshape(-1).astype(np.float32)   # RNE, as torch rounds scalars
-    if a.size % 2:
-        a = np.concatenate([a, np.zeros(1, np.float32)])
-    return a.view(np.int64)
-
-
 def plan_hier(code: int, segs: Sequence[HierSeg], mid_rates, mid_goals, top_rates) -> HierPlan:
     """Device metadata of one flame_hier_fedbuff launch (no GPU needed):
     [segments (8 words)] [mid_w S x M] [mid_delta S x M] [clients S x M x C]
@@ -788,12 +832,11 @@ def plan_hier(code: int, segs: Sequence[HierSeg], mid_rates, mid_goals, top_rate
     C = len(mid_rates[0])
     if C == 0 or any(len(r) != C for r in mid_rates):
         raise ValueError("every middle needs the same (>= 1) number of arrivals")
-    chunk = chunk_elems(code)
+    b = _Block(chunk_elems(code))
     head = np.zeros((S, HSEG_WORDS), dtype=np.uint64)
     wtab = np.empty((S, M), dtype=np.uint64)
     dtab = np.zeros((S, M), dtype=np.uint64)
     ctab = np.empty((S, M * C), dtype=np.uint64)
-    begin = 0
     for i, s in enumerate(segs):
         if len(s.mid_w) != M or len(s.clients) != M * C or (s.mid_delta is not None and len(s.mid_delta) != M):
             raise ValueError("segment tables must be [n_mids] and [n_mids * n_clients]")
@@ -801,22 +844,14 @@ def plan_hier(code: int, segs: Sequence[HierSeg], mid_rates, mid_goals, top_rate
         ctab[i] = s.clients
         if s.mid_delta is not None:
             dtab[i] = s.mid_delta
-        fixed = [s.top_w, s.top_in, s.top_out]
-        unaligned = (bool(np.any(ctab[i] % VEC_BYTES)) or bool(np.any(wtab[i] % VEC_BYTES))
-                     or bool(np.any(dtab[i] % VEC_BYTES)) or any(p % VEC_BYTES for p in fixed if p))
-        head[i] = (*fixed, s.numel, begin, N.FLAME_SEG_UNALIGNED if unaligned else 0, s.tile_stride,
-                   s.mid_tile_stride)
-        begin += -(-s.numel // chunk) if s.numel > 0 else 0
-    if begin == 0:
-        begin = 1
-    parts = [head.view(np.int64).reshape(-1), wtab.view(np.int64).reshape(-1), dtab.view(np.int64).reshape(-1),
-             ctab.view(np.int64).reshape(-1), _f32_words(mid_rates), _f32_words(mid_goals), _f32_words(top_rates)]
-    names = ["segs", "mid_w", "mid_delta", "clients", "mid_rates", "mid_goal", "top_rates"]
-    offs, o = {}, 0
-    for nm, p in zip(names, parts):
-        offs[nm] = o
-        o += p.size * 8
-    return HierPlan(code, np.concatenate(parts), S, begin, M, C, offs)
+        fixed = (s.top_w, s.top_in, s.top_out)
+        head[i] = (*fixed, s.numel, b.chunk_begin(s.numel), b.unaligned(fixed, ctab[i], wtab[i], dtab[i]),
+                   s.tile_stride, s.mid_tile_stride)
+    for nm, a in (("segs", head), ("mid_w", wtab), ("mid_delta", dtab), ("clients", ctab),
+                  ("mid_rates", _f32(mid_rates)), ("mid_goal", _f32(mid_goals)), ("top_rates", _f32(top_rates))):
+        b.add(nm, a)
+    meta, n_chunks = b.finish()
+    return HierPlan(code, meta, S, n_chunks, M, C, b.offs)
 
 
 def hier_fedbuff_(segs: Sequence[HierSeg], code: int, mid_rates, mid_goals, top_rates, *, top_accum: bool,
@@ -837,23 +872,17 @@ def hier_fedbuff_(segs: Sequence[HierSeg], code: int, mid_rates, mid_goals, top_
     top_out = any(s.top_out for s in segs)
     nbytes = isz * (P * (M * C + (M if with_delta else 0) + (1 if top_accum else 0) + (1 if top_out else 0)
                          + (2 if top_goal is not None else 0)) + wsum * (1 if mid_readonly else 2))
-    if ARGMETA and p.meta.nbytes <= argmeta_max_bytes():
-        # small launch (e.g. one FedBuff aggregator's fused scale_add): metadata as a kernel argument
-        o = p.offs
-        with _timed("flame_hier_fedbuff", device, nbytes):
-            N.check(L.flame_hier_fedbuff_argmeta(code, flags, p.meta.ctypes.data, p.meta.nbytes, p.n_segs, p.n_chunks,
-                                                 M, C, o["mid_w"], o["mid_delta"] if with_delta else -1, o["clients"],
-                                                 o["mid_rates"], o["mid_goal"], o["top_rates"], float(top_goal or 0),
-                                                 _stream_ptr(device)))
-        return
-    dm = _staging.upload(p.meta, device)
-    b = dm.data_ptr()
-    with _timed("flame_hier_fedbuff", device, nbytes):
-        N.check(L.flame_hier_fedbuff(code, flags, b + p.offs["segs"], p.n_segs, p.n_chunks, M, C,
-                                     b + p.offs["mid_w"], b + p.offs["mid_delta"] if with_delta else None,
-                                     b + p.offs["clients"], b + p.offs["mid_rates"], b + p.offs["mid_goal"],
-                                     b + p.offs["top_rates"], float(top_goal or 0), _stream_ptr(device)))
-    keep.append(dm)
+    o = p.offs
+    # a small launch (e.g. one FedBuff aggregator's fused scale_add) takes its metadata as a kernel argument
+    _launch("flame_hier_fedbuff", nbytes, device, keep, p.meta,
+            lambda b: L.flame_hier_fedbuff(code, flags, b + o["segs"], p.n_segs, p.n_chunks, M, C, b + o["mid_w"],
+                                           b + o["mid_delta"] if with_delta else None, b + o["clients"],
+                                           b + o["mid_rates"], b + o["mid_goal"], b + o["top_rates"],
+                                           float(top_goal or 0), _stream_ptr(device)),
+            lambda host, n: L.flame_hier_fedbuff_argmeta(code, flags, host, n, p.n_segs, p.n_chunks, M, C, o["mid_w"],
+                                                         o["mid_delta"] if with_delta else -1, o["clients"],
+                                                         o["mid_rates"], o["mid_goal"], o["top_rates"],
+                                                         float(top_goal or 0), _stream_ptr(device)))
 
 
 def hier_resident_per_cu(code: int, n_mids: int, sync: bool = False) -> int:
@@ -911,41 +940,35 @@ def plan_feddyn(code: int, segs: Sequence[DynSeg], flags: Sequence[int]):
     S, K = len(segs), len(flags)
     if S == 0 or K == 0:
         raise ValueError("feddyn plan needs >= 1 segment and >= 1 step")
-    chunk = chunk_elems(code)
+    b = _Block(chunk_elems(code))
     head = np.zeros((S, N.DYN_SEGMENT_INT64S), dtype=np.uint64)
     tab = np.zeros((S, K * 3), dtype=np.uint64)
-    begin = 0
     for i, s in enumerate(segs):
         if len(s.steps) != K:
             raise ValueError("every segment needs one pointer triple per step")
         tab[i] = np.asarray(s.steps, dtype=np.uint64).reshape(-1)
-        unaligned = bool(np.any(tab[i] % VEC_BYTES)) or any(p % VEC_BYTES for p in (s.out, s.inp, s.cld))
-        head[i] = (s.out, s.inp, s.cld, s.numel, begin, N.FLAME_SEG_UNALIGNED if unaligned else 0, s.tile_stride,
+        fixed = (s.out, s.inp, s.cld)
+        head[i] = (*fixed, s.numel, b.chunk_begin(s.numel), b.unaligned(fixed, tab[i]), s.tile_stride,
                    s.hist_tile_stride)
-        begin += -(-s.numel // chunk) if s.numel > 0 else 0
-    fl = np.asarray(flags, dtype=np.uint32)
-    if fl.size % 2:
-        fl = np.concatenate([fl, np.zeros(1, np.uint32)])
-    parts = [head.view(np.int64).reshape(-1), tab.view(np.int64).reshape(-1), fl.view(np.int64)]
-    offs = {"segs": 0, "steps": parts[0].size * 8, "flags": (parts[0].size + parts[1].size) * 8}
-    return np.concatenate(parts), max(begin, 1), offs
+    b.add("segs", head)
+    b.add("steps", tab)
+    b.add("flags", np.asarray(flags, dtype=np.uint32))
+    meta, n_chunks = b.finish()
+    return meta, n_chunks, b.offs
 
 
 def feddyn_round_(code: int, segs: Sequence[DynSeg], flags: Sequence[int], n_phase1: int, rate_avg: float,
                   rate_mean: float, device, keep: list) -> None:
     """One flame_feddyn_round launch (the caller checked dtypes / devices / contiguity)."""
     meta, n_chunks, offs = plan_feddyn(code, segs, flags)
-    dm = _staging.upload(meta, device)
-    b = dm.data_ptr()
     P = sum(s.numel for s in segs)
     reads = sum(bool(f & N.FLAME_DYN_W) + bool(f & N.FLAME_DYN_HIN) for f in flags)
     writes = sum(bool(f & N.FLAME_DYN_HOUT) for f in flags)
     nbytes = ITEMSIZE[code] * P * (reads + writes + 3)     # + base read, average and cld written
-    with _timed("flame_feddyn_round", device, nbytes):
-        N.check(N.lib().flame_feddyn_round(code, b + offs["segs"], len(segs), n_chunks, b + offs["steps"],
-                                           b + offs["flags"], len(flags), n_phase1, float(rate_avg),
-                                           float(rate_mean), _stream_ptr(device)))
-    keep.append(dm)
+    _launch("flame_feddyn_round", nbytes, device, keep, meta,
+            lambda b: N.lib().flame_feddyn_round(code, b + offs["segs"], len(segs), n_chunks, b + offs["steps"],
+                                                 b + offs["flags"], len(flags), n_phase1, float(rate_avg),
+                                                 float(rate_mean), _stream_ptr(device)))
 
 
 def synth_fill_(out: torch.Tensor, seed: int, stream_id: int, start: int, sigma: float) -> None:
@@ -1109,7 +1132,7 @@ def update_stats(weights_list, device=None):
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     keep = []
-    groups = collections.OrderedDict()          # (dtype code, client indices) -> [Seg]
+    items = []                                  # (dtype, client indices, Seg), one per key
     all_cis = tuple(range(n))
     w0 = ws[0]
     rows = None
@@ -1121,8 +1144,7 @@ def update_stats(weights_list, device=None):
         if rows is not None:
             for k in fkeys:
                 ptrs, tile_bytes = rows[k]
-                groups.setdefault((dtype_code(dts[k]), all_cis), []).append(
-                    Seg(numels[k], clients=ptrs, tile_stride=tile_bytes))
+                items.append((dts[k], all_cis, Seg(numels[k], clients=ptrs, tile_stride=tile_bytes)))
     if rows is None:
         per = collections.OrderedDict()         # (key, dtype) -> client indices, in first-seen order
         for ci, w in enumerate(ws):
@@ -1134,7 +1156,8 @@ def update_stats(weights_list, device=None):
         for (k, dt), cis in per.items():
             numel = _numel_of(logical_shape(ws[cis[0]], k))
             row, tstride = _client_row([ws[ci][k] for ci in cis], _KeyLike(numel, dt), device, keep)
-            groups.setdefault((dtype_code(dt), tuple(cis)), []).append(Seg(numel, clients=row, tile_stride=tstride))
+            items.append((dt, tuple(cis), Seg(numel, clients=row, tile_stride=tstride)))
+    groups = by_dtype(items, lambda it: it[0], also=lambda it: it[1])     # (dtype code, client indices) -> items
     # one output block per distinct client set (normally one: every update has every key)
     slots, total = collections.OrderedDict(), 0
     for (_, cis) in groups:
@@ -1145,19 +1168,16 @@ def update_stats(weights_list, device=None):
         return np.zeros(n, np.float64), np.zeros(n, np.int64)
     out = torch.zeros(2 * total, dtype=torch.int64, device=device)      # [sumsq as doubles | counts]
     L = N.lib()
-    plans = [(code, cis, plan(code, segs, [0.0] * len(cis)), sum(s.numel for s in segs))
-             for (code, cis), segs in groups.items()]
+    plans = [(code, cis, plan(code, [sg for _, _, sg in its], [0.0] * len(cis)), sum(sg.numel for _, _, sg in its))
+             for (code, cis), its in groups.items()]
     sbytes = max(int(L.flame_update_stats_scratch_bytes(p.n_chunks, p.n_clients)) for _, _, p, _ in plans)
     scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
     for code, cis, p, elems in plans:
-        dm = _staging.upload(p.meta, device)
-        segp, clp, _, _ = _device_ptrs(dm, p)
-        nbytes = elems * ITEMSIZE[code] * len(cis)
-        with _timed("flame_update_stats", device, nbytes):
-            N.check(L.flame_update_stats(code, segp, p.n_segs, p.n_chunks, clp, p.n_clients,
-                                         out.data_ptr() + 8 * slots[cis], out.data_ptr() + 8 * (total + slots[cis]),
-                                         scratch.data_ptr(), sbytes, _stream_ptr(device)))
-        keep.append(dm)
+        _launch("flame_update_stats", elems * ITEMSIZE[code] * len(cis), device, keep, p.meta,
+                lambda b: L.flame_update_stats(code, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+                                               out.data_ptr() + 8 * slots[cis],
+                                               out.data_ptr() + 8 * (total + slots[cis]), scratch.data_ptr(), sbytes,
+                                               _stream_ptr(device)))
     keep.append(scratch)
     _keepalive(keep, device)
     host = out.cpu().numpy()                    # the one D2H; waits for the launches above
@@ -1258,10 +1278,7 @@ def _accumulate_slab(agg: dict, entries, device, key_groups=None, after_group=No
     targets = {k: _Target(agg[k], device) for k in agg.keys()}
     keep = []
     for gi, g in enumerate(key_groups if key_groups is not None else [list(agg.keys())]):
-        groups = collections.OrderedDict()
-        for k in g:
-            groups.setdefault(dtype_code(agg[k].dtype), []).append(k)
-        for code, ks in groups.items():
+        for code, ks in by_dtype(g, lambda k: agg[k].dtype).items():
             segs = []
             for k in ks:
                 ptrs, tile_bytes = rows[k]

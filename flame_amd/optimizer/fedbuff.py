@@ -319,25 +319,19 @@ def _fused_scale_add(base_weights, agg, agg_goal, delta, key_groups=None, after_
     if keys != agg._keys:
         return False
     device = engine.pick_device(base_weights, *[w for w, _ in agg._pending])
-    codes = {}
     for k in keys:
         t = base_weights[k]
         shape, dt = agg._meta[k]
-        code = engine.DTYPE_CODE.get(dt)
-        if (code not in (engine.N.FLAME_F32, engine.N.FLAME_BF16, engine.N.FLAME_F16) or t.dtype != dt
-                or t.device != device or not t.is_contiguous() or t.numel() != math.prod(shape)
+        if (engine.DTYPE_CODE.get(dt) not in (engine.N.FLAME_F32, engine.N.FLAME_BF16, engine.N.FLAME_F16)
+                or t.dtype != dt or t.device != device or not t.is_contiguous() or t.numel() != math.prod(shape)
                 or (delta is not None and (delta[k].device != device or not delta[k].is_contiguous()))):
             return False
-        codes[k] = code
     rows, keep = _hier_rows([agg], keys, device)
     if rows is None:
         return False
     rates = [[r for _, r in agg._pending]]
     for gi, gkeys in enumerate(key_groups if key_groups is not None else [keys]):
-        groups = collections.OrderedDict()
-        for k in gkeys:
-            groups.setdefault(codes[k], []).append(k)
-        for code, ks in groups.items():
+        for code, ks in engine.by_dtype(gkeys, lambda k: agg._meta[k][1]).items():
             segs = [engine.HierSeg(numel=base_weights[k].numel(), mid_w=[base_weights[k].data_ptr()],
                                    clients=rows[k][0], mid_delta=[delta[k].data_ptr()] if delta is not None else None,
                                    tile_stride=rows[k][1]) for k in ks]
@@ -488,15 +482,9 @@ def _hier_rows(aggs, keys, device):
     for k in keys:
         shape, dt = aggs[0]._meta[k]
         ref = torch.empty(shape, dtype=dt, device="meta")   # numel / dtype of the aggregate
-        ptrs, stride = [], None
-        for a in aggs:
-            row, ts = engine._client_row([w[k] for w, _ in a._pending], ref, device, keep)
-            if stride is None:
-                stride = ts
-            elif ts != stride:
-                return None, keep
-            ptrs.extend(row)
-        rows[k] = (np.asarray(ptrs, dtype=np.uint64), stride)
+        rows[k] = engine._middle_rows([[w[k] for w, _ in a._pending] for a in aggs], ref, device, keep)
+        if rows[k] is None:
+            return None, keep
     return rows, keep
 
 
@@ -601,10 +589,7 @@ def hierarchy_round(middles, top_agg=None, *, version: int, top_weights=None, to
     mid_rates = [[r for _, r in a._pending] for a in aggs]
     mid_goals = [g for _, _, g, _ in middles]
     for gi, g in enumerate(key_groups if key_groups is not None else [keys]):
-        groups = collections.OrderedDict()
-        for k in g:
-            groups.setdefault(engine.dtype_code(aggs[0]._meta[k][1]), []).append(k)
-        for code, ks in groups.items():
+        for code, ks in engine.by_dtype(g, lambda k: aggs[0]._meta[k][1]).items():
             segs = []
             for k in ks:
                 ptrs, stride = rows[k]

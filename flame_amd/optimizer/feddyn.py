@@ -224,7 +224,7 @@ class FedDyn(FedAvg):
             if rest:
                 self._reference_round(rest, arrivals, had, rate, device, new_hist, cld)
             if fused:
-                self._fused_round_pp(fused, arrivals, had, rate, device, cld)
+                self._fused_round(fused, arrivals, had, rate, device, new_hist, cld, pp=self._pp)
             if rest:
                 self._pp_absorb(rest, arrivals, had, new_hist)
         else:
@@ -301,85 +301,62 @@ class FedDyn(FedAvg):
                 pp.write(e, k, h)
                 del src[k]
 
-    def _fused_round_pp(self, keys, arrivals, had, rate, device, cld):
-        pp = self._pp
-        steps, n_phase1 = engine.feddyn_program([e for e, _ in arrivals], list(self.local_param_dict), had)
-        pp.ensure([e for _, e in steps])
-        flags = [f for f, _ in steps]
-        rate_mean = 1 / len(self.local_param_dict)
-        wmap = dict(arrivals)
-        w_ends = [e for f, e in steps if f & N.FLAME_DYN_W]
-        targets = {k: engine._Target(self.agg_weights[k], device) for k in keys}
-        groups = collections.OrderedDict()
-        for k in keys:
-            groups.setdefault(engine.dtype_code(self.agg_weights[k].dtype), []).append(k)
-        keep = []
-        for code, ks in groups.items():
-            segs = []
-            for k in ks:
-                t = targets[k].dev
-                row, tile_stride = engine._client_row([wmap[e][k] for e in w_ends], t, device, keep)
-                wptr = dict(zip(w_ends, row))
-                c = torch.empty_like(t)
-                cld[k] = c
-                written = set()
-                ptrs = []
-                for f, e in steps:
-                    # h is read from the store holding the end's history (the one just written,
-                    # if a phase-1 step of this program wrote it); h' goes to the other store
-                    src = pp.cur[e] ^ (1 if e in written else 0)
-                    ptrs.append((wptr[e] if f & N.FLAME_DYN_W else 0,
-                                 pp.ptr(src, k, e) if f & N.FLAME_DYN_HIN else 0,
-                                 pp.ptr(pp.cur[e] ^ 1, k, e) if f & N.FLAME_DYN_HOUT else 0))
-                    if f & N.FLAME_DYN_HOUT:
-                        written.add(e)
-                segs.append(engine.DynSeg(t.numel(), out=t.data_ptr(), inp=t.data_ptr(), cld=c.data_ptr(),
-                                          steps=ptrs, tile_stride=tile_stride, hist_tile_stride=pp.tile_stride(k)))
-            engine.feddyn_round_(code, segs, flags, n_phase1, rate, rate_mean, device, keep)
-        for f, e in steps:
-            if f & N.FLAME_DYN_HOUT:
-                pp.cur[e] ^= 1
-        engine._keepalive(keep, device)
-        for k, t in targets.items():
-            t.writeback()
-            a = self.agg_weights[k]
-            if a.device != device:
-                cld[k] = cld[k].to(a.device)
-            cld[k] = cld[k].view(a.shape)
-
     # ------------------------------------------------------------------ one launch per dtype
-    def _fused_round(self, keys, arrivals, had, rate, device, new_hist, cld):
+    def _fused_round(self, keys, arrivals, had, rate, device, new_hist, cld, pp=None):
+        """One flame_feddyn_round launch per dtype.  A step's history pointers come from the ends'
+        own tensors (read and written in place; ``new_hist`` receives a new end's first history), or
+        with ``pp`` from the ping-pong stores: read from the store holding the end's history,
+        written to the other one, which becomes the current one once the launches are queued."""
         steps, n_phase1 = engine.feddyn_program([e for e, _ in arrivals], list(self.local_param_dict), had)
+        if pp is not None:
+            pp.ensure([e for _, e in steps])
         flags = [f for f, _ in steps]
         rate_mean = 1 / len(self.local_param_dict)
         wmap = dict(arrivals)
         w_ends = [e for f, e in steps if f & N.FLAME_DYN_W]
         targets = {k: engine._Target(self.agg_weights[k], device) for k in keys}
-        groups = collections.OrderedDict()
-        for k in keys:
-            groups.setdefault(engine.dtype_code(self.agg_weights[k].dtype), []).append(k)
+
+        def own(k, t):
+            hbuf = {}
+            for f, e in steps:
+                if e in had:
+                    hbuf[e] = self.local_param_dict[e][k]
+                elif e not in hbuf:   # first history of this end: the kernel writes w into it
+                    hbuf[e] = new_hist[e][k] = torch.empty(engine.logical_shape(wmap[e], k), dtype=t.dtype,
+                                                           device=device)
+            return [(hbuf[e].data_ptr(), hbuf[e].data_ptr()) for _, e in steps], 0
+
+        def stored(k, t):
+            written, out = set(), []
+            for f, e in steps:
+                # h is read from the store holding the end's history (the one just written,
+                # if a phase-1 step of this program wrote it); h' goes to the other store
+                src = pp.cur[e] ^ (1 if e in written else 0)
+                out.append((pp.ptr(src, k, e) if f & N.FLAME_DYN_HIN else 0,
+                            pp.ptr(pp.cur[e] ^ 1, k, e) if f & N.FLAME_DYN_HOUT else 0))
+                if f & N.FLAME_DYN_HOUT:
+                    written.add(e)
+            return out, pp.tile_stride(k)
+
         keep = []
-        for code, ks in groups.items():
+        for code, ks in engine.by_dtype(keys, lambda k: self.agg_weights[k].dtype).items():
             segs = []
             for k in ks:
                 t = targets[k].dev
-                hbuf = {}
-                for f, e in steps:
-                    if e in had:
-                        hbuf[e] = self.local_param_dict[e][k]
-                    elif e not in hbuf:   # first history of this end: the kernel writes w into it
-                        hbuf[e] = new_hist[e][k] = torch.empty(engine.logical_shape(wmap[e], k), dtype=t.dtype,
-                                                               device=device)
+                hist, hist_stride = (own if pp is None else stored)(k, t)
                 row, tile_stride = engine._client_row([wmap[e][k] for e in w_ends], t, device, keep)
                 wptr = dict(zip(w_ends, row))
                 c = torch.empty_like(t)
                 cld[k] = c
-                ptrs = [(wptr[e] if f & N.FLAME_DYN_W else 0,
-                         hbuf[e].data_ptr() if f & N.FLAME_DYN_HIN else 0,
-                         hbuf[e].data_ptr() if f & N.FLAME_DYN_HOUT else 0) for f, e in steps]
+                ptrs = [(wptr[e] if f & N.FLAME_DYN_W else 0, h_in if f & N.FLAME_DYN_HIN else 0,
+                         h_out if f & N.FLAME_DYN_HOUT else 0) for (f, e), (h_in, h_out) in zip(steps, hist)]
                 segs.append(engine.DynSeg(t.numel(), out=t.data_ptr(), inp=t.data_ptr(), cld=c.data_ptr(),
-                                          steps=ptrs, tile_stride=tile_stride))
+                                          steps=ptrs, tile_stride=tile_stride, hist_tile_stride=hist_stride))
             engine.feddyn_round_(code, segs, flags, n_phase1, rate, rate_mean, device, keep)
+        if pp is not None:
+            for f, e in steps:
+                if f & N.FLAME_DYN_HOUT:
+                    pp.cur[e] ^= 1
         engine._keepalive(keep, device)
         for k, t in targets.items():
             t.writeback()

@@ -127,26 +127,15 @@ def _fused(keys, mids, entries, top_weights, top_rates, device, deltas, update_m
     """``fast``: slab pointer rows of every key (engine.slab_rows) or None (per-view rows)."""
     keep = []
     mid_rates = [[r for _, r in e] for e in entries]
-    groups = collections.OrderedDict()
-    for k in keys:
-        groups.setdefault(engine.dtype_code(top_weights[k].dtype), []).append(k)
-    for code, ks in groups.items():
+    for code, ks in engine.by_dtype(keys, lambda k: top_weights[k].dtype).items():
         segs = []
         for k in ks:
             t = top_weights[k]
-            ptrs, stride = [], None
-            ok = True
-            for e in (entries if fast is None else ()):
-                row, ts = engine._client_row([w[k] for w, _ in e], t, device, keep)
-                if stride is None:
-                    stride = ts
-                elif ts != stride:     # mixed tiled / contiguous middles: contiguous copies
-                    ok = False
-                    break
-                ptrs.extend(row)
-            if fast is not None:
-                ptrs, stride = fast[k]
-            elif not ok:
+            rows = fast[k] if fast is not None else engine._middle_rows([[w[k] for w, _ in e] for e in entries], t,
+                                                                        device, keep)
+            if rows is not None:
+                ptrs, stride = rows
+            else:                      # mixed tiled / contiguous middles: contiguous copies
                 ptrs, stride = [], 0
                 for e in entries:
                     for w, _ in e:
