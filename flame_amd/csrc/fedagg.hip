@@ -744,6 +744,240 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_scaled_kernel(const flame_s
         store_chunk(op, ov);
 }
 
+// ---------------------------------------------------------------- trimmed mean / median
+// Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
+// the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
+// in fp64 and divided (DESIGN.md §2 is the contract).  The order is -inf < .. < -0 < +0 < .. < +inf
+// < NaN, taken on monotone integer keys -- never a floating-point min / max, whose minNum drops a
+// NaN and duplicates its partner.  Selection streams over the clients in cache order: `lo` holds
+// the k smallest keys seen so far, `hi` the k largest of what left `lo`; what leaves `hi` is kept.
+// Both are sorted chains in registers, indexed only by unrolled constants.  A chain of capacity KT
+// serves any k <= KT without a branch: stages j >= k start as pass-throughs (lo[j] the smallest
+// key: min keeps it, max hands the arrival on unchanged; hi[j] the largest), stages j < k start
+// full of the opposite extreme, so every stage is one integer min and one max per value.  (A
+// wave-uniform `if (j < k)` per stage was built first: the merge behind each branch cost a third
+// VALU op, a v_mov, per stage and value, and four more instructions per stage -- DESIGN.md §4.)  The
+// client loop is peeled into its three phases (arrivals < k fill lo, arrivals < 2k fill hi, the
+// rest emit), so the extremes the chains start with only ever fall out while nothing is kept: no
+// sentinel is told apart from data.  The host picks the smallest instantiated KT >= k.
+constexpr int kTrimMaxK = 16;
+template <int V> using ic_ = std::integral_constant<int, V>;    // a phase as a compile-time argument
+#ifndef FLAME_T_TRIM_UNROLL
+#define FLAME_T_TRIM_UNROLL 8
+#endif
+#ifndef FLAME_T_TRIM_UNROLL_DEEP
+#define FLAME_T_TRIM_UNROLL_DEEP 4
+#endif
+// client loads in flight per lane: fewer for the deep chains, which are VALU-bound
+template <int KT> constexpr int trim_unroll() { return KT >= 8 ? FLAME_T_TRIM_UNROLL_DEEP : FLAME_T_TRIM_UNROLL; }
+
+// Key traits.  R: one register's worth of keys (two 16-bit keys packed for bf16 / f16), NR of them
+// per 16-byte lane vector.  keys(): the lane vector as keys, every NaN the all-ones key.
+// add(): the keys decoded, widened to fp64 (exact) and added to the lane's accumulators; the
+// all-ones key decodes to the quiet NaN 0x7f..f by the same inverse map as every other key.
+template <int DT> struct TrimK;
+template <> struct TrimK<FLAME_F32> {
+    using R = uint32_t; static constexpr int NR = 4;
+    __device__ static R lowest() { return 0u; }
+    __device__ static R highest() { return ~0u; }
+    __device__ static R kmin(R a, R b) { return a < b ? a : b; }
+    __device__ static R kmax(R a, R b) { return a < b ? b : a; }
+    __device__ static void keys(const V16& v, R (&k)[NR]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const uint32_t u = v.w[i];
+            const uint32_t m = static_cast<uint32_t>(static_cast<int32_t>(u) >> 31) | 0x80000000u;
+            k[i] = (u & 0x7FFFFFFFu) > 0x7F800000u ? ~0u : (u ^ m);
+        }
+    }
+    __device__ static void add(const R (&k)[NR], double (&acc)[4]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const uint32_t m = ~static_cast<uint32_t>(static_cast<int32_t>(k[i]) >> 31) | 0x80000000u;
+            acc[i] = __dadd_rn(acc[i], static_cast<double>(__uint_as_float(k[i] ^ m)));
+        }
+    }
+};
+template <> struct TrimK<FLAME_F64> {
+    using R = uint64_t; static constexpr int NR = 2;
+    __device__ static R lowest() { return 0ull; }
+    __device__ static R highest() { return ~0ull; }
+    __device__ static R kmin(R a, R b) { return a < b ? a : b; }
+    __device__ static R kmax(R a, R b) { return a < b ? b : a; }
+    __device__ static void keys(const V16& v, R (&k)[NR]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const uint64_t u = static_cast<uint64_t>(v.w[2 * i]) | (static_cast<uint64_t>(v.w[2 * i + 1]) << 32);
+            const uint64_t m = static_cast<uint64_t>(static_cast<int64_t>(u) >> 63) | 0x8000000000000000ull;
+            k[i] = (u & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull ? ~0ull : (u ^ m);
+        }
+    }
+    __device__ static void add(const R (&k)[NR], double (&acc)[2]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const uint64_t m = ~static_cast<uint64_t>(static_cast<int64_t>(k[i]) >> 63) | 0x8000000000000000ull;
+            acc[i] = __dadd_rn(acc[i], __longlong_as_double(static_cast<long long>(k[i] ^ m)));
+        }
+    }
+};
+// bf16 / f16: the same map on 16 bits, two keys per register (v_pk_min_u16 / v_pk_max_u16)
+using ss2 = __attribute__((ext_vector_type(2))) short;
+template <int DT> struct TrimK16 {
+    using R = us2; static constexpr int NR = 4;
+    static constexpr unsigned short kInf = DT == FLAME_BF16 ? 0x7F80 : 0x7C00;
+    __device__ static R lowest() { return us2{0, 0}; }
+    __device__ static R highest() { return us2{0xFFFF, 0xFFFF}; }
+    __device__ static R kmin(R a, R b) { return __builtin_elementwise_min(a, b); }
+    __device__ static R kmax(R a, R b) { return __builtin_elementwise_max(a, b); }
+    __device__ static void keys(const V16& v, R (&k)[NR]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const us2 u = __builtin_bit_cast(us2, v.w[i]);
+            const us2 m = __builtin_bit_cast(us2, __builtin_bit_cast(ss2, u) >> 15) | us2{0x8000, 0x8000};
+            const us2 a = u & us2{0x7FFF, 0x7FFF};
+            // a > inf <=> min(a, inf + 1) - min(a, inf) == 1; 0 - that is the all-ones mask of a NaN
+            const us2 nan = us2{0, 0} - (__builtin_elementwise_min(a, us2{kInf + 1, kInf + 1}) -
+                                         __builtin_elementwise_min(a, us2{kInf, kInf}));
+            k[i] = (u ^ m) | nan;
+        }
+    }
+    __device__ static void add(const R (&k)[NR], double (&acc)[8]) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const us2 m = ~__builtin_bit_cast(us2, __builtin_bit_cast(ss2, k[i]) >> 15) | us2{0x8000, 0x8000};
+            const us2 h = k[i] ^ m;
+            acc[2 * i] = __dadd_rn(acc[2 * i], static_cast<double>(Tr<DT>::ld(h.x)));
+            acc[2 * i + 1] = __dadd_rn(acc[2 * i + 1], static_cast<double>(Tr<DT>::ld(h.y)));
+        }
+    }
+};
+template <> struct TrimK<FLAME_BF16> : TrimK16<FLAME_BF16> {};
+template <> struct TrimK<FLAME_F16> : TrimK16<FLAME_F16> {};
+
+// mean64 rounded to the dtype: f64 keeps it, f32 one RNE step, bf16 / f16 two (fp64 -> fp32 -> 16 bit)
+template <int DT> __device__ __forceinline__ typename Tr<DT>::A trim_round(double m) {
+    if constexpr (DT == FLAME_F64) return m;
+    else if constexpr (DT == FLAME_F32) return __double2float_rn(m);
+    else if constexpr (DT == FLAME_BF16) return bf16_round(__double2float_rn(m));
+    else return f16_round(__double2float_rn(m));
+}
+
+// Clients [0, n) of one lane vector through the chains; acc takes the n - 2k kept values in the
+// order they emerge.  VEC as in reduce_clients.
+template <int DT, int KT, int CU, bool VEC>
+__device__ __forceinline__ void trimmed_clients(double (&acc)[Tr<DT>::EPT], const uint64_t* __restrict__ cp, int n, int k,
+                                                int64_t e0, int64_t numel, int64_t coff) {
+    using X = Tr<DT>;
+    using T = typename X::T;
+    using K = TrimK<DT>;
+    using R = typename K::R;
+    constexpr int EPT = X::EPT, NR = K::NR;
+    R lo[KT][NR], hi[KT][NR];
+#pragma unroll
+    for (int j = 0; j < KT; ++j)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            lo[j][r] = j < k ? K::highest() : K::lowest();
+            hi[j][r] = j < k ? K::lowest() : K::highest();
+        }
+    auto load_client = [&](int c) -> V16 {
+        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
+        if constexpr (VEC) {
+            return ld_nt(p);
+        } else {
+            T x[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
+            return pack<T, EPT>(x);
+        }
+    };
+    // PHASE 0: into lo; 1: what leaves lo into hi; 2: what leaves hi is kept
+    auto arrive = [&](auto phase, const V16& v) {
+        constexpr int PHASE = decltype(phase)::value;
+        R x[NR];
+        K::keys(v, x);
+#pragma unroll
+        for (int j = 0; j < KT; ++j)
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const R a = lo[j][r];
+                lo[j][r] = K::kmin(a, x[r]);
+                x[r] = K::kmax(a, x[r]);
+            }
+        if constexpr (PHASE >= 1) {
+#pragma unroll
+            for (int j = 0; j < KT; ++j)
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const R a = hi[j][r];
+                    hi[j][r] = K::kmax(a, x[r]);
+                    x[r] = K::kmin(a, x[r]);
+                }
+        }
+        if constexpr (PHASE == 2) K::add(x, acc);
+    };
+    auto run = [&](auto phase, int i, int end) {
+        for (; i + CU <= end; i += CU) {
+            V16 v[CU];
+#pragma unroll
+            for (int u = 0; u < CU; ++u) v[u] = load_client(i + u);
+#pragma unroll
+            for (int u = 0; u < CU; ++u) arrive(phase, v[u]);
+        }
+        for (; i < end; ++i) arrive(phase, load_client(i));
+    };
+    run(ic_<0>{}, 0, k);
+    run(ic_<1>{}, k, 2 * k);
+    run(ic_<2>{}, 2 * k, n);
+}
+
+template <int DT, int KT>
+__global__ __launch_bounds__(kBlock) void agg_trimmed_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                             const uint64_t* __restrict__ clients, int n_clients,
+                                                             int trim_k, unsigned flags, int64_t n_chunks) {
+    using X = Tr<DT>;
+    using T = typename X::T;
+    using A = typename X::A;
+    constexpr int EPT = X::EPT;
+    static_assert(kVPT == 1, "agg_trimmed_kernel: one lane vector per chunk");
+    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const int64_t coff = client_offset<DT>(sg, chunk);
+    const bool init_first = (flags & FLAME_AGG_INIT_FIRST) != 0;
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const double kept = static_cast<double>(n_clients - 2 * trim_k);
+    const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
+    T* op = reinterpret_cast<T*>(sg.out) + e0;
+    double acc[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) acc[j] = 0.0;
+    // out = base + mean, one add in the dtype (torch-CPU's `base += mean`); INIT_FIRST: the mean
+    auto result = [&](double a, T b) -> T {
+        const A mean = trim_round<DT>(a / kept);
+        return X::st(init_first ? mean : X::add(X::ld(b), mean));
+    };
+    if (vec) {
+        trimmed_clients<DT, KT, trim_unroll<KT>(), true>(acc, cp, n_clients, trim_k, e0, sg.numel, coff);
+        T b[EPT], o[EPT];
+        if (!init_first) unpack<T, EPT>(ld_v(bp), b);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
+        V16 ov[kVPT];
+        ov[0] = pack<T, EPT>(o);
+        store_chunk(op, ov);
+        return;
+    }
+    trimmed_clients<DT, KT, 1, false>(acc, cp, n_clients, trim_k, e0, sg.numel, coff);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
+}
+
 // ---------------------------------------------------------------- update statistics (update guard)
 // Per client: the sum of squares of its finite elements and the count of its non-finite ones, over
 // every segment (differential_privacy.py:68-76 is the norm this feeds).  The only kernel that
@@ -2993,6 +3227,42 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment* segs
                            scales64, flags, n_chunks);
     });
     if (!known) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    return check_launch(who);
+}
+
+// The trimmed mean stands outside the launch-branch table too: the chain capacity follows from
+// trim_k alone (the smallest instantiated KT >= trim_k), nothing else is picked.
+int flame_agg_trimmed_max_k(void) { return kTrimMaxK; }
+
+int flame_agg_trimmed(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                      const void* const* clients, int32_t n_clients, int32_t trim_k, void* stream) {
+    const char* const who = "flame_agg_trimmed";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (trim_k < 0 || trim_k > kTrimMaxK)
+        return set_err(trim_k < 0 ? FLAME_EINVAL : FLAME_ENOTSUP, "%s: trim_k %d outside [0, %d] (flame_agg_trimmed_max_k)", who,
+                       trim_k, kTrimMaxK);
+    if (n_clients <= 2 * trim_k)
+        return set_err(FLAME_EINVAL, "%s: n_clients %d must exceed 2 * trim_k = %d", who, n_clients, 2 * trim_k);
+    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = check_flags(who, flags, FLAME_AGG_INIT_FIRST | FLAME_AGG_XCD_MAP)) return rc;
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    constexpr int kCaps[] = {1, 2, 3, 4, 6, 8, 12, 16};      // a round pays for KT stages, not for trim_k
+    static_assert(kCaps[7] == kTrimMaxK, "the capacities end at kTrimMaxK");
+    int kt = kTrimMaxK;
+    for (int i = 7; i >= 0; --i)
+        if (kCaps[i] >= trim_k) kt = kCaps[i];
+    dispatch<1, 2, 3, 4, 6, 8, 12, 16>(kt, [&](auto cap) {
+        dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+            hipLaunchKernelGGL((agg_trimmed_kernel<decltype(dt)::value, decltype(cap)::value>),
+                               dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0, st, segs, n_segs,
+                               reinterpret_cast<const uint64_t*>(clients), n_clients, trim_k, flags, n_chunks);
+        });
+    });
     return check_launch(who);
 }
 

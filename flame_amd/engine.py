@@ -4,7 +4,8 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``synth_fill_``) need the native library and a HIP device.
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``synth_fill_``) need the native library and a
+HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
 segments, a metadata block from one of the plan functions (all built on ``_Block``), then
@@ -1188,6 +1189,84 @@ def update_stats(weights_list, device=None):
         sumsq[idx] += sq[o:o + len(cis)]
         nonfinite[idx] += nf[o:o + len(cis)]
     return sumsq, nonfinite
+
+
+def trimmed_max_k() -> int:
+    """The largest trim count the kernels carry (flame_agg_trimmed_max_k)."""
+    return int(N.lib().flame_agg_trimmed_max_k())
+
+
+def trimmed_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, device=None) -> None:
+    """agg[key] += the coordinate-wise ``k``-trimmed mean of the updates, in place (kernel:
+    flame_agg_trimmed; Yin et al., ICML 2018 -- flame has no counterpart).  Per element the ``k``
+    smallest and ``k`` largest of the ``n`` values are dropped (NaN sorts last, as ``torch.sort``
+    places it), the rest are summed in fp64 in their streaming order and divided by ``n - 2k``;
+    ``k = (n - 1) // 2`` is the median, ``k = 0`` the unweighted mean.  With ``init_first`` the
+    mean itself is written and the aggregate is not read.  DESIGN.md §2 states the contract.
+
+    Float keys (f32 / bf16 / f16 / f64) are grouped by dtype, one launch each; every update must
+    carry exactly the aggregate's float keys in the aggregate's dtypes (ValueError otherwise).
+    Integer / bool / narrow keys (``num_batches_tracked``, masks) are not trimmed: they take the
+    existing statement with equal weights, ``accumulate`` with rate ``1 / n`` -- no robustness is
+    claimed for counters.  Counts play no part: a weighted trimmed mean would let a liar choose
+    its own weight.  The updates are only read."""
+    ws = list(weights_list)
+    n = len(ws)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"trimmed_mean: k must be an int, not {type(k).__name__}")
+    k = int(k)
+    if k < 0 or n <= 2 * k:
+        raise ValueError(f"trimmed_mean: need 0 <= k and n > 2k, got k = {k} with {n} update(s)")
+    if k > trimmed_max_k():
+        raise NotImplementedError(f"trimmed_mean: k = {k} exceeds the kernels' chain capacity {trimmed_max_k()}")
+    fkeys = [key for key, t in agg.items() if t.is_floating_point()]
+    others = [key for key in agg if key not in fkeys]
+    want = {key: agg[key].dtype for key in fkeys}
+    for w in representatives(ws):
+        have = {key: weight_dtype(w, key) for key in w.keys()}
+        if {key for key, dt in have.items() if dt.is_floating_point} != set(fkeys) or \
+                any(have[key] != dt for key, dt in want.items()):
+            raise ValueError("trimmed_mean: every update must carry the aggregate's float keys in the aggregate's dtypes")
+    if init_first and others:
+        raise ValueError(f"trimmed_mean: init_first covers float keys only; {others!r} need a base")
+    if device is not None:
+        device = torch.device(device)
+    else:
+        device = next((t.device for t in agg.values() if isinstance(t, torch.Tensor) and t.is_cuda), None) \
+            or pick_device(*ws)
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.trimmed_mean: needs a HIP device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if fkeys:
+        for key in fkeys:
+            dtype_code(want[key])               # an unsupported float dtype raises
+        targets = {key: _Target(agg[key], device) for key in fkeys}
+        numels = {key: agg[key].numel() for key in fkeys}
+        rows = slab_rows(ws, fkeys, numels, want, device) if getattr(ws[0], "slab", None) is not None else None
+        keep = []
+        L = N.lib()
+        for code, ks in by_dtype(fkeys, lambda key: want[key]).items():
+            segs = []
+            for key in ks:
+                o = targets[key].dev
+                row, tstride = rows[key] if rows is not None else _client_row([w[key] for w in ws], o, device, keep)
+                segs.append(Seg(o.numel(), out=o.data_ptr(), inp=0 if init_first else o.data_ptr(), clients=row,
+                                tile_stride=tstride))
+            p = plan(code, segs, [0.0] * n)     # the kernel reads no rates: today's block, as update_stats builds it
+            flags = N.FLAME_AGG_INIT_FIRST if init_first else 0
+            if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs):
+                flags |= N.FLAME_AGG_XCD_MAP
+            nbytes = sum(s.numel for s in segs) * ITEMSIZE[code] * (n + (1 if init_first else 2))
+            _launch("flame_agg_trimmed", nbytes, device, keep, p.meta,
+                    lambda b: L.flame_agg_trimmed(code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+                                                  k, _stream_ptr(device)))
+        _keepalive(keep, device)
+        for t in targets.values():
+            t.writeback()
+    if others:
+        accumulate({key: agg[key] for key in others},
+                   [({key: w[key] for key in others if key in w}, 1.0 / n) for w in ws], device=device)
 
 
 def weight_dtype(weights, k) -> torch.dtype:

@@ -8,9 +8,10 @@ from .feddyn import FedDyn
 from .fedgft import FedGFT
 from .fedopt import FedOPT
 from .fedprox import FedProx
+from .fedtrimmed import FedMedian, FedTrimmedMean
 from .fedyogi import FedYogi
 from .scaffold import Scaffold
 from .train_result import TrainResult
 
 __all__ = ["AbstractOptimizer", "FedAvg", "FedOPT", "FedAdam", "FedYogi", "FedAdaGrad", "FedBuff",
-           "FedProx", "FedDyn", "FedGFT", "Scaffold", "TrainResult"]
+           "FedProx", "FedDyn", "FedGFT", "Scaffold", "TrainResult", "FedTrimmedMean", "FedMedian"]

@@ -8,8 +8,9 @@ class FedAdam(FedOPT):
     variant = "fedadam"
 
     def __init__(self, beta_1=0.9, beta_2=0.99, eta=1e-2, tau=1e-3, defer: bool = False, *,
-                 clip_threshold=None, nonfinite: str = "keep"):
-        super().__init__(beta_1, beta_2, eta, tau, defer=defer, clip_threshold=clip_threshold, nonfinite=nonfinite)
+                 clip_threshold=None, nonfinite: str = "keep", trim=None):
+        super().__init__(beta_1, beta_2, eta, tau, defer=defer, clip_threshold=clip_threshold, nonfinite=nonfinite,
+                         trim=trim)
 
     def _delta_v_tensor(self, v, d):
         return self.beta_2 * v + (1 - self.beta_2) * d**2

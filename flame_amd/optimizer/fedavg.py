@@ -30,6 +30,13 @@ Server-side update guard (opt-in, ``FedAvg(clip_threshold=C, nonfinite="skip")``
 the ``nonfinite`` policy, forms the rates from the remaining ``total`` and reduces with the
 clip scales (``flame_agg_reduce_scaled``).  ``update_stats`` holds the round's records.
 With both kwargs at their defaults none of this runs.
+
+Trimmed mean / median (opt-in, ``FedAvg(trim=2)``, ``trim=0.1``, ``trim="median"``, see
+``flame_amd/optimizer/trim.py``): ``do()`` replaces the weighted average of the float keys by the
+coordinate-wise trimmed mean of the popped updates (``engine.trimmed_mean``, kernel
+``flame_agg_trimmed``), added onto ``base_weights`` in place.  The ``nonfinite`` policies run
+first.  ``trim`` with ``clip_threshold``, ``defer=True`` or the sharded wrapper is refused.  With
+``trim=None`` (the default) none of this runs.
 """
 import collections
 import collections.abc
@@ -41,6 +48,7 @@ import torch
 
 from .. import engine, metrics
 from . import guard
+from . import trim as trim_
 from .abstract import AbstractOptimizer
 from .fedbuff import _own_shm_views
 from .regularizer import Regularizer
@@ -126,7 +134,7 @@ class FedAvg(AbstractOptimizer):
     """FedAvg class."""
 
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
-                 clip_threshold=None, nonfinite: str = "keep"):
+                 clip_threshold=None, nonfinite: str = "keep", trim=None):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
@@ -134,6 +142,20 @@ class FedAvg(AbstractOptimizer):
         self.max_pending_bytes = max_pending_bytes
         self._deferred = None      # the DeferredWeights the last deferred do() returned
         self._init_guard(clip_threshold, nonfinite, defer)
+        self._init_trim(trim, defer)
+
+    def _init_trim(self, trim, defer):
+        self.trim = trim_.check_kwarg(trim)
+        self.trim_k = None         # the last trimmed do()'s k
+        if self.trim is None:
+            return
+        if self.clip_threshold is not None:
+            trim_.refuse(f"{type(self).__name__}(clip_threshold=...)", self.trim,
+                         "a clipped update would be trimmed on its scaled values, which needs the scale inside "
+                         "the selection kernel (a follow-up); use nonfinite= alone with trim")
+        if defer or getattr(self, "chain_defer", False):
+            trim_.refuse(f"{type(self).__name__}(defer=True)", self.trim,
+                         "a trimmed mean needs every update of the round at once; use defer=False")
 
     def _init_guard(self, clip_threshold, nonfinite, defer):
         self.clip_threshold, self.nonfinite = guard.check_kwargs(clip_threshold, nonfinite)
@@ -174,6 +196,30 @@ class FedAvg(AbstractOptimizer):
         scales = [records[i].scale for i in kept]
         return entries, (scales if any(s != 1.0 for s in scales) else None)
 
+    def _do_trimmed(self, base_weights, cache, total, kwargs):
+        """do() under ``trim``: base_weights += the coordinate-wise trimmed mean of the cached
+        updates.  A round that cannot be trimmed (``n <= 2k``, or ``k`` beyond the kernels'
+        capacity) raises before anything is popped.  Under a ``nonfinite`` policy the updates are
+        popped and measured first, as the guard does, and ``n`` is what remains."""
+        if "flame_amd_key_groups" in kwargs:
+            trim_.refuse("ShardedOptimizer", self.trim,
+                         "each rank would trim its own slices in waves; the selection kernel takes no key groups "
+                         "yet (a follow-up)")
+        max_k = engine.trimmed_max_k()
+        k = trim_.check_round(self.trim, len(cache), max_k)
+        if self.guarded:
+            entries, _ = self._pop_guarded(cache, total)
+            if not entries:            # every update skipped: as for an empty cache
+                return None
+            if len(entries) != len(self.update_stats):
+                k = trim_.check_round(self.trim, len(entries), max_k)
+        else:
+            entries = self._pop_entries(cache, total)
+        engine.trimmed_mean(base_weights, [w for w, _ in entries], k)
+        self.trim_k = k
+        trim_.save_metrics(self, k, len(entries))
+        return base_weights
+
     def do(self, base_weights, cache, *, total: int = 0, version: int = 0, **kwargs):
         """Aggregate the cached trainer updates into ``base_weights`` (in place)."""
         logger.debug("calling fedavg (flame_amd)")
@@ -191,6 +237,8 @@ class FedAvg(AbstractOptimizer):
         self.agg_weights = base_weights
         if len(cache) == 0 or total == 0:
             return None
+        if self.trim is not None:
+            return self._do_trimmed(base_weights, cache, total, kwargs)
         scales = None
         if self.guarded:
             entries, scales = self._pop_guarded(cache, total)

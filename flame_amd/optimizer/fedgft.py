@@ -139,8 +139,8 @@ except Exception:  # noqa: BLE001
 class FedGFT(FedAvg):
     """FedGFT class: FedAvg aggregation (HIP kernel) + server-side fairness bias."""
 
-    def __init__(self, fair, gamma, reg="l2", *, clip_threshold=None, nonfinite: str = "keep"):
-        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite)
+    def __init__(self, fair, gamma, reg="l2", *, clip_threshold=None, nonfinite: str = "keep", trim=None):
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim)
         self.fair = fair
         self.regularizer = FedGFTRegularizer(fair, gamma, reg)
         self.bias = Bias(fair=self.fair, local=False)

@@ -43,6 +43,7 @@ from collections import OrderedDict
 import torch
 
 from .. import elementwise as ew, engine, metrics
+from . import trim as trim_
 from .fedavg import FedAvg
 
 logger = logging.getLogger(__name__)
@@ -80,7 +81,10 @@ class FedOPT(FedAvg):
     max_chain_bytes = 16 << 30
 
     def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
-                 nonfinite: str = "keep"):
+                 nonfinite: str = "keep", trim=None):
+        trim_.refuse(type(self).__name__, trim_.check_kwarg(trim),
+                     "the fused FedOPT kernels form the weighted average themselves; a trimmed pseudo-gradient "
+                     "is a follow-up")
         self._poisoned = None
         self._chain = None
         self._current = None

@@ -40,7 +40,7 @@ except Exception:  # noqa: BLE001
 class FedProx(FedAvg):
     """FedProx class (server side = FedAvg)."""
 
-    def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep"):
-        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite)
+    def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None):
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim)
         self.mu = mu
         self.regularizer = FedProxRegularizer(self.mu)

@@ -604,6 +604,11 @@ class ShardedOptimizer:
                 "flame_amd ShardedOptimizer: the wrapped optimizer's clip_threshold / nonfinite (the server-side "
                 "update guard) are not supported under sharding: each rank sees only its slices, so the global "
                 "norm needs an all-reduce of the per-update sums of squares (a follow-up)")
+        if getattr(inner, "trim", None) is not None:
+            raise NotImplementedError(
+                "flame_amd ShardedOptimizer: the wrapped optimizer's trim (coordinate-wise trimmed-mean / median "
+                "aggregation) is not supported under sharding: the selection kernel takes no key groups yet "
+                "(a follow-up)")
         self.inner = inner
         # gather=False (FedAvg / FedProx): no all-gathers -- each rank's base_weights is current on its
         # owned ranges (and the replicated tails) only, one launch over them; for a caller whose next

@@ -33,6 +33,8 @@
  *                               per-update sums of squares and non-finite counts on the aggregator
  *   flame_agg_reduce_scaled     privacy/differential_privacy.py:79-82 (torch.mul(d_w, scale)) followed
  *                               by optimizer/fedavg.py:93-104, in one pass
+ *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
+ *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_synth_fill            (bench/test plumbing: counter-based synthetic updates)
  *   flame_hier_resident_per_cu  (no reference counterpart: occupancy query the parameter
  *                               shard uses to size its waves, flame_amd/shard.py)
@@ -211,6 +213,39 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment *segs
                             int64_t n_chunks, const void *const *clients, int32_t n_clients,
                             const float *rates32, const double *rates64, const float *scales32,
                             const double *scales64, void *stream);
+
+/*
+ * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,
+ * Ramchandran, Bartlett: "Byzantine-Robust Distributed Learning: Towards Optimal Statistical
+ * Rates", ICML 2018).  flame has no counterpart file: its optimizers only average.
+ *   segs, clients : the tables flame_agg_reduce takes (tensors, tiled UpdateSlab slots, misaligned
+ *                   views); no rates -- a weighted trimmed mean would let a liar choose its weight.
+ *   trim_k        : values dropped at EACH end per element; 0 <= trim_k <= flame_agg_trimmed_max_k()
+ *                   (16) and n_clients > 2 * trim_k.  trim_k = (n_clients - 1) / 2 is the median
+ *                   (one value kept for odd n_clients, the mean of two for even).
+ * Per element e, with x_i = v_i[e] in client order:
+ *   order   -inf < .. < -0 < +0 < .. < +inf < NaN (all NaNs equal and largest, as torch.sort
+ *           places them), compared on monotone integer keys, never by floating-point min / max;
+ *   select  streaming in client order: `lo` keeps the trim_k smallest values seen so far, `hi` the
+ *           trim_k largest of those that left `lo`; a value that leaves `hi` is kept.  The
+ *           n_clients - 2 * trim_k kept values are the multiset sorted(x)[trim_k : n - trim_k];
+ *   sum     each kept value widened to fp64 (exact for f32 / bf16 / f16) and added, one IEEE fp64 add
+ *           each, to an accumulator that starts at +0.0, in the order the values emerge -- a
+ *           function of the values and the client order only, never of the launch geometry;
+ *   mean    acc / double(n_clients - 2 * trim_k), one fp64 division, rounded to the dtype (f64: as
+ *           is; f32: one RNE step; bf16 / f16: two, fp64 -> fp32 -> 16 bit);
+ *   out[e] = round(in[e] + mean), one add in the dtype (torch-CPU's `base += mean`); with
+ *           FLAME_AGG_INIT_FIRST out[e] = mean and `in` is not read.
+ * Up to trim_k NaN / +inf / -inf values per element therefore vanish; more of them on one side
+ * propagate as IEEE arithmetic says.  trim_k = 0 is the unweighted mean accumulated in fp64.
+ * No floating-point atomics: equal launches give equal bits.  Float dtypes only (FLAME_ENOTSUP
+ * otherwise); flags FLAME_AGG_INIT_FIRST and FLAME_AGG_XCD_MAP (FLAME_AGG_SEG_RATES: FLAME_ENOTSUP);
+ * device tables only.  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_trimmed(int dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                      int64_t n_chunks, const void *const *clients, int32_t n_clients, int32_t trim_k,
+                      void *stream);
+int flame_agg_trimmed_max_k(void);
 
 /*
  * Fused FedAvg + FedOPT adaptive step (dtype FLAME_F32, FLAME_BF16 or FLAME_F16; base,
