@@ -265,6 +265,16 @@ def _compile(outs, targets, inputs=None):
     return prog, bufs
 
 
+def _gpu(device, what: str) -> torch.device:
+    """``device`` as a torch.device; a launch site refuses anything but a GPU before it allocates
+    or launches (a host pointer in a kernel's buffer table is a GPU memory fault, not an error)."""
+    device = device if isinstance(device, torch.device) else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"flame_amd.elementwise.{what}: tensors must live on the GPU, not on {device} "
+                           "(no CPU fallback)")
+    return device
+
+
 def materialize(*outs, device=None, into=None):
     """Run the statements that built ``outs`` as ONE flame_elementwise launch on ``device`` (the
     first CUDA leaf's by default) and return their values as new device tensors -- or, with
@@ -289,6 +299,7 @@ def materialize(*outs, device=None, into=None):
         device = next((lf.tensor.device for lf in leaves if lf.tensor.is_cuda), None)
         if device is None:
             device = engine.pick_device()
+    device = _gpu(device, "materialize")
     numel = 1
     for s in outs[0].shape:
         numel *= s
@@ -354,6 +365,7 @@ class Program:
 
     def __call__(self, *inputs, device):
         from . import engine
+        device = _gpu(device, "Program.__call__")
         if len(inputs) != self.n_in:
             raise TypeError(f"flame_amd elementwise: {len(inputs)} inputs for a program of {self.n_in}")
         shape = tuple(inputs[0].shape)
@@ -382,6 +394,7 @@ class Program:
         written)."""
         import numpy as np
         from . import engine
+        device = _gpu(device, "Program.run_many")
         if not rows:
             return []
         if len(rows) == 1 and into is None:

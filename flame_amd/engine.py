@@ -382,6 +382,19 @@ def _as_device(t: torch.Tensor, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def _staged(t: torch.Tensor, device) -> torch.Tensor:
+    """A contiguous device copy of ``t`` (``t`` itself when it already is one), never zero-copy:
+    for optimizer state a kernel writes in place (FedOPT's ``m_t`` / ``v_t``) or whose address
+    goes into a segment as it is (``current``, FedBuff's aggregate in :func:`scale_add_`).  The
+    zero-copy branch of :func:`_as_device` is for read-only client rows, whose host addresses
+    :func:`_client_row` translates."""
+    if t.device != device:
+        if t.device.type == "cpu":
+            shm_lease.check_live(t)
+        t = t.to(device, non_blocking=not shm_lease.aliases(t))
+    return t.contiguous()
+
+
 def tiled_stride(c: torch.Tensor, numel: int) -> int:
     """Bytes between chunks if ``c`` is a tiled slab view for a ``numel``-element
     aggregate (shape (ceil(numel/T), T), unit inner stride; see flame_amd/slab.py), else 0."""
@@ -747,7 +760,9 @@ def scale_add_(bases: List[torch.Tensor], aggs: List[torch.Tensor], goal: int,
         segs = []
         for s in idx:
             b = bases[s]
-            a = _as_device(aggs[s], device)
+            # staged, not zero-copy: a.data_ptr() goes into the segment as it is, and the aggregate
+            # is optimizer state (one H2D copy of a host-resident one), not a client row
+            a = _staged(aggs[s], device)
             if a.numel() != b.numel():
                 raise RuntimeError(f"flame_amd: scale_add of {a.numel()} elements into {b.numel()}")
             if a.dtype != b.dtype:

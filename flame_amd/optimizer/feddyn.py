@@ -206,6 +206,8 @@ class FedDyn(FedAvg):
         pp = self.history.startswith("pingpong")
         if pp and self._pp is None:
             self._init_pingpong(arrivals, device)
+        if pp:
+            self._pp_adopt(device)
         # keys some end's history of which left the stores (one pass over the ends, not one per key)
         moved = set()
         if pp:
@@ -268,6 +270,26 @@ class FedDyn(FedAvg):
                                                            device="meta")) for k in keys)
         self._pp = _PingPongHistories(template, device, max(len(self.local_param_dict), 1),
                                       tiled=self.history == "pingpong")
+
+    def _pp_adopt(self, device):
+        """A history that is a plain mapping (restored from a checkpoint, or assigned by the caller)
+        joins the stores: its template keys are written into the end's slot -- staged to the device
+        first -- and the end reads through a :class:`_StoredHistory` again.  Without this the fused
+        round would go on reading the stores' own (older or unset) bytes for that end.  A tensor
+        whose dtype or size does not fit the store stays in the end's ``rest`` (_pp_absorb)."""
+        pp = self._pp
+        for e, h in self.local_param_dict.items():
+            if h is None or isinstance(h, _StoredHistory):
+                continue
+            pp.ensure([e])
+            rest = {}
+            for k, t in h.items():
+                tm = pp.template.get(k)
+                if tm is not None and t.dtype == tm.dtype and t.numel() == tm.numel():
+                    pp.write(e, k, engine._staged(t, device))
+                else:
+                    rest[k] = t
+            self.local_param_dict[e] = _StoredHistory(pp, e, list(h.keys()), rest)
 
     def _fusable_pp(self, k, arrivals, moved) -> bool:
         a = self.agg_weights[k]

@@ -148,7 +148,9 @@ class FedOPT(FedAvg):
     @property
     def d_t(self):
         if self._d_t is None and self._prev_current is not None and self.agg_weights is not None:
-            self._d_t = {k: self.agg_weights[k] - self._prev_current[k] for k in self.agg_weights.keys()}
+            # (on the FedAvg result's device: with a host model, or state restored onto the host,
+            # the previous current lives elsewhere)
+            self._d_t = {k: a - self._prev_current[k].to(a.device) for k, a in self.agg_weights.items()}
         return self._d_t
 
     @d_t.setter
@@ -233,7 +235,7 @@ class FedOPT(FedAvg):
             sub = {k: base_weights[k] for k in generic}
             engine.accumulate(sub, [({k: w[k] for k in generic if k in w}, r) for w, r in entries], device=device,
                               **({} if scales is None else {"scales": scales}))
-            res = self._adapt_generic(generic, base_weights, current, state_zero)
+            res = self._adapt_generic(generic, base_weights, current, state_zero, device)
             if alloc is not None:
                 for k, v in res.items():
                     res[k] = alloc(k, v.dtype, v.shape).copy_(v)
@@ -260,7 +262,9 @@ class FedOPT(FedAvg):
         targets = [engine._Target(base_weights[k], device) for k in ks]
         alias = [_same_storage(current[k], base_weights[k]) for k in ks]
         # an aliased key's current is the FedAvg result itself: the kernel takes cur = avg
-        curs = [t.dev if a else engine._as_device(current[k], device) for t, a, k in zip(targets, alias, ks)]
+        # (state is staged, never zero-copy: the segment carries cur's address as it is, and the
+        # kernel writes m / v in place)
+        curs = [t.dev if a else engine._staged(current[k], device) for t, a, k in zip(targets, alias, ks)]
         outs = [alloc(k, base_weights[k].dtype, base_weights[k].shape) if alloc is not None else
                 torch.empty(base_weights[k].shape, dtype=base_weights[k].dtype, device=device) for k in ks]
         ms, vs = [], []
@@ -269,8 +273,8 @@ class FedOPT(FedAvg):
                 self.m_t[k] = torch.empty(base_weights[k].shape, dtype=base_weights[k].dtype, device=device)
                 self.v_t[k] = torch.empty(base_weights[k].shape, dtype=base_weights[k].dtype, device=device)
             else:
-                self.m_t[k] = engine._as_device(self.m_t[k], device)
-                self.v_t[k] = engine._as_device(self.v_t[k], device)
+                self.m_t[k] = engine._staged(self.m_t[k], device)
+                self.v_t[k] = engine._staged(self.v_t[k], device)
             ms.append(self.m_t[k])
             vs.append(self.v_t[k])
         avgs = [t.dev for t in targets]
@@ -422,12 +426,15 @@ class FedOPT(FedAvg):
                                "groups had been updated, so m_t / v_t / current_weights no longer agree; "
                                f"re-create the optimizer ({type(e).__name__}: {e})") from e
 
-    def _adapt_generic(self, keys, average, current, state_zero):
+    def _adapt_generic(self, keys, average, current, state_zero, device):
         """fedopt.py:106-129 for the keys the fused kernel does not take (int buffers such as
         num_batches_tracked and mixed-dtype keys): the reference's statements, the
         subclass's _delta_v_tensor included, recorded on elementwise.Lazy operands and run as
         ONE flame_elementwise launch per key -- torch's own dtype promotions, torch-CPU's
-        arithmetic per dtype (include/flame_amd.h), no PyTorch compute."""
+        arithmetic per dtype (include/flame_amd.h), no PyTorch compute.  Every program runs on
+        ``device``, the round's compute device (a host-resident average or state tensor is staged
+        there by the program); the new m_t / v_t / current are device tensors, as the fused
+        path's are."""
         out = {}
         programs = self.__dict__.setdefault("_ew_programs", {})
         hyper = (self.beta_1, self.beta_2, self.eta, self.tau)
@@ -436,13 +443,13 @@ class FedOPT(FedAvg):
             ins = [average[k], current[k]]
             if not (state_zero or k not in self.m_t or k not in self.v_t):
                 ins += [self.m_t[k], self.v_t[k]]
-            # one compiled program per dtype / 0-dim signature, one launch per program and device:
-            # a ResNet's BatchNorm num_batches_tracked keys all share one
+            # one compiled program per dtype / 0-dim signature, one launch per program: a ResNet's
+            # BatchNorm num_batches_tracked keys all share one
             sig = (hyper, tuple((t.dtype, t.dim() == 0) for t in ins))
             if sig not in programs:
                 programs[sig] = ew.trace(self._adapt_statement, [(t.dtype, tuple(t.shape)) for t in ins])
-            groups.setdefault((sig, average[k].device), []).append((k, ins))
-        for (sig, device), rows in groups.items():
+            groups.setdefault(sig, []).append((k, ins))
+        for sig, rows in groups.items():
             res = programs[sig].run_many([ins for _, ins in rows], device)
             for (k, _), (m, v, new) in zip(rows, res):
                 self.m_t[k], self.v_t[k], out[k] = m, v, new

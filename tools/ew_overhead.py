@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def torch_ops_generic(self, keys, average, current, state_zero):
+def torch_ops_generic(self, keys, average, current, state_zero, device=None):
     """Round 5's FedOPT._adapt_generic: fedopt.py:106-129 as torch ops on the device."""
     out = {}
     for k in keys:
@@ -121,7 +121,7 @@ def fp64_rate(n=25_000_000, rounds=7, blocks=3):
                                     [[]], [], hyper, False)
         return {"k": out}
 
-    arms = (("elementwise", lambda: opt._adapt_generic(["k"], {"k": avg}, {"k": cur}, False)),
+    arms = (("elementwise", lambda: opt._adapt_generic(["k"], {"k": avg}, {"k": cur}, False, avg.device)),
             ("torch-ops", lambda: torch_ops_generic(opt, ["k"], {"k": avg}, {"k": cur}, False)),
             ("fused", fused))
     meds = {name: [] for name, _ in arms}
