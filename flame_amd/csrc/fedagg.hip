@@ -6,7 +6,8 @@
 //   optimizer/fedopt.py:102-129 (+ fedadam.py:33-35, fedyogi.py:34-36, fedadagrad.py:33-35).
 //
 // Design:
-//   * HBM-read bound (≈1 flop per byte): no MFMA; every byte is read once.  LDS only holds
+//   * HBM-read bound (≈1 flop per byte): no MFMA (the pairwise Gram kernel, update_gram_kernel, is
+//     the one exception: fp64 matrix cores); every byte is read once.  LDS only holds
 //     output blocks so their HBM writes go out as bursts (FedOPT, the hierarchy), or caps
 //     residency at 2 workgroups per CU for long launches (HBM streams fastest there).
 //   * One workgroup (256 lanes) owns one chunk of one segment; each lane owns
@@ -1172,6 +1173,230 @@ __global__ __launch_bounds__(kBlock) void update_stats_finish_kernel(const doubl
         const double t = __dadd_rn(__dadd_rn(__dadd_rn(wsum[0], wsum[1]), wsum[2]), wsum[3]);
         st1(sumsq + blockIdx.x, __dadd_rn(ld1(sumsq + blockIdx.x), t));
     }
+}
+
+// ---------------------------------------------------------------- pairwise Gram (Multi-Krum)
+// G[i][j] = sum over every element of s(x_i) * s(x_j), s = stat_elem's sanitising (finite ? x : 0,
+// widened to fp64), on the fp64 matrix cores: v_mfma_f64_16x16x4_f64.  Clients go in blocks of 16
+// and tiles of kGramTile = 64.  A workgroup owns one tile pair (I <= J) over a range of chunks;
+// wave w owns the 16-client row block 16 w of tile I against the four column blocks of tile J: four
+// double4 accumulators.  Lane (c = lane & 15, g = lane >> 4) loads 16 bytes of client c at byte
+// 64 t + 16 g of the chunk, t = 0 .. 63: EPT elements, hence EPT k-steps whose k index is g -- A is
+// A[row = lane & 15][k = lane >> 4], B is B[k = lane >> 4][col = lane & 15], one double per lane,
+// so a client's vector is the A operand of its row block and the B operand of its column block
+// with no lane movement, and on a diagonal block they are the same registers.  The k order is the
+// same for every pair of clients, which is all a dot product needs.  Clients past n_clients and
+// elements past numel enter as 0.0 and are never read.  fp32 x fp32, bf16 x bf16 and fp16 x fp16
+// products are exact in fp64: the accumulation is the only rounding.
+// The C/D map of the f64 instruction is col = lane & 15, row = (lane >> 4) + 4 * reg (NOT the f32
+// map); gram_finish_kernel is the only place that reads it.  Each workgroup stores its 64 x 64
+// partial in register order (16 doubles per lane, coalesced) into the caller's scratch; the finish
+// kernel adds a tile pair's partials in a fixed order and writes both triangles from the upper one.
+// No floating-point atomic anywhere.  The non-finite count is taken by the diagonal workgroups
+// (each client's elements pass there exactly once as an A operand).
+constexpr int kGramTile = 64;                    // clients per tile: 4 waves x 16 rows, 4 column blocks
+constexpr int kGramMaxClients = 1024;
+constexpr int kGramPart = kGramTile * kGramTile; // doubles per partial
+#ifndef FLAME_T_GRAM_MIN_R
+#define FLAME_T_GRAM_MIN_R 4
+#endif
+constexpr int64_t kGramMinR = FLAME_T_GRAM_MIN_R;       // fewest chunks per workgroup (a 32 KiB partial each)
+#ifndef FLAME_T_GRAM_TARGET_WG
+#define FLAME_T_GRAM_TARGET_WG 2048
+#endif
+constexpr int64_t kGramTargetWG = FLAME_T_GRAM_TARGET_WG; // workgroups a launch aims at (8 per CU)
+#ifndef FLAME_T_GRAM_UNROLL
+#define FLAME_T_GRAM_UNROLL 2
+#endif
+constexpr int kGramUnroll = FLAME_T_GRAM_UNROLL;         // 64-byte steps whose loads are issued together
+static_assert(64 % kGramUnroll == 0, "a chunk is 64 steps of 64 bytes");
+using d4 = __attribute__((ext_vector_type(4))) double;
+
+constexpr int64_t gram_tiles(int n_clients) { return (n_clients + kGramTile - 1) / kGramTile; }
+constexpr int64_t gram_pairs(int n_clients) { return gram_tiles(n_clients) * (gram_tiles(n_clients) + 1) / 2; }
+// chunks per workgroup: at least kGramMinR, and so many that pairs x ranges stays near kGramTargetWG
+inline int64_t gram_range(int64_t n_chunks, int n_clients) {
+    const int64_t r = (n_chunks * gram_pairs(n_clients) + kGramTargetWG - 1) / kGramTargetWG;
+    return r > kGramMinR ? r : kGramMinR;
+}
+
+// 16 bytes of one client: the vector load, or (tail chunk, misaligned view) element loads with
+// bounds, zero bits past numel; no load at all for a client past the table (p == nullptr)
+template <int DT>
+__device__ __forceinline__ V16 gram_load(const char* p, bool vec, int64_t e, int64_t numel) {
+    using T = typename Tr<DT>::T;
+    constexpr int EPT = Tr<DT>::EPT;
+    V16 r;
+    r.w[0] = r.w[1] = r.w[2] = r.w[3] = 0;
+    if (p == nullptr) return r;
+    if (vec) return ld_nt(p);
+    T x[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) x[j] = e + j < numel ? ld1(reinterpret_cast<const T*>(p) + j) : T(0);
+    return pack<T, EPT>(x);
+}
+// sanitise (finite ? x : 0), count, widen
+template <int DT>
+__device__ __forceinline__ void gram_widen(const V16& v, double (&d)[Tr<DT>::EPT], unsigned& bad) {
+    using T = typename Tr<DT>::T;
+    constexpr int EPT = Tr<DT>::EPT;
+    T x[EPT];
+    unpack<T, EPT>(v, x);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        if constexpr (DT == FLAME_F64) {
+            const bool nf = !__builtin_isfinite(x[j]);
+            d[j] = nf ? 0.0 : x[j];
+            bad += nf;
+        } else {
+            const float f = Tr<DT>::ld(x[j]);
+            const bool nf = !__builtin_isfinite(f);
+            d[j] = static_cast<double>(nf ? 0.0f : f);
+            bad += nf;
+        }
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kBlock) void update_gram_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                             const uint64_t* __restrict__ clients, int n_clients,
+                                                             int64_t n_chunks, int64_t range, int n_pairs,
+                                                             double* __restrict__ scratch,
+                                                             unsigned long long* __restrict__ nonfinite) {
+    using T = typename Tr<DT>::T;
+    constexpr int EPT = Tr<DT>::EPT;
+    constexpr int64_t CE = chunk_elems<DT>();
+    static_assert(CE * sizeof(T) == kChunkBytes, "a chunk is 4 KiB of every dtype");
+    // tile pair (I <= J) of this workgroup: pairs are numbered row by row of the upper triangle
+    const int tiles = static_cast<int>(gram_tiles(n_clients));
+    int I = 0, rem = blockIdx.x;
+    while (rem >= tiles - I) rem -= tiles - I, ++I;
+    const int J = I + rem;
+    const bool diag = I == J;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int64_t c0 = static_cast<int64_t>(blockIdx.y) * range;
+    const int64_t c1 = c0 + range < n_chunks ? c0 + range : n_chunks;
+    const int arow = I * kGramTile + 16 * wave + c;          // this lane's A client
+    const bool wave_on = I * kGramTile + 16 * wave < n_clients;          // wave-uniform
+    int nb = (n_clients - J * kGramTile + 15) / 16;          // column blocks of tile J that hold clients
+    if (nb > 4) nb = 4;
+    d4 acc[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[b] = d4{0.0, 0.0, 0.0, 0.0};
+    unsigned bad = 0;
+    if (wave_on) {
+        int64_t chunk = c0;
+#pragma unroll 1
+        for (int s = find_segment(segs, n_segs, c0); s < n_segs && chunk < c1; ++s) {
+            const int64_t numel = segs[s].numel, begin = segs[s].chunk_begin;
+            if (numel <= 0) continue;
+            int64_t end = begin + (numel + CE - 1) / CE;
+            if (end > c1) end = c1;
+            if (chunk < begin) chunk = begin;
+            if (chunk >= end) continue;
+            const int64_t tstride = segs[s].client_tile_stride;
+            const int64_t step = tstride ? tstride : kChunkBytes;
+            const int64_t full = (segs[s].flags & FLAME_SEG_UNALIGNED) ? 0 : numel / CE;   // chunks [0, full) are whole and aligned
+            const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+            const char* pa = arow < n_clients ? reinterpret_cast<const char*>(ld1(cp + arow)) : nullptr;
+            const char* pb[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int col = J * kGramTile + 16 * b + c;
+                pb[b] = (b < nb && col < n_clients) ? reinterpret_cast<const char*>(ld1(cp + col)) : nullptr;
+            }
+#pragma unroll 1
+            for (int64_t cl = chunk - begin; cl < end - begin; ++cl) {
+                const bool vec = cl < full;                   // workgroup-uniform
+                const int64_t coff = cl * step + 16 * g;
+                const int64_t e0 = cl * CE + g * EPT;
+#pragma unroll 1
+                for (int t = 0; t < 64; t += kGramUnroll) {
+                    V16 ra[kGramUnroll], rb[kGramUnroll][4];
+#pragma unroll
+                    for (int u = 0; u < kGramUnroll; ++u) {
+                        const int64_t off = coff + 64 * (t + u);
+                        const int64_t e = e0 + 4 * EPT * (t + u);
+                        ra[u] = gram_load<DT>(pa ? pa + off : nullptr, vec, e, numel);
+#pragma unroll
+                        for (int b = 0; b < 4; ++b)
+                            if (b < nb && !(diag && b == wave)) rb[u][b] = gram_load<DT>(pb[b] ? pb[b] + off : nullptr, vec, e, numel);
+                    }
+#pragma unroll
+                    for (int u = 0; u < kGramUnroll; ++u) {
+                        double da[EPT];
+                        gram_widen<DT>(ra[u], da, bad);
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            if (b >= nb) continue;            // wave-uniform
+                            if (diag && b == wave) {          // wave-uniform: A and B are the same registers
+#pragma unroll
+                                for (int j = 0; j < EPT; ++j)
+                                    acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[j], da[j], acc[b], 0, 0, 0);
+                            } else {
+                                double db[EPT];
+                                unsigned ignored = 0;
+                                gram_widen<DT>(rb[u][b], db, ignored);
+#pragma unroll
+                                for (int j = 0; j < EPT; ++j)
+                                    acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[j], db[j], acc[b], 0, 0, 0);
+                            }
+                        }
+                    }
+                }
+            }
+            chunk = end;
+        }
+    }
+    // the partial, in register order: entry k = 4 b + reg of lane `threadIdx.x`
+    double* part = scratch + (static_cast<int64_t>(blockIdx.y) * n_pairs + blockIdx.x) * kGramPart;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st1(part + (4 * b + r) * kBlock + threadIdx.x, acc[b][r]);
+    if (diag && __any(bad != 0)) {      // rare: integer counts may use an atomic
+        bad += __shfl_xor(bad, 16, 64);          // the four lanes of a client
+        bad += __shfl_xor(bad, 32, 64);
+        if (g == 0 && bad != 0 && arow < n_clients) atomicAdd(nonfinite + arow, static_cast<unsigned long long>(bad));
+    }
+}
+
+// gram[i][j] (and [j][i]) += a tile pair's partials.  A workgroup owns 64 consecutive entries of
+// the pair's 4,096 (blockIdx.y); wave s adds the partials of ranges s, s + 4, .. in index order (a
+// wave's load is 512 contiguous bytes), then the four wave sums are added in wave order: a fixed
+// order whatever the launch, and one workgroup per pair no longer walks every partial alone (64 x
+// 25M fp32 has one pair and 2,035 partials).  Entry e = 256 k + t is what lane t of the Gram
+// workgroup held as k = 4 b + reg: row 16 (t >> 6) + ((t & 63) >> 4) + 4 reg and column
+// 16 b + (t & 15) of the tile pair -- the f64 instruction's C/D map.  A diagonal tile writes from
+// its upper triangle only, so both triangles are the same bits.
+constexpr int kGramFinishSplit = kGramPart / 64;     // workgroups per tile pair
+__global__ __launch_bounds__(kBlock) void gram_finish_kernel(const double* __restrict__ scratch, int64_t n_ranges,
+                                                             int n_pairs, int n_clients, double* __restrict__ gram) {
+    __shared__ double wsum[kWaves][64];
+    const int tiles = static_cast<int>(gram_tiles(n_clients));
+    int I = 0, rem = blockIdx.x;
+    while (rem >= tiles - I) rem -= tiles - I, ++I;
+    const int J = I + rem;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int e = static_cast<int>(blockIdx.y) * 64 + lane;
+    const int64_t stride = static_cast<int64_t>(n_pairs) * kGramPart;
+    const double* p = scratch + static_cast<int64_t>(blockIdx.x) * kGramPart + e;
+    double sum = 0.0;
+#pragma unroll 8
+    for (int64_t r = wave; r < n_ranges; r += kWaves) sum = __dadd_rn(sum, ld1(p + r * stride));
+    wsum[wave][lane] = sum;
+    __syncthreads();
+    if (wave != 0) return;
+    const int k = e >> 8, t = e & 255;
+    const int i = I * kGramTile + 16 * (t >> 6) + ((t & 63) >> 4) + 4 * (k & 3);
+    const int j = J * kGramTile + 16 * (k >> 2) + (t & 15);
+    if (i >= n_clients || j >= n_clients || i > j) return;
+    const double total = __dadd_rn(__dadd_rn(__dadd_rn(wsum[0][lane], wsum[1][lane]), wsum[2][lane]), wsum[3][lane]);
+    double* up = gram + static_cast<int64_t>(i) * n_clients + j;
+    const double v = __dadd_rn(ld1(up), total);
+    st1(up, v);
+    if (i != j) st1(gram + static_cast<int64_t>(j) * n_clients + i, v);
 }
 
 // ---------------------------------------------------------------- fused FedOPT (fp32)
@@ -3297,6 +3522,53 @@ int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int
     if (int rc = check_launch(who)) return rc;
     hipLaunchKernelGGL(update_stats_finish_kernel, dim3(static_cast<unsigned>(n_clients)), dim3(kBlock), 0, st,
                        static_cast<const double*>(scratch), n_wg, sumsq);
+    return check_launch(who);
+}
+
+// The Gram stands outside the launch-branch table as the statistics do: one instantiation per dtype.
+int flame_update_gram_max_clients(void) { return kGramMaxClients; }
+
+// An upper bound of what a launch writes (pairs x ranges partials), monotone in both arguments:
+// ranges <= ceil(n_chunks / kGramMinR) and pairs x ranges <= kGramTargetWG + pairs (gram_range).
+int64_t flame_update_gram_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
+    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll || n_clients <= 0 || n_clients > kGramMaxClients) return 0;
+    const int64_t pairs = gram_pairs(n_clients);
+    const int64_t a = (n_chunks + kGramMinR - 1) / kGramMinR * pairs, b = kGramTargetWG + pairs;
+    return (a < b ? a : b) * kGramPart * static_cast<int64_t>(sizeof(double));
+}
+
+int flame_update_gram(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                      const void* const* clients, int32_t n_clients, double* gram, int64_t* nonfinite,
+                      void* scratch, int64_t scratch_bytes, void* stream) {
+    const char* const who = "flame_update_gram";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (n_clients <= 0) return set_err(FLAME_EINVAL, "%s: n_clients <= 0", who);
+    if (n_clients > kGramMaxClients)
+        return set_err(FLAME_ENOTSUP, "%s: n_clients %d exceeds %d (flame_update_gram_max_clients)", who, n_clients,
+                       kGramMaxClients);
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (!gram || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
+    const int64_t need = flame_update_gram_scratch_bytes(n_chunks, n_clients);
+    if (!scratch || scratch_bytes < need)
+        return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
+                       static_cast<long long>(scratch_bytes), static_cast<long long>(need));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t range = gram_range(n_chunks, n_clients);
+    const int64_t n_ranges = (n_chunks + range - 1) / range;
+    const int n_pairs = static_cast<int>(gram_pairs(n_clients));
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((update_gram_kernel<decltype(dt)::value>),
+                           dim3(static_cast<unsigned>(n_pairs), static_cast<unsigned>(n_ranges)), dim3(kBlock), 0, st, segs,
+                           n_segs, reinterpret_cast<const uint64_t*>(clients), n_clients, n_chunks, range, n_pairs,
+                           static_cast<double*>(scratch), reinterpret_cast<unsigned long long*>(nonfinite));
+    });
+    if (int rc = check_launch(who)) return rc;
+    hipLaunchKernelGGL(gram_finish_kernel, dim3(static_cast<unsigned>(n_pairs), kGramFinishSplit), dim3(kBlock), 0, st,
+                       static_cast<const double*>(scratch), n_ranges, n_pairs, n_clients, gram);
     return check_launch(who);
 }
 

@@ -1206,6 +1206,86 @@ def update_stats(weights_list, device=None):
     return sumsq, nonfinite
 
 
+def gram_max_clients() -> int:
+    """The most updates one Gram launch takes (flame_update_gram_max_clients)."""
+    return int(N.lib().flame_update_gram_max_clients())
+
+
+def update_gram(weights_list, device=None):
+    """The pairwise Gram matrix of the updates over their sanitised float elements, and each
+    update's non-finite count (kernel: flame_update_gram, fp64 matrix cores; Krum / Multi-Krum's
+    distances come from it, ``optimizer/krum.py``).  Returns ``(gram: np.float64[n, n],
+    nonfinite: np.int64[n])`` in the order of ``weights_list``; ``gram[i][i]`` is
+    :func:`update_stats`' ``sumsq[i]`` up to summation order.
+
+    Built as :func:`update_stats` is: each update's FLOAT tensors are grouped by their own dtype
+    -- slots of one UpdateSlab through :func:`slab_rows`, without touching a view -- and every
+    dtype is one launch into the shared outputs.  Integer and bool tensors take no part.  Every
+    update must carry every float key in one dtype (ValueError naming the key: a distance between
+    updates of different shape means nothing).  The call ends with one device-to-host copy of
+    ``8 n (n + 1)`` bytes, which waits for the stream: this is a synchronisation point."""
+    ws = list(weights_list)
+    n = len(ws)
+    if n == 0:
+        return np.zeros((0, 0), np.float64), np.zeros(0, np.int64)
+    if n > gram_max_clients():
+        raise NotImplementedError(f"flame_amd.update_gram: {n} updates exceed the kernel's capacity of {gram_max_clients()}")
+    device = torch.device(device) if device is not None else pick_device(*ws)
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.update_gram: needs a HIP device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    keep = []
+    items = []                                  # (dtype, Seg), one per float key
+    w0 = ws[0]
+    rows = None
+    if getattr(w0, "slab", None) is not None:
+        fkeys = [k for k in w0.keys() if weight_dtype(w0, k).is_floating_point and weight_dtype(w0, k) in DTYPE_CODE]
+        numels = {k: _numel_of(logical_shape(w0, k)) for k in fkeys}
+        dts = {k: weight_dtype(w0, k) for k in fkeys}
+        rows = slab_rows(ws, fkeys, numels, dts, device) if fkeys else None
+        if rows is not None:
+            for k in fkeys:
+                ptrs, tile_bytes = rows[k]
+                items.append((dts[k], Seg(numels[k], clients=ptrs, tile_stride=tile_bytes)))
+    if rows is None:
+        per = collections.OrderedDict()         # key -> {dtype, shape} of the update that brought it first
+        for ci, w in enumerate(ws):
+            for k in w.keys():
+                dt = weight_dtype(w, k)
+                if dt.is_floating_point:
+                    dtype_code(dt)              # an unsupported float dtype raises
+                    per.setdefault(k, (dt, tuple(logical_shape(w, k))))
+        for ci, w in enumerate(ws):
+            for k, (dt, shape) in per.items():
+                if k not in w:
+                    raise ValueError(f"flame_amd.update_gram: update {ci} lacks the key {k!r} that another update has")
+                if weight_dtype(w, k) != dt or tuple(logical_shape(w, k)) != shape:
+                    raise ValueError(f"flame_amd.update_gram: update {ci} holds {k!r} as {weight_dtype(w, k)} "
+                                     f"{tuple(logical_shape(w, k))}, another as {dt} {shape}")
+        for k, (dt, shape) in per.items():
+            numel = _numel_of(shape)
+            row, tstride = _client_row([w[k] for w in ws], _KeyLike(numel, dt), device, keep)
+            items.append((dt, Seg(numel, clients=row, tile_stride=tstride)))
+    if not items:
+        return np.zeros((n, n), np.float64), np.zeros(n, np.int64)
+    out = torch.zeros(n * n + n, dtype=torch.int64, device=device)      # [gram as doubles | counts]
+    L = N.lib()
+    plans = [(code, plan(code, [sg for _, sg in its], [0.0] * n), sum(sg.numel for _, sg in its))
+             for code, its in by_dtype(items, lambda it: it[0]).items()]
+    sbytes = max(int(L.flame_update_gram_scratch_bytes(p.n_chunks, n)) for _, p, _ in plans)
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
+    for code, p, elems in plans:
+        _launch("flame_update_gram", elems * ITEMSIZE[code] * n, device, keep, p.meta,
+                lambda b: L.flame_update_gram(code, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+                                              out.data_ptr(), out.data_ptr() + 8 * n * n, scratch.data_ptr(), sbytes,
+                                              _stream_ptr(device)))
+    keep.append(scratch)
+    _keepalive(keep, device)
+    host = out.cpu().numpy()                    # the one D2H; waits for the launches above
+    return host[:n * n].view(np.float64).reshape(n, n).copy(), host[n * n:].copy()
+
+
 def trimmed_max_k() -> int:
     """The largest trim count the kernels carry (flame_agg_trimmed_max_k)."""
     return int(N.lib().flame_agg_trimmed_max_k())

@@ -6,6 +6,7 @@ from .fedavg import FedAvg
 from .fedbuff import FedBuff
 from .feddyn import FedDyn
 from .fedgft import FedGFT
+from .fedkrum import FedKrum, FedMultiKrum
 from .fedopt import FedOPT
 from .fedprox import FedProx
 from .fedtrimmed import FedMedian, FedTrimmedMean
@@ -14,4 +15,5 @@ from .scaffold import Scaffold
 from .train_result import TrainResult
 
 __all__ = ["AbstractOptimizer", "FedAvg", "FedOPT", "FedAdam", "FedYogi", "FedAdaGrad", "FedBuff",
-           "FedProx", "FedDyn", "FedGFT", "Scaffold", "TrainResult", "FedTrimmedMean", "FedMedian"]
+           "FedProx", "FedDyn", "FedGFT", "Scaffold", "TrainResult", "FedTrimmedMean", "FedMedian",
+           "FedMultiKrum", "FedKrum"]

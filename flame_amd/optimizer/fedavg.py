@@ -37,6 +37,14 @@ coordinate-wise trimmed mean of the popped updates (``engine.trimmed_mean``, ker
 ``flame_agg_trimmed``), added onto ``base_weights`` in place.  The ``nonfinite`` policies run
 first.  ``trim`` with ``clip_threshold``, ``defer=True`` or the sharded wrapper is refused.  With
 ``trim=None`` (the default) none of this runs.
+
+Krum / Multi-Krum (opt-in, ``FedAvg(krum=2)``, ``krum=0.2``, ``krum_select=1``, see
+``flame_amd/optimizer/krum.py``): ``do()`` measures the round's pairwise Gram matrix once
+(``engine.update_gram``, kernel ``flame_update_gram``), scores every update by its distances to its
+nearest neighbours on the host, and averages the selected ones with equal weights through the
+reduction above.  The Gram's diagonal is the guard's sum of squares, so ``clip_threshold`` and
+``nonfinite`` cost no second measuring pass.  ``krum`` with ``trim``, ``defer=True`` or the sharded
+wrapper is refused.  With ``krum=None`` (the default) none of this runs.
 """
 import collections
 import collections.abc
@@ -48,6 +56,7 @@ import torch
 
 from .. import engine, metrics
 from . import guard
+from . import krum as krum_
 from . import trim as trim_
 from .abstract import AbstractOptimizer
 from .fedbuff import _own_shm_views
@@ -134,7 +143,7 @@ class FedAvg(AbstractOptimizer):
     """FedAvg class."""
 
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
-                 clip_threshold=None, nonfinite: str = "keep", trim=None):
+                 clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
@@ -143,6 +152,19 @@ class FedAvg(AbstractOptimizer):
         self._deferred = None      # the DeferredWeights the last deferred do() returned
         self._init_guard(clip_threshold, nonfinite, defer)
         self._init_trim(trim, defer)
+        self._init_krum(krum, krum_select, defer)
+
+    def _init_krum(self, krum, krum_select, defer):
+        self.krum, self.krum_select = krum_.check_kwargs(krum, krum_select)
+        self.krum_records = []     # the last krum do()'s KrumRecords, in cache order
+        if self.krum is None:
+            return
+        if getattr(self, "trim", None) is not None:
+            krum_.refuse(f"{type(self).__name__}(trim=...)", self.krum,
+                         "two robust rules in one round have no stated meaning; choose trim or krum")
+        if defer or getattr(self, "chain_defer", False):
+            krum_.refuse(f"{type(self).__name__}(defer=True)", self.krum,
+                         "Krum scores every update against the round's others; use defer=False")
 
     def _init_trim(self, trim, defer):
         self.trim = trim_.check_kwarg(trim)
@@ -196,6 +218,55 @@ class FedAvg(AbstractOptimizer):
         scales = [records[i].scale for i in kept]
         return entries, (scales if any(s != 1.0 for s in scales) else None)
 
+    def _check_krum(self, cache, kwargs):
+        """What a krum round refuses before anything is popped; returns ``(f, q, m)``."""
+        if "flame_amd_key_groups" in kwargs:
+            krum_.refuse("ShardedOptimizer", self.krum,
+                         "each rank holds a slice of every update; its partial Gram matrices would need an "
+                         "all-reduce before the selection (a follow-up)")
+        return krum_.check_round(self.krum, self.krum_select, len(cache), engine.gram_max_clients())
+
+    def _pop_krum(self, cache, total, kwargs):
+        """_pop_guarded's sibling under ``krum``: pop, measure the round's Gram matrix once, let the
+        guard (if set) decide on its diagonal and the non-finite counts, select, and give the
+        selected updates the rate ``1 / len(selected)``.  Returns ``(entries, scales)`` as
+        _pop_guarded does; ``entries`` is empty when nothing can be selected."""
+        f, q, m = self._check_krum(cache, kwargs)
+        ends = list(cache.iterkeys())
+        popped = [cache.pop(e) for e in ends]
+        gram, nonfinite = engine.update_gram([t.weights for t in popped])
+        kept = list(range(len(ends)))
+        scales = [1.0] * len(ends)
+        if self.guarded:
+            try:
+                records, kept, _ = guard.apply_policy(ends, [t.count for t in popped], gram.diagonal(), nonfinite,
+                                                      total, self.clip_threshold, self.nonfinite)
+            except guard.NonFiniteUpdate as e:      # "raise": the records still say which ends were bad
+                self.update_stats = e.records
+                guard.save_metrics(self, e.records)
+                raise
+            self.update_stats = records
+            guard.save_metrics(self, records)
+            scales = [r.scale for r in records]
+            if len(kept) != len(ends):          # "skip" shrank the round
+                if not kept:
+                    self.krum_records = krum_.records(ends, gram, nonfinite, [float("inf")] * len(ends), [])
+                    return [], None
+                f, q, m = krum_.check_round(self.krum, self.krum_select, len(kept), engine.gram_max_clients())
+        idx = list(kept)
+        scores_k, selected_k = krum_.select(gram[idx][:, idx], nonfinite[idx], [scales[i] for i in idx], f, m)
+        scores = [float("inf")] * len(ends)
+        for pos, i in enumerate(idx):
+            scores[i] = scores_k[pos]
+        selected = [idx[pos] for pos in selected_k]
+        self.krum_records = krum_.records(ends, gram, nonfinite, scores, selected)
+        krum_.save_metrics(self, self.krum_records, f)
+        if not selected:
+            return [], None
+        entries = [(popped[i].weights, 1.0 / len(selected)) for i in selected]
+        sel_scales = [scales[i] for i in selected]
+        return entries, (sel_scales if any(s != 1.0 for s in sel_scales) else None)
+
     def _do_trimmed(self, base_weights, cache, total, kwargs):
         """do() under ``trim``: base_weights += the coordinate-wise trimmed mean of the cached
         updates.  A round that cannot be trimmed (``n <= 2k``, or ``k`` beyond the kernels'
@@ -225,6 +296,7 @@ class FedAvg(AbstractOptimizer):
         logger.debug("calling fedavg (flame_amd)")
         assert base_weights is not None
         self.update_stats = []     # this call's records only (an empty round measures nothing)
+        self.krum_records = []
         if isinstance(base_weights, DeferredWeights):
             base_weights = base_weights.materialize()
         pend = self._deferred
@@ -240,7 +312,11 @@ class FedAvg(AbstractOptimizer):
         if self.trim is not None:
             return self._do_trimmed(base_weights, cache, total, kwargs)
         scales = None
-        if self.guarded:
+        if self.krum is not None:
+            entries, scales = self._pop_krum(cache, total, kwargs)
+            if not entries:            # nothing eligible: as for an empty cache
+                return None
+        elif self.guarded:
             entries, scales = self._pop_guarded(cache, total)
             if not entries:            # every update skipped: as for an empty cache
                 return None

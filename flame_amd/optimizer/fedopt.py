@@ -81,7 +81,7 @@ class FedOPT(FedAvg):
     max_chain_bytes = 16 << 30
 
     def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
-                 nonfinite: str = "keep", trim=None):
+                 nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
         trim_.refuse(type(self).__name__, trim_.check_kwarg(trim),
                      "the fused FedOPT kernels form the weighted average themselves; a trimmed pseudo-gradient "
                      "is a follow-up")
@@ -92,7 +92,7 @@ class FedOPT(FedAvg):
         self._v = None
         self._agg = None
         self.chain_defer = defer        # before FedAvg's constructor: the guard refuses either defer
-        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite)
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, krum=krum, krum_select=krum_select)
         self.current_weights = None
         self._d_t = None
         self._prev_current = None
@@ -161,6 +161,9 @@ class FedOPT(FedAvg):
         logger.debug("calling fedopt (flame_amd)")
         self._check_poisoned()
         self.update_stats = []
+        self.krum_records = []
+        if self.krum is not None and len(cache) > 0 and total != 0:
+            self._check_krum(cache, kwargs)     # the sharded wrapper and an impossible round, before any pop
         if self.chain_defer and not kwargs.keys() & _SHARD_KWARGS:
             ch = self._chain
             if ch is not None and ch.base is base_weights and (len(cache) == 0 or total == 0):
@@ -195,7 +198,12 @@ class FedOPT(FedAvg):
     def _do_fused(self, base_weights, cache, total, key_groups=None, after_group=None, alloc=None):
         self.agg_weights = base_weights
         scales = None
-        if self.guarded:
+        if self.krum is not None:
+            entries, scales = self._pop_krum(cache, total, {} if key_groups is None else {"flame_amd_key_groups": key_groups})
+            if not entries:     # nothing eligible: as every update skipped
+                self.agg_weights = None
+                return self.current_weights
+        elif self.guarded:
             entries, scales = self._pop_guarded(cache, total)
             if not entries:     # every update skipped: FedAvg.do returns None (fedopt.py:80-85)
                 self.agg_weights = None

@@ -40,7 +40,9 @@ except Exception:  # noqa: BLE001
 class FedProx(FedAvg):
     """FedProx class (server side = FedAvg)."""
 
-    def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None):
-        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim)
+    def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None,
+                 krum_select=None):
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim, krum=krum,
+                         krum_select=krum_select)
         self.mu = mu
         self.regularizer = FedProxRegularizer(self.mu)

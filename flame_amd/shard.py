@@ -609,6 +609,11 @@ class ShardedOptimizer:
                 "flame_amd ShardedOptimizer: the wrapped optimizer's trim (coordinate-wise trimmed-mean / median "
                 "aggregation) is not supported under sharding: the selection kernel takes no key groups yet "
                 "(a follow-up)")
+        if getattr(inner, "krum", None) is not None:
+            raise NotImplementedError(
+                "flame_amd ShardedOptimizer: the wrapped optimizer's krum (Krum / Multi-Krum aggregation) is not "
+                "supported under sharding: each rank's partial Gram matrix would need an all-reduce before the "
+                "selection (a follow-up)")
         self.inner = inner
         # gather=False (FedAvg / FedProx): no all-gathers -- each rank's base_weights is current on its
         # owned ranges (and the replicated tails) only, one launch over them; for a caller whose next

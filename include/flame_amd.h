@@ -198,6 +198,36 @@ int flame_update_stats(int dtype, const flame_segment *segs, int32_t n_segs, int
 int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients);
 
 /*
+ * Pairwise Gram matrix of a round's updates: what Krum / Multi-Krum (Blanchard, El Mhamdi,
+ * Guerraoui, Stainer: "Machine Learning with Adversaries: Byzantine Tolerant Gradient Descent",
+ * NeurIPS 2017) needs of the device.  flame has no counterpart file.
+ *   segs, clients : the tables flame_update_stats takes; only numel, chunk_begin, flags
+ *                   (FLAME_SEG_UNALIGNED) and client_tile_stride of a segment are read, so one
+ *                   launch covers tensors, tiled UpdateSlab slots and misaligned views alike.
+ *   gram          : device double [n_clients][n_clients];  gram[i][j] += sum over every element e
+ *                   of every segment of s(x_i[e]) * s(x_j[e]), where s(x) is x widened to fp64 if x
+ *                   is finite, else 0.0 -- flame_update_stats' sanitising, so gram[i][i] is its
+ *                   sumsq[i] up to summation order.  Products of f32 / bf16 / f16 values are exact
+ *                   in fp64; the accumulation (v_mfma_f64_16x16x4_f64, then fp64 adds) is the only
+ *                   rounding: |error| <= (elements + 1) * 2^-53 * sum |x_i x_j| (f64 keys: + 2, one
+ *                   more rounding per product).  Both triangles are written and are bitwise equal.
+ *   nonfinite     : device int64 [n_clients];  nonfinite[i] += number of NaN / +-inf elements.
+ *   scratch       : device buffer of >= flame_update_gram_scratch_bytes(n_chunks, n_clients) bytes
+ *                   (scratch_bytes: its size), overwritten.  At most 1 GiB for every n_clients <=
+ *                   1024 at any n_chunks (the chunk range of a workgroup grows with both).
+ * Both outputs are accumulated into: zero them, then launch once per float dtype of a model on one
+ * stream.  No floating-point atomics: partial sums are combined in a fixed order, so the same
+ * launch on the same data gives the same bits.  dtype FLAME_F32, FLAME_BF16, FLAME_F16 or
+ * FLAME_F64 (integer dtypes: FLAME_ENOTSUP); 1 <= n_clients <= flame_update_gram_max_clients()
+ * (1024; more: FLAME_ENOTSUP).  Not a launch branch of flame_launch_branches().
+ */
+int flame_update_gram(int dtype, const flame_segment *segs, int32_t n_segs, int64_t n_chunks,
+                      const void *const *clients, int32_t n_clients, double *gram, int64_t *nonfinite,
+                      void *scratch, int64_t scratch_bytes, void *stream);
+int64_t flame_update_gram_scratch_bytes(int64_t n_chunks, int32_t n_clients);
+int flame_update_gram_max_clients(void);
+
+/*
  * Server-side update guard, part 2: flame_agg_reduce with a per-client clip scale.
  *   scales32 : device [n_clients] fp32 scales (f32 / bf16 / f16); scales64: device [n_clients]
  *              fp64 scales (FLAME_F64; either may be NULL when the dtype does not use it).
