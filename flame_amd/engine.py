@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
@@ -1007,6 +1008,25 @@ def pick_device(*dicts) -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _cuda_device_of(d):
+    """The device of the first GPU tensor in dict ``d`` (None: it holds none)."""
+    return next((t.device for t in d.values() if isinstance(t, torch.Tensor) and t.is_cuda), None)
+
+
+def _hip_device(device, who, *dicts, prefer=None) -> torch.device:
+    """Launcher ``who``'s device: ``device`` if given, else where ``prefer`` (the aggregate) lives, else
+    :func:`pick_device` over ``dicts``; anything but a GPU raises, one without an index is the current."""
+    if device is not None:
+        device = torch.device(device)
+    else:
+        device = (prefer is not None and _cuda_device_of(prefer)) or pick_device(*dicts)
+    if device.type != "cuda":
+        raise RuntimeError(f"flame_amd.{who}: needs a HIP device (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 class _Target:
     """A tensor to be updated in place on the device; stages CPU / strided tensors."""
 
@@ -1039,8 +1059,7 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     if not entries:
         return
     if device is None:   # the aggregate's own device first (no per-entry list for the common case)
-        device = next((t.device for t in agg.values() if isinstance(t, torch.Tensor) and t.is_cuda), None) \
-            or pick_device(*[w for w, _ in entries])
+        device = _cuda_device_of(agg) or pick_device(*[w for w, _ in entries])
     if scales is not None and len(scales) != len(entries):
         raise ValueError("accumulate: one scale per entry")
     if _accumulate_slab(agg, entries, device, key_groups, after_group, scales):
@@ -1120,11 +1139,98 @@ class _KeyLike:
         return torch.empty((), dtype=self.dtype).element_size()
 
 
-def _numel_of(shape) -> int:
-    n = 1
-    for d in shape:
-        n *= int(d)
-    return n
+def _rows(ws, fkeys, numels, dts, device, keep, per_view=True):
+    """``{key: (pointer row, tile stride bytes)}`` of keys every update of ``ws`` carries: from the
+    slot numbers when all are slots of ONE UpdateSlab (:func:`slab_rows`, no view touched), else with
+    ``per_view`` one :func:`_client_row` per key (``keep``: what must outlive the launch), else None."""
+    rows = slab_rows(ws, fkeys, numels, dts, device) if fkeys and getattr(ws[0], "slab", None) is not None else None
+    if rows is None and per_view:
+        rows = {k: _client_row([w[k] for w in ws], _KeyLike(numels[k], dts[k]), device, keep) for k in fkeys}
+    return rows
+
+
+def _float_items(ws, device, keep, uniform=None):
+    """The FLOAT keys of the updates ``ws`` as ``(dtype, client indices, Seg)`` items, one per key,
+    for the launches that read updates and write no model.  Integer and bool tensors take no part;
+    an unsupported float dtype raises (:func:`dtype_code`).  Slots of one UpdateSlab take
+    :func:`_rows`' fast path (the first slot's keys stand for all); otherwise every view is looked at:
+
+    * ragged allowed (``uniform`` None, :func:`update_stats`): a ``(key, dtype)`` is measured over
+      the updates that carry it, so the client indices may differ between items;
+    * uniform required (``uniform`` names the launcher, :func:`update_gram`): every update carries
+      every float key in one dtype and shape (a distance between other updates means nothing)."""
+    all_cis = tuple(range(len(ws)))
+    w0 = ws[0]
+    if getattr(w0, "slab", None) is not None:
+        fkeys = [k for k in w0.keys() if weight_dtype(w0, k).is_floating_point and weight_dtype(w0, k) in DTYPE_CODE]
+        numels = {k: math.prod(logical_shape(w0, k)) for k in fkeys}
+        dts = {k: weight_dtype(w0, k) for k in fkeys}
+        rows = _rows(ws, fkeys, numels, dts, device, keep, per_view=False)
+        if rows is not None:
+            return [(dts[k], all_cis, Seg(numels[k], clients=rows[k][0], tile_stride=rows[k][1])) for k in fkeys]
+    per = collections.OrderedDict()     # first-seen order.  ragged: (key, dtype) -> client indices;
+    for ci, w in enumerate(ws):         # uniform: key -> (dtype, shape) of the update that brought it first
+        for k in w.keys():
+            dt = weight_dtype(w, k)
+            if dt.is_floating_point:
+                dtype_code(dt)          # an unsupported float dtype raises
+                if uniform is None:
+                    per.setdefault((k, dt), []).append(ci)
+                else:
+                    per.setdefault(k, (dt, tuple(logical_shape(w, k))))
+    if uniform is None:
+        keyed = [(k, dt, logical_shape(ws[cis[0]], k), tuple(cis)) for (k, dt), cis in per.items()]
+    else:
+        for ci, w in enumerate(ws):
+            for k, (dt, shape) in per.items():
+                if k not in w:
+                    raise ValueError(f"flame_amd.{uniform}: update {ci} lacks the key {k!r} that another update has")
+                if weight_dtype(w, k) != dt or tuple(logical_shape(w, k)) != shape:
+                    raise ValueError(f"flame_amd.{uniform}: update {ci} holds {k!r} as {weight_dtype(w, k)} "
+                                     f"{tuple(logical_shape(w, k))}, another as {dt} {shape}")
+        keyed = [(k, dt, shape, all_cis) for k, (dt, shape) in per.items()]
+    items = []
+    for k, dt, shape, cis in keyed:
+        numel = math.prod(shape)
+        row, tstride = _client_row([ws[ci][k] for ci in cis], _KeyLike(numel, dt), device, keep)
+        items.append((dt, cis, Seg(numel, clients=row, tile_stride=tstride)))
+    return items
+
+
+def _measure(kernel, items, device, keep, width):
+    """Entry point ``kernel`` (scratch size: ``<kernel>_scratch_bytes``) over :func:`_float_items`'
+    items: one launch per (dtype, client set) in first-seen order, every group planned first (no
+    rates are read), ONE scratch buffer sized for the largest plan, ONE zeroed int64 output block
+    all launches add into, copied back once (that copy waits for the stream).  The block is
+    ``[first | second]``, each part by *slot*: one per distinct client set in first-seen order
+    (normally one), ``width(n)`` and ``n`` words for ``n`` clients.  Returns the parts (host int64)
+    and ``{client set: (first offset, second offset)}``."""
+    L = N.lib()
+    entry, scratch_bytes = getattr(L, kernel), getattr(L, kernel + "_scratch_bytes")
+    one = items[0][1]       # the usual case is ONE client set (the same tuple): no per-item hash of it then
+    also = None if all(it[1] is one for it in items) else (lambda it: it[1])
+    groups = [(key if also else (key, one), its) for key, its in by_dtype(items, lambda it: it[0], also=also).items()]
+    slots, first, second = collections.OrderedDict(), 0, 0      # groups: [((dtype code, client indices), items)]
+    for (_, cis), _ in groups:
+        if cis not in slots:
+            slots[cis] = (first, second)
+            first += width(len(cis))
+            second += len(cis)
+    out = torch.zeros(first + second, dtype=torch.int64, device=device)
+    plans = [(code, cis, plan(code, [sg for _, _, sg in its], [0.0] * len(cis)), sum(sg.numel for _, _, sg in its))
+             for (code, cis), its in groups]
+    sbytes = max(int(scratch_bytes(p.n_chunks, p.n_clients)) for _, _, p, _ in plans)
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
+    for code, cis, p, elems in plans:
+        o1, o2 = slots[cis]
+        _launch(kernel, elems * ITEMSIZE[code] * len(cis), device, keep, p.meta,
+                lambda b: entry(code, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+                                out.data_ptr() + 8 * o1, out.data_ptr() + 8 * (first + o2), scratch.data_ptr(), sbytes,
+                                _stream_ptr(device)))
+    keep.append(scratch)
+    _keepalive(keep, device)
+    host = out.cpu().numpy()                    # the one D2H; waits for the launches above
+    return host[:first], host[first:], slots
 
 
 def update_stats(weights_list, device=None):
@@ -1133,73 +1239,24 @@ def update_stats(weights_list, device=None):
     root of the former).  Returns ``(sumsq: np.float64[n], nonfinite: np.int64[n])`` in the
     order of ``weights_list``.
 
-    Each update's FLOAT tensors (f32 / bf16 / f16 / f64) are grouped by their own dtype -- slots
-    of one UpdateSlab through :func:`slab_rows`, without touching a view -- and every dtype is one
-    launch into the shared outputs.  Integer and bool tensors take no part (BatchNorm's
-    ``num_batches_tracked`` is not part of the norm).  The call ends with one device-to-host copy
-    of 16 bytes per update, which waits for the stream: this is a synchronisation point."""
+    Each update's FLOAT tensors are grouped by their own dtype (:func:`_float_items`, ragged key
+    sets allowed) and every dtype is one launch into ``[sumsq as doubles | counts]`` (:func:`_measure`).
+    Integer and bool tensors take no part (BatchNorm's ``num_batches_tracked`` is not part of the
+    norm).  The call ends with one device-to-host copy of 16 bytes per update, which waits for the
+    stream: this is a synchronisation point."""
     ws = list(weights_list)
     n = len(ws)
-    if n == 0:
-        return np.zeros(0, np.float64), np.zeros(0, np.int64)
-    device = torch.device(device) if device is not None else pick_device(*ws)
-    if device.type != "cuda":
-        raise RuntimeError("flame_amd.update_stats: needs a HIP device (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    keep = []
-    items = []                                  # (dtype, client indices, Seg), one per key
-    all_cis = tuple(range(n))
-    w0 = ws[0]
-    rows = None
-    if getattr(w0, "slab", None) is not None:
-        fkeys = [k for k in w0.keys() if weight_dtype(w0, k).is_floating_point and weight_dtype(w0, k) in DTYPE_CODE]
-        numels = {k: _numel_of(logical_shape(w0, k)) for k in fkeys}
-        dts = {k: weight_dtype(w0, k) for k in fkeys}
-        rows = slab_rows(ws, fkeys, numels, dts, device) if fkeys else None
-        if rows is not None:
-            for k in fkeys:
-                ptrs, tile_bytes = rows[k]
-                items.append((dts[k], all_cis, Seg(numels[k], clients=ptrs, tile_stride=tile_bytes)))
-    if rows is None:
-        per = collections.OrderedDict()         # (key, dtype) -> client indices, in first-seen order
-        for ci, w in enumerate(ws):
-            for k in w.keys():
-                dt = weight_dtype(w, k)
-                if dt.is_floating_point:
-                    dtype_code(dt)              # an unsupported float dtype raises
-                    per.setdefault((k, dt), []).append(ci)
-        for (k, dt), cis in per.items():
-            numel = _numel_of(logical_shape(ws[cis[0]], k))
-            row, tstride = _client_row([ws[ci][k] for ci in cis], _KeyLike(numel, dt), device, keep)
-            items.append((dt, tuple(cis), Seg(numel, clients=row, tile_stride=tstride)))
-    groups = by_dtype(items, lambda it: it[0], also=lambda it: it[1])     # (dtype code, client indices) -> items
-    # one output block per distinct client set (normally one: every update has every key)
-    slots, total = collections.OrderedDict(), 0
-    for (_, cis) in groups:
-        if cis not in slots:
-            slots[cis] = total
-            total += len(cis)
-    if total == 0:
-        return np.zeros(n, np.float64), np.zeros(n, np.int64)
-    out = torch.zeros(2 * total, dtype=torch.int64, device=device)      # [sumsq as doubles | counts]
-    L = N.lib()
-    plans = [(code, cis, plan(code, [sg for _, _, sg in its], [0.0] * len(cis)), sum(sg.numel for _, _, sg in its))
-             for (code, cis), its in groups.items()]
-    sbytes = max(int(L.flame_update_stats_scratch_bytes(p.n_chunks, p.n_clients)) for _, _, p, _ in plans)
-    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
-    for code, cis, p, elems in plans:
-        _launch("flame_update_stats", elems * ITEMSIZE[code] * len(cis), device, keep, p.meta,
-                lambda b: L.flame_update_stats(code, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
-                                               out.data_ptr() + 8 * slots[cis],
-                                               out.data_ptr() + 8 * (total + slots[cis]), scratch.data_ptr(), sbytes,
-                                               _stream_ptr(device)))
-    keep.append(scratch)
-    _keepalive(keep, device)
-    host = out.cpu().numpy()                    # the one D2H; waits for the launches above
-    sq, nf = host[:total].view(np.float64), host[total:]
     sumsq, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int64)
-    for cis, o in slots.items():
+    if n == 0:
+        return sumsq, nonfinite
+    device = _hip_device(device, "update_stats", *ws)
+    keep = []
+    items = _float_items(ws, device, keep)
+    if not items:
+        return sumsq, nonfinite
+    sq, nf, slots = _measure("flame_update_stats", items, device, keep, int)
+    sq = sq.view(np.float64)
+    for cis, (o, _) in slots.items():
         idx = np.asarray(cis, dtype=np.int64)
         sumsq[idx] += sq[o:o + len(cis)]
         nonfinite[idx] += nf[o:o + len(cis)]
@@ -1218,11 +1275,9 @@ def update_gram(weights_list, device=None):
     nonfinite: np.int64[n])`` in the order of ``weights_list``; ``gram[i][i]`` is
     :func:`update_stats`' ``sumsq[i]`` up to summation order.
 
-    Built as :func:`update_stats` is: each update's FLOAT tensors are grouped by their own dtype
-    -- slots of one UpdateSlab through :func:`slab_rows`, without touching a view -- and every
-    dtype is one launch into the shared outputs.  Integer and bool tensors take no part.  Every
-    update must carry every float key in one dtype (ValueError naming the key: a distance between
-    updates of different shape means nothing).  The call ends with one device-to-host copy of
+    :func:`update_stats`' front end under :func:`_float_items`' other policy: every update must carry
+    every float key in one dtype and shape (ValueError naming the key), so there is one slot,
+    ``[n * n gram as doubles | n counts]``.  The call ends with one device-to-host copy of
     ``8 n (n + 1)`` bytes, which waits for the stream: this is a synchronisation point."""
     ws = list(weights_list)
     n = len(ws)
@@ -1230,60 +1285,13 @@ def update_gram(weights_list, device=None):
         return np.zeros((0, 0), np.float64), np.zeros(0, np.int64)
     if n > gram_max_clients():
         raise NotImplementedError(f"flame_amd.update_gram: {n} updates exceed the kernel's capacity of {gram_max_clients()}")
-    device = torch.device(device) if device is not None else pick_device(*ws)
-    if device.type != "cuda":
-        raise RuntimeError("flame_amd.update_gram: needs a HIP device (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _hip_device(device, "update_gram", *ws)
     keep = []
-    items = []                                  # (dtype, Seg), one per float key
-    w0 = ws[0]
-    rows = None
-    if getattr(w0, "slab", None) is not None:
-        fkeys = [k for k in w0.keys() if weight_dtype(w0, k).is_floating_point and weight_dtype(w0, k) in DTYPE_CODE]
-        numels = {k: _numel_of(logical_shape(w0, k)) for k in fkeys}
-        dts = {k: weight_dtype(w0, k) for k in fkeys}
-        rows = slab_rows(ws, fkeys, numels, dts, device) if fkeys else None
-        if rows is not None:
-            for k in fkeys:
-                ptrs, tile_bytes = rows[k]
-                items.append((dts[k], Seg(numels[k], clients=ptrs, tile_stride=tile_bytes)))
-    if rows is None:
-        per = collections.OrderedDict()         # key -> {dtype, shape} of the update that brought it first
-        for ci, w in enumerate(ws):
-            for k in w.keys():
-                dt = weight_dtype(w, k)
-                if dt.is_floating_point:
-                    dtype_code(dt)              # an unsupported float dtype raises
-                    per.setdefault(k, (dt, tuple(logical_shape(w, k))))
-        for ci, w in enumerate(ws):
-            for k, (dt, shape) in per.items():
-                if k not in w:
-                    raise ValueError(f"flame_amd.update_gram: update {ci} lacks the key {k!r} that another update has")
-                if weight_dtype(w, k) != dt or tuple(logical_shape(w, k)) != shape:
-                    raise ValueError(f"flame_amd.update_gram: update {ci} holds {k!r} as {weight_dtype(w, k)} "
-                                     f"{tuple(logical_shape(w, k))}, another as {dt} {shape}")
-        for k, (dt, shape) in per.items():
-            numel = _numel_of(shape)
-            row, tstride = _client_row([w[k] for w in ws], _KeyLike(numel, dt), device, keep)
-            items.append((dt, Seg(numel, clients=row, tile_stride=tstride)))
+    items = _float_items(ws, device, keep, uniform="update_gram")
     if not items:
         return np.zeros((n, n), np.float64), np.zeros(n, np.int64)
-    out = torch.zeros(n * n + n, dtype=torch.int64, device=device)      # [gram as doubles | counts]
-    L = N.lib()
-    plans = [(code, plan(code, [sg for _, sg in its], [0.0] * n), sum(sg.numel for _, sg in its))
-             for code, its in by_dtype(items, lambda it: it[0]).items()]
-    sbytes = max(int(L.flame_update_gram_scratch_bytes(p.n_chunks, n)) for _, p, _ in plans)
-    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
-    for code, p, elems in plans:
-        _launch("flame_update_gram", elems * ITEMSIZE[code] * n, device, keep, p.meta,
-                lambda b: L.flame_update_gram(code, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
-                                              out.data_ptr(), out.data_ptr() + 8 * n * n, scratch.data_ptr(), sbytes,
-                                              _stream_ptr(device)))
-    keep.append(scratch)
-    _keepalive(keep, device)
-    host = out.cpu().numpy()                    # the one D2H; waits for the launches above
-    return host[:n * n].view(np.float64).reshape(n, n).copy(), host[n * n:].copy()
+    gram, nf, _ = _measure("flame_update_gram", items, device, keep, lambda n_cl: n_cl * n_cl)
+    return gram.view(np.float64).reshape(n, n).copy(), nf.copy()
 
 
 def trimmed_max_k() -> int:
@@ -1324,28 +1332,20 @@ def trimmed_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, d
             raise ValueError("trimmed_mean: every update must carry the aggregate's float keys in the aggregate's dtypes")
     if init_first and others:
         raise ValueError(f"trimmed_mean: init_first covers float keys only; {others!r} need a base")
-    if device is not None:
-        device = torch.device(device)
-    else:
-        device = next((t.device for t in agg.values() if isinstance(t, torch.Tensor) and t.is_cuda), None) \
-            or pick_device(*ws)
-    if device.type != "cuda":
-        raise RuntimeError("flame_amd.trimmed_mean: needs a HIP device (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _hip_device(device, "trimmed_mean", *ws, prefer=agg)
     if fkeys:
         for key in fkeys:
             dtype_code(want[key])               # an unsupported float dtype raises
         targets = {key: _Target(agg[key], device) for key in fkeys}
         numels = {key: agg[key].numel() for key in fkeys}
-        rows = slab_rows(ws, fkeys, numels, want, device) if getattr(ws[0], "slab", None) is not None else None
         keep = []
+        rows = _rows(ws, fkeys, numels, want, device, keep)
         L = N.lib()
         for code, ks in by_dtype(fkeys, lambda key: want[key]).items():
             segs = []
             for key in ks:
                 o = targets[key].dev
-                row, tstride = rows[key] if rows is not None else _client_row([w[key] for w in ws], o, device, keep)
+                row, tstride = rows[key]
                 segs.append(Seg(o.numel(), out=o.data_ptr(), inp=0 if init_first else o.data_ptr(), clients=row,
                                 tile_stride=tstride))
             p = plan(code, segs, [0.0] * n)     # the kernel reads no rates: today's block, as update_stats builds it
@@ -1602,10 +1602,7 @@ def logical_tensor(weights, k) -> torch.Tensor:
     shape = tuple(logical_shape(weights, k))
     if tuple(v.shape) == shape:
         return v
-    n = 1
-    for d in shape:
-        n *= d
-    return v.reshape(-1)[:n].reshape(shape)
+    return v.reshape(-1)[:math.prod(shape)].reshape(shape)
 
 
 def first_tmp(weights: dict, rate: float, *, device=None) -> dict:

@@ -88,12 +88,21 @@ def flush() -> None:
         _save(mc, alias, rec)
 
 
+def collector(owner):
+    """``(metric_collector, alias)`` of an optimizer: the collector is None when it reports nothing,
+    the alias defaults to the class name in lower case."""
+    mc = getattr(owner, "metric_collector", None)
+    if mc is None:
+        return None, None
+    return mc, getattr(owner, "metric_alias", None) or type(owner).__name__.lower()
+
+
 @contextlib.contextmanager
 def recording(owner):
     """Report the launches made inside the block to ``owner.metric_collector`` -- for work an
     optimizer queued in ``do()`` and launches later (a deferred aggregate reduced when it is
     first read), under the owner's alias like its own calls."""
-    mc = getattr(owner, "metric_collector", None)
+    mc, alias = collector(owner)
     if mc is None or getattr(owner, "_flame_amd_recording", False):
         yield
         return
@@ -103,7 +112,7 @@ def recording(owner):
             yield
     finally:
         owner._flame_amd_recording = False
-    submit(mc, getattr(owner, "metric_alias", None) or type(owner).__name__.lower(), rec)
+    submit(mc, alias, rec)
 
 
 def instrument(fn):
@@ -112,7 +121,7 @@ def instrument(fn):
 
     @functools.wraps(fn)
     def wrapper(self, *args, **kwargs):
-        mc = getattr(self, "metric_collector", None)
+        mc, alias = collector(self)
         if mc is None or getattr(self, "_flame_amd_recording", False):
             return fn(self, *args, **kwargs)
         self._flame_amd_recording = True
@@ -121,7 +130,7 @@ def instrument(fn):
                 out = fn(self, *args, **kwargs)
         finally:
             self._flame_amd_recording = False
-        submit(mc, getattr(self, "metric_alias", None) or type(self).__name__.lower(), rec)
+        submit(mc, alias, rec)
         return out
 
     return wrapper

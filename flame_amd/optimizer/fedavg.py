@@ -24,27 +24,28 @@ anything reads the result (``w[k]``, ``items()``, ``load_state_dict``, ``deepcop
 ``max_pending`` arrivals / ``max_pending_bytes`` are queued.  ``base_weights`` itself
 (a plain dict) lags until then: read the returned object, as flame's roles do.
 
-Server-side update guard (opt-in, ``FedAvg(clip_threshold=C, nonfinite="skip")``, see
-``flame_amd/optimizer/guard.py``): ``do()`` measures every popped update once
-(``engine.update_stats``: its norm over the float tensors and its non-finite count), applies
-the ``nonfinite`` policy, forms the rates from the remaining ``total`` and reduces with the
-clip scales (``flame_agg_reduce_scaled``).  ``update_stats`` holds the round's records.
-With both kwargs at their defaults none of this runs.
+One selection stage (``FedAvg._select``) stands between the cache and the reduction, for this class,
+FedProx, FedGFT and the FedOPT family alike, and for every combination of the three opt-in kwargs
+below.  It is a straight pipeline -- refuse, pop, measure, policy, select, rates:
+what the round refuses is refused with the cache still full; the entries are popped in
+``cache.iterkeys()`` order; the updates are measured at most once; the ``nonfinite`` policy and the
+clip scales come from the sums of squares; krum selects among what is left; rates and scales are
+formed last.  With every kwarg at its default the stage is the reference's pop loop and nothing else.
+What the kwargs refuse of each other, of ``defer=True`` and of the sharded wrapper is one table,
+``flame_amd/optimizer/refusals.py``.
 
-Trimmed mean / median (opt-in, ``FedAvg(trim=2)``, ``trim=0.1``, ``trim="median"``, see
-``flame_amd/optimizer/trim.py``): ``do()`` replaces the weighted average of the float keys by the
-coordinate-wise trimmed mean of the popped updates (``engine.trimmed_mean``, kernel
-``flame_agg_trimmed``), added onto ``base_weights`` in place.  The ``nonfinite`` policies run
-first.  ``trim`` with ``clip_threshold``, ``defer=True`` or the sharded wrapper is refused.  With
-``trim=None`` (the default) none of this runs.
-
-Krum / Multi-Krum (opt-in, ``FedAvg(krum=2)``, ``krum=0.2``, ``krum_select=1``, see
-``flame_amd/optimizer/krum.py``): ``do()`` measures the round's pairwise Gram matrix once
-(``engine.update_gram``, kernel ``flame_update_gram``), scores every update by its distances to its
-nearest neighbours on the host, and averages the selected ones with equal weights through the
-reduction above.  The Gram's diagonal is the guard's sum of squares, so ``clip_threshold`` and
-``nonfinite`` cost no second measuring pass.  ``krum`` with ``trim``, ``defer=True`` or the sharded
-wrapper is refused.  With ``krum=None`` (the default) none of this runs.
+* Update guard (``clip_threshold=C``, ``nonfinite="skip"``; ``guard.py``): measured by
+  ``engine.update_stats`` (each update's norm over the float tensors and its non-finite count); the
+  rates come from what is left of ``total`` and the reduction takes the clip scales
+  (``flame_agg_reduce_scaled``).  ``update_stats`` holds the round's records.
+* Trimmed mean / median (``trim=2``, ``trim=0.1``, ``trim="median"``; ``trim.py``): the weighted
+  average of the float keys is replaced by the coordinate-wise trimmed mean of what the stage left
+  (``engine.trimmed_mean``, kernel ``flame_agg_trimmed``), added onto ``base_weights`` in place.
+* Krum / Multi-Krum (``krum=2``, ``krum=0.2``, ``krum_select=1``; ``krum.py``): measured by
+  ``engine.update_gram`` (the pairwise Gram matrix, kernel ``flame_update_gram``) instead; its diagonal
+  is the guard's sum of squares, so the guard costs no second pass.  Every update is scored on the
+  host by its distances to its nearest neighbours and the selected ones are averaged with equal
+  weights through the reduction above.
 """
 import collections
 import collections.abc
@@ -55,7 +56,7 @@ import weakref
 import torch
 
 from .. import engine, metrics
-from . import guard
+from . import guard, refusals
 from . import krum as krum_
 from . import trim as trim_
 from .abstract import AbstractOptimizer
@@ -142,6 +143,8 @@ class DeferredWeights(collections.abc.Mapping):
 class FedAvg(AbstractOptimizer):
     """FedAvg class."""
 
+    chain_defer = False        # FedOPT's deferred eager chain (an instance attribute there)
+
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
                  clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
         self.agg_weights = None
@@ -150,146 +153,81 @@ class FedAvg(AbstractOptimizer):
         self.max_pending = max_pending
         self.max_pending_bytes = max_pending_bytes
         self._deferred = None      # the DeferredWeights the last deferred do() returned
-        self._init_guard(clip_threshold, nonfinite, defer)
-        self._init_trim(trim, defer)
-        self._init_krum(krum, krum_select, defer)
-
-    def _init_krum(self, krum, krum_select, defer):
-        self.krum, self.krum_select = krum_.check_kwargs(krum, krum_select)
-        self.krum_records = []     # the last krum do()'s KrumRecords, in cache order
-        if self.krum is None:
-            return
-        if getattr(self, "trim", None) is not None:
-            krum_.refuse(f"{type(self).__name__}(trim=...)", self.krum,
-                         "two robust rules in one round have no stated meaning; choose trim or krum")
-        if defer or getattr(self, "chain_defer", False):
-            krum_.refuse(f"{type(self).__name__}(defer=True)", self.krum,
-                         "Krum scores every update against the round's others; use defer=False")
-
-    def _init_trim(self, trim, defer):
-        self.trim = trim_.check_kwarg(trim)
-        self.trim_k = None         # the last trimmed do()'s k
-        if self.trim is None:
-            return
-        if self.clip_threshold is not None:
-            trim_.refuse(f"{type(self).__name__}(clip_threshold=...)", self.trim,
-                         "a clipped update would be trimmed on its scaled values, which needs the scale inside "
-                         "the selection kernel (a follow-up); use nonfinite= alone with trim")
-        if defer or getattr(self, "chain_defer", False):
-            trim_.refuse(f"{type(self).__name__}(defer=True)", self.trim,
-                         "a trimmed mean needs every update of the round at once; use defer=False")
-
-    def _init_guard(self, clip_threshold, nonfinite, defer):
         self.clip_threshold, self.nonfinite = guard.check_kwargs(clip_threshold, nonfinite)
+        self.trim = trim_.check_kwarg(trim)
+        self.krum, self.krum_select = krum_.check_kwargs(krum, krum_select)
         self.update_stats = []     # the last do()'s UpdateRecords, in cache order (empty: nothing measured)
-        if defer or getattr(self, "chain_defer", False):     # FedAvg's queue or FedOPT's chain
-            guard.refuse(f"{type(self).__name__}(defer=True)", self.clip_threshold, self.nonfinite,
-                         "a deferred queue fixes each arrival's rate when it arrives, before the guard "
-                         "could measure it; use defer=False")
+        self.trim_k = None         # the last trimmed do()'s k
+        self.krum_records = []     # the last krum do()'s KrumRecords, in cache order
+        # every kwarg is valid: now what they refuse of each other and of a deferred queue (FedAvg's or FedOPT's)
+        refusals.check(self, *[c for c in ("clip_threshold", "trim") if refusals.is_set(self, c)],
+                       *(("defer",) if defer or self.chain_defer else ()))
 
     @property
     def guarded(self) -> bool:
         return guard.is_set(self.clip_threshold, self.nonfinite)
 
-    def _pop_entries(self, cache, total):
-        # after popping, the item is removed from the cache (fedavg.py:80-82); rate = count / total
-        return [(tres.weights, tres.count / total) for tres in map(cache.pop, list(cache.iterkeys()))]
-
-    def _pop_guarded(self, cache, total):
-        """_pop_entries under the update guard: pop, measure every update once, apply the
-        ``nonfinite`` policy, and only then form the rates from what is left of ``total``.
-        Returns ``(entries, scales)``; ``entries`` is empty when every update was skipped,
-        ``scales`` None when no update is clipped (the plain reduction then runs)."""
-        ends = list(cache.iterkeys())
-        popped = [cache.pop(e) for e in ends]
-        sumsq, nonfinite = engine.update_stats([t.weights for t in popped])
-        try:
-            records, kept, total = guard.apply_policy(ends, [t.count for t in popped], sumsq, nonfinite, total,
-                                                      self.clip_threshold, self.nonfinite)
-        except guard.NonFiniteUpdate as e:      # "raise": the records still say which ends were bad
-            self.update_stats = e.records
-            guard.save_metrics(self, e.records)
-            raise
-        self.update_stats = records
-        guard.save_metrics(self, records)
-        if not kept or total == 0:
-            return [], None
-        entries = [(popped[i].weights, popped[i].count / total) for i in kept]
-        scales = [records[i].scale for i in kept]
-        return entries, (scales if any(s != 1.0 for s in scales) else None)
-
-    def _check_krum(self, cache, kwargs):
-        """What a krum round refuses before anything is popped; returns ``(f, q, m)``."""
+    def _check_round(self, n, kwargs=()):
+        """What a round of ``n`` updates refuses (stage step 1: before anything is popped): the sharded
+        wrapper's key groups, and an ``n`` that krum or trim cannot take.  Returns krum's ``(f, q, m)``."""
         if "flame_amd_key_groups" in kwargs:
-            krum_.refuse("ShardedOptimizer", self.krum,
-                         "each rank holds a slice of every update; its partial Gram matrices would need an "
-                         "all-reduce before the selection (a follow-up)")
-        return krum_.check_round(self.krum, self.krum_select, len(cache), engine.gram_max_clients())
+            refusals.check(self, "key_groups")
+        if self.krum is not None:
+            return krum_.check_round(self.krum, self.krum_select, n, engine.gram_max_clients())
+        if self.trim is not None:
+            trim_.check_round(self.trim, n, engine.trimmed_max_k())
 
-    def _pop_krum(self, cache, total, kwargs):
-        """_pop_guarded's sibling under ``krum``: pop, measure the round's Gram matrix once, let the
-        guard (if set) decide on its diagonal and the non-finite counts, select, and give the
-        selected updates the rate ``1 / len(selected)``.  Returns ``(entries, scales)`` as
-        _pop_guarded does; ``entries`` is empty when nothing can be selected."""
-        f, q, m = self._check_krum(cache, kwargs)
-        ends = list(cache.iterkeys())
+    def _select(self, cache, total, kwargs=()):
+        """THE selection stage of a round, for every class and every combination of the update guard,
+        ``trim`` and ``krum``: refuse, pop, measure, policy, select, rates.  Returns
+        ``(entries, scales)``: ``[(weights, rate)]`` in cache order -- empty when nothing is left to
+        aggregate, as for an empty cache -- and the clip scales, None unless some update is clipped
+        (the plain reduction then runs)."""
+        if self.krum is None and self.trim is None and not self.guarded:
+            # the plain round: after popping, the item is removed from the cache (fedavg.py:80-82);
+            # rate = count / total; nothing is measured or recorded
+            return [(tres.weights, tres.count / total) for tres in map(cache.pop, list(cache.iterkeys()))], None
+        plan = self._check_round(len(cache), kwargs)                    # 1. refuse, the cache still full
+        ends = list(cache.iterkeys())                                   # 2. pop, in cache.iterkeys() order
         popped = [cache.pop(e) for e in ends]
-        gram, nonfinite = engine.update_gram([t.weights for t in popped])
-        kept = list(range(len(ends)))
-        scales = [1.0] * len(ends)
-        if self.guarded:
+        n = len(ends)
+        if self.krum is not None:                                       # 3. measure once
+            gram, nonfinite = engine.update_gram([t.weights for t in popped])
+            sumsq = gram.diagonal()                                     # the guard's sums of squares: no second pass
+        elif self.guarded:
+            sumsq, nonfinite = engine.update_stats([t.weights for t in popped])
+        kept, scales = list(range(n)), [1.0] * n
+        if self.guarded:                                                # 4. the nonfinite policy and the clip scales
+            refused = None
             try:
-                records, kept, _ = guard.apply_policy(ends, [t.count for t in popped], gram.diagonal(), nonfinite,
-                                                      total, self.clip_threshold, self.nonfinite)
+                records, kept, total = guard.apply_policy(ends, [t.count for t in popped], sumsq, nonfinite, total,
+                                                          self.clip_threshold, self.nonfinite)
             except guard.NonFiniteUpdate as e:      # "raise": the records still say which ends were bad
-                self.update_stats = e.records
-                guard.save_metrics(self, e.records)
-                raise
+                refused, records = e, e.records
             self.update_stats = records
             guard.save_metrics(self, records)
+            if refused is not None:
+                raise refused
             scales = [r.scale for r in records]
-            if len(kept) != len(ends):          # "skip" shrank the round
-                if not kept:
-                    self.krum_records = krum_.records(ends, gram, nonfinite, [float("inf")] * len(ends), [])
-                    return [], None
-                f, q, m = krum_.check_round(self.krum, self.krum_select, len(kept), engine.gram_max_clients())
-        idx = list(kept)
-        scores_k, selected_k = krum_.select(gram[idx][:, idx], nonfinite[idx], [scales[i] for i in idx], f, m)
-        scores = [float("inf")] * len(ends)
-        for pos, i in enumerate(idx):
-            scores[i] = scores_k[pos]
-        selected = [idx[pos] for pos in selected_k]
-        self.krum_records = krum_.records(ends, gram, nonfinite, scores, selected)
-        krum_.save_metrics(self, self.krum_records, f)
-        if not selected:
-            return [], None
-        entries = [(popped[i].weights, 1.0 / len(selected)) for i in selected]
-        sel_scales = [scales[i] for i in selected]
-        return entries, (sel_scales if any(s != 1.0 for s in sel_scales) else None)
-
-    def _do_trimmed(self, base_weights, cache, total, kwargs):
-        """do() under ``trim``: base_weights += the coordinate-wise trimmed mean of the cached
-        updates.  A round that cannot be trimmed (``n <= 2k``, or ``k`` beyond the kernels'
-        capacity) raises before anything is popped.  Under a ``nonfinite`` policy the updates are
-        popped and measured first, as the guard does, and ``n`` is what remains."""
-        if "flame_amd_key_groups" in kwargs:
-            trim_.refuse("ShardedOptimizer", self.trim,
-                         "each rank would trim its own slices in waves; the selection kernel takes no key groups "
-                         "yet (a follow-up)")
-        max_k = engine.trimmed_max_k()
-        k = trim_.check_round(self.trim, len(cache), max_k)
-        if self.guarded:
-            entries, _ = self._pop_guarded(cache, total)
-            if not entries:            # every update skipped: as for an empty cache
-                return None
-            if len(entries) != len(self.update_stats):
-                k = trim_.check_round(self.trim, len(entries), max_k)
+        if self.krum is not None:                                       # 5. select ...
+            chosen, scores = [], [float("inf")] * n
+            if kept:
+                f, _, m = plan if len(kept) == n else self._check_round(len(kept))     # "skip" shrank the round
+                scores_k, chosen_k = krum_.select(gram[kept][:, kept], nonfinite[kept], [scales[i] for i in kept], f, m)
+                for pos, i in enumerate(kept):
+                    scores[i] = scores_k[pos]
+                chosen = [kept[pos] for pos in chosen_k]
+            self.krum_records = krum_.records(ends, gram, nonfinite, scores, chosen)
+            if kept:
+                krum_.save_metrics(self, self.krum_records, f)
+            rates = [1.0 / len(chosen) for _ in chosen]                 # 6. ... and rates: equal weights
         else:
-            entries = self._pop_entries(cache, total)
-        engine.trimmed_mean(base_weights, [w for w, _ in entries], k)
-        self.trim_k = k
-        trim_.save_metrics(self, k, len(entries))
-        return base_weights
+            chosen = kept if total != 0 else []
+            if chosen and len(chosen) != n:
+                self._check_round(len(chosen))                          # trim: is what "skip" left enough?
+            rates = [popped[i].count / total for i in chosen]           # 6. count / what is left of total
+        scales = [scales[i] for i in chosen]
+        return [(popped[i].weights, r) for i, r in zip(chosen, rates)], (scales if any(s != 1.0 for s in scales) else None)
 
     def do(self, base_weights, cache, *, total: int = 0, version: int = 0, **kwargs):
         """Aggregate the cached trainer updates into ``base_weights`` (in place)."""
@@ -309,19 +247,16 @@ class FedAvg(AbstractOptimizer):
         self.agg_weights = base_weights
         if len(cache) == 0 or total == 0:
             return None
+        entries, scales = self._select(cache, total, kwargs)
+        if not entries:                # nothing left to aggregate: as for an empty cache
+            return None
         if self.trim is not None:
-            return self._do_trimmed(base_weights, cache, total, kwargs)
-        scales = None
-        if self.krum is not None:
-            entries, scales = self._pop_krum(cache, total, kwargs)
-            if not entries:            # nothing eligible: as for an empty cache
-                return None
-        elif self.guarded:
-            entries, scales = self._pop_guarded(cache, total)
-            if not entries:            # every update skipped: as for an empty cache
-                return None
-        else:
-            entries = self._pop_entries(cache, total)
+            # base_weights += the coordinate-wise trimmed mean of what the stage left (n of them)
+            k = trim_.count(self.trim, len(entries))
+            engine.trimmed_mean(base_weights, [w for w, _ in entries], k)
+            self.trim_k = k
+            trim_.save_metrics(self, k, len(entries))
+            return base_weights
         if self.defer and "flame_amd_key_groups" not in kwargs:
             if pend is None:
                 self._deferred = pend = DeferredWeights(base_weights, self.max_pending, self.max_pending_bytes,

@@ -31,6 +31,11 @@ returns a :class:`DeferredCurrent`; the queue runs as ONE ``flame_fedopt_chain``
 when anything reads the results (the returned mapping, ``current_weights``, ``m_t``,
 ``v_t``, ``agg_weights``), bit-identical to a launch per call.  Until then the base dict
 lags, as ``FedAvg(defer=True)``'s does.  ``d_t`` is not kept across a deferred queue.
+
+The update guard and ``krum`` reach the fused round through FedAvg's one selection stage
+(``FedAvg._select``: refuse, pop, measure, policy, select, rates), called once by ``_do_fused`` as
+``FedAvg.do`` calls it; what a krum round refuses is also checked in ``do()`` before the deferred
+chain is flushed.  A round with clip scales takes the split launch.  ``trim`` is refused.
 """
 import collections.abc
 import copy
@@ -43,6 +48,7 @@ from collections import OrderedDict
 import torch
 
 from .. import elementwise as ew, engine, metrics
+from . import refusals
 from . import trim as trim_
 from .fedavg import FedAvg
 
@@ -82,16 +88,15 @@ class FedOPT(FedAvg):
 
     def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
                  nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
-        trim_.refuse(type(self).__name__, trim_.check_kwarg(trim),
-                     "the fused FedOPT kernels form the weighted average themselves; a trimmed pseudo-gradient "
-                     "is a follow-up")
+        self.trim = trim_.check_kwarg(trim)
+        refusals.check(self, "fedopt")      # trim: before anything else of the constructor
         self._poisoned = None
         self._chain = None
         self._current = None
         self._m = None
         self._v = None
         self._agg = None
-        self.chain_defer = defer        # before FedAvg's constructor: the guard refuses either defer
+        self.chain_defer = defer        # before FedAvg's constructor, which checks what a deferred chain refuses
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, krum=krum, krum_select=krum_select)
         self.current_weights = None
         self._d_t = None
@@ -163,7 +168,7 @@ class FedOPT(FedAvg):
         self.update_stats = []
         self.krum_records = []
         if self.krum is not None and len(cache) > 0 and total != 0:
-            self._check_krum(cache, kwargs)     # the sharded wrapper and an impossible round, before any pop
+            self._check_round(len(cache), kwargs)   # the sharded wrapper and an impossible round, before any pop
         if self.chain_defer and not kwargs.keys() & _SHARD_KWARGS:
             ch = self._chain
             if ch is not None and ch.base is base_weights and (len(cache) == 0 or total == 0):
@@ -183,8 +188,7 @@ class FedOPT(FedAvg):
             # flame_amd.shard passes its plan's waves (one launch per wave, its all-gather started
             # right behind it) and an allocator placing each key's new `current` straight into
             # the full tensor the gather fills (callers from flame pass none of these)
-            return self._do_fused(base_weights, cache, total, kwargs.get("flame_amd_key_groups"),
-                                  kwargs.get("flame_amd_after_group"), kwargs.get("flame_amd_out_alloc"))
+            return self._do_fused(base_weights, cache, total, kwargs)
         self.agg_weights = super().do(base_weights, cache, total=total, version=version)
         if self.agg_weights is None:
             return self.current_weights
@@ -195,21 +199,14 @@ class FedOPT(FedAvg):
         return self.current_weights
 
     # ------------------------------------------------------------------ fused round
-    def _do_fused(self, base_weights, cache, total, key_groups=None, after_group=None, alloc=None):
+    def _do_fused(self, base_weights, cache, total, kwargs):
+        key_groups, after_group = kwargs.get("flame_amd_key_groups"), kwargs.get("flame_amd_after_group")
+        alloc = kwargs.get("flame_amd_out_alloc")
         self.agg_weights = base_weights
-        scales = None
-        if self.krum is not None:
-            entries, scales = self._pop_krum(cache, total, {} if key_groups is None else {"flame_amd_key_groups": key_groups})
-            if not entries:     # nothing eligible: as every update skipped
-                self.agg_weights = None
-                return self.current_weights
-        elif self.guarded:
-            entries, scales = self._pop_guarded(cache, total)
-            if not entries:     # every update skipped: FedAvg.do returns None (fedopt.py:80-85)
-                self.agg_weights = None
-                return self.current_weights
-        else:
-            entries = self._pop_entries(cache, total)
+        entries, scales = self._select(cache, total, kwargs)
+        if not entries:         # nothing left to aggregate: FedAvg.do returns None (fedopt.py:80-85)
+            self.agg_weights = None
+            return self.current_weights
         current = self.current_weights
         device = engine.pick_device(base_weights, current, *[w for w, _ in entries])
         keys = list(base_weights.keys())

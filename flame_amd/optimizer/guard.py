@@ -27,6 +27,9 @@ corrects the call that skips; later calls of the round use the role's uncorrecte
 import collections
 import math
 
+from .. import metrics
+from . import refusals
+
 NONFINITE_POLICIES = ("keep", "raise", "skip")
 NORM_EPS = 1e-6          # differential_privacy.py:80
 
@@ -62,8 +65,7 @@ def is_set(clip_threshold, nonfinite) -> bool:
 def refuse(who: str, clip_threshold, nonfinite, why: str) -> None:
     """Raise if a class or combination that is out of the guard's scope is asked to guard."""
     if is_set(clip_threshold, nonfinite):
-        raise NotImplementedError(f"flame_amd {who}: clip_threshold / nonfinite (the server-side update guard) "
-                                  f"are not supported here: {why}")
+        raise NotImplementedError(refusals.message("guard", who, why))
 
 
 def clip_scale(norm: float, clip_threshold) -> float:
@@ -99,10 +101,9 @@ def apply_policy(ends, counts, sumsq, nonfinite, total, clip_threshold, policy):
 
 def save_metrics(owner, records) -> None:
     """``update_norm_max`` / ``updates_clipped`` / ``updates_skipped`` beside the kernel metrics."""
-    mc = getattr(owner, "metric_collector", None)
+    mc, alias = metrics.collector(owner)
     if mc is None or not records:
         return
-    alias = getattr(owner, "metric_alias", None) or type(owner).__name__.lower()
     mc.save("update_norm_max", alias, max(r.norm for r in records))
     mc.save("updates_clipped", alias, sum(1 for r in records if r.scale != 1.0))
     mc.save("updates_skipped", alias, sum(1 for r in records if r.skipped))

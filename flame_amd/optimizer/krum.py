@@ -25,6 +25,8 @@ import math
 
 import numpy as np
 
+from .. import metrics
+
 KrumRecord = collections.namedtuple("KrumRecord", "end norm nonfinite score selected")
 
 
@@ -118,19 +120,11 @@ def records(ends, gram, nonfinite, scores, selected):
                        scores[i], i in chosen) for i, end in enumerate(ends)]
 
 
-def refuse(who: str, krum, why: str) -> None:
-    """Raise if a class or combination that is out of Krum's scope is asked for it."""
-    if krum is not None:
-        raise NotImplementedError(f"flame_amd {who}: krum (Krum / Multi-Krum aggregation) is not supported here: "
-                                  f"{why}")
-
-
 def save_metrics(owner, recs, f: int) -> None:
     """``krum_selected`` / ``krum_f`` / ``krum_score_max`` (over the finite scores) beside the kernel metrics."""
-    mc = getattr(owner, "metric_collector", None)
+    mc, alias = metrics.collector(owner)
     if mc is None or not recs:
         return
-    alias = getattr(owner, "metric_alias", None) or type(owner).__name__.lower()
     finite = [r.score for r in recs if math.isfinite(r.score)]
     mc.save("krum_selected", alias, sum(1 for r in recs if r.selected))
     mc.save("krum_f", alias, f)

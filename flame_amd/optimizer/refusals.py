@@ -1,0 +1,57 @@
+"""What the update guard, ``trim`` and ``krum`` refuse, stated once: ``(feature, context) -> why``.
+
+A *feature* is ``"guard"`` (``clip_threshold`` / ``nonfinite``), ``"trim"`` or ``"krum"``; a *context*
+is what it meets: a deferred queue (``"defer"``: ``FedAvg(defer=True)`` or FedOPT's chain), another
+kwarg (``"clip_threshold"``, ``"trim"``), the FedOPT family (``"fedopt"``), the sharded wrapper at its
+construction (``"shard"``) or the key groups it passes to ``do()`` (``"key_groups"``).  Constructors
+set their attributes first and then call :func:`check` once; the order of the table is the order in
+which a constructor that meets several contexts reports them.  Every refusal is a
+NotImplementedError; a bad value is a ValueError / TypeError from the kwarg's own check before it.
+"""
+NAME = {"guard": "clip_threshold / nonfinite (the server-side update guard) are",
+        "trim": "trim (coordinate-wise trimmed-mean / median aggregation) is",
+        "krum": "krum (Krum / Multi-Krum aggregation) is"}
+
+# (feature, context) -> (who refuses, ``{cls}`` the optimizer's class; why)
+TABLE = {
+    ("guard", "defer"): ("{cls}(defer=True)", "a deferred queue fixes each arrival's rate when it arrives, before "
+                         "the guard could measure it; use defer=False"),
+    ("trim", "fedopt"): ("{cls}", "the fused FedOPT kernels form the weighted average themselves; a trimmed "
+                         "pseudo-gradient is a follow-up"),
+    ("trim", "clip_threshold"): ("{cls}(clip_threshold=...)", "a clipped update would be trimmed on its scaled values, "
+                                 "which needs the scale inside the selection kernel (a follow-up); use nonfinite= "
+                                 "alone with trim"),
+    ("trim", "defer"): ("{cls}(defer=True)", "a trimmed mean needs every update of the round at once; use defer=False"),
+    ("krum", "trim"): ("{cls}(trim=...)", "two robust rules in one round have no stated meaning; choose trim or krum"),
+    ("krum", "defer"): ("{cls}(defer=True)", "Krum scores every update against the round's others; use defer=False"),
+    ("trim", "key_groups"): ("ShardedOptimizer", "each rank would trim its own slices in waves; the selection kernel "
+                             "takes no key groups yet (a follow-up)"),
+    ("krum", "key_groups"): ("ShardedOptimizer", "each rank holds a slice of every update; its partial Gram matrices "
+                             "would need an all-reduce before the selection (a follow-up)"),
+    ("guard", "shard"): ("ShardedOptimizer", "each rank sees only its slices, so the global norm needs an all-reduce of "
+                         "the per-update sums of squares (a follow-up)"),
+    ("trim", "shard"): ("ShardedOptimizer", "the selection kernel takes no key groups yet (a follow-up)"),
+    ("krum", "shard"): ("ShardedOptimizer", "each rank's partial Gram matrix would need an all-reduce before the "
+                        "selection (a follow-up)"),
+}
+
+
+def message(feature: str, who: str, why: str, wrapped: bool = False) -> str:
+    if wrapped:
+        return f"flame_amd {who}: the wrapped optimizer's {NAME[feature]} not supported under sharding: {why}"
+    return f"flame_amd {who}: {NAME[feature]} not supported here: {why}"
+
+
+def is_set(opt, what: str) -> bool:
+    """Is feature (or kwarg) ``what`` set on ``opt`` (any optimizer: one without the kwargs has none)?"""
+    if what == "guard":
+        return bool(getattr(opt, "guarded", False))
+    return getattr(opt, what, None) is not None
+
+
+def check(opt, *contexts) -> None:
+    """Raise the table's refusal for the first of its rows whose context is among ``contexts`` and
+    whose feature ``opt`` has set."""
+    for (feature, context), (who, why) in TABLE.items():
+        if context in contexts and is_set(opt, feature):
+            raise NotImplementedError(message(feature, who.format(cls=type(opt).__name__), why, context == "shard"))

@@ -18,6 +18,8 @@ counters.  The arithmetic is stated in DESIGN.md §2 and ``include/flame_amd.h``
 """
 import math
 
+from .. import metrics
+
 MEDIAN = "median"
 
 
@@ -64,18 +66,10 @@ def check_round(trim, n: int, max_k: int) -> int:
     return k
 
 
-def refuse(who: str, trim, why: str) -> None:
-    """Raise if a class or combination that is out of the trimmed mean's scope is asked to trim."""
-    if trim is not None:
-        raise NotImplementedError(f"flame_amd {who}: trim (coordinate-wise trimmed-mean / median aggregation) "
-                                  f"is not supported here: {why}")
-
-
 def save_metrics(owner, k: int, n: int) -> None:
     """``trim_k`` / ``updates_trimmed_from`` beside the kernel metrics."""
-    mc = getattr(owner, "metric_collector", None)
+    mc, alias = metrics.collector(owner)
     if mc is None:
         return
-    alias = getattr(owner, "metric_alias", None) or type(owner).__name__.lower()
     mc.save("trim_k", alias, k)
     mc.save("updates_trimmed_from", alias, n)

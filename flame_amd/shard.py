@@ -47,6 +47,7 @@ from typing import Dict, Optional
 import torch
 
 from . import engine, shm_lease
+from .optimizer import refusals
 
 ALIGN_ELEMS = 2048               # a multiple of every kernel chunk / slab tile (1024 fp32, 2048 bf16 / fp16)
 DEFAULT_FRACS = (0.75, 0.20, 0.05)
@@ -599,21 +600,7 @@ class ShardedOptimizer:
     def __init__(self, inner, group=None, device: Optional[torch.device] = None, accumulate_only: bool = False,
                  *, waves: Optional[bool] = None, fracs=DEFAULT_FRACS, align: int = ALIGN_ELEMS,
                  plan: Optional[ShardPlan] = None, gather: bool = True):
-        if getattr(inner, "guarded", False):
-            raise NotImplementedError(
-                "flame_amd ShardedOptimizer: the wrapped optimizer's clip_threshold / nonfinite (the server-side "
-                "update guard) are not supported under sharding: each rank sees only its slices, so the global "
-                "norm needs an all-reduce of the per-update sums of squares (a follow-up)")
-        if getattr(inner, "trim", None) is not None:
-            raise NotImplementedError(
-                "flame_amd ShardedOptimizer: the wrapped optimizer's trim (coordinate-wise trimmed-mean / median "
-                "aggregation) is not supported under sharding: the selection kernel takes no key groups yet "
-                "(a follow-up)")
-        if getattr(inner, "krum", None) is not None:
-            raise NotImplementedError(
-                "flame_amd ShardedOptimizer: the wrapped optimizer's krum (Krum / Multi-Krum aggregation) is not "
-                "supported under sharding: each rank's partial Gram matrix would need an all-reduce before the "
-                "selection (a follow-up)")
+        refusals.check(inner, "shard")      # the update guard, trim and krum: each rank sees only its slices
         self.inner = inner
         # gather=False (FedAvg / FedProx): no all-gathers -- each rank's base_weights is current on its
         # owned ranges (and the replicated tails) only, one launch over them; for a caller whose next

@@ -8,16 +8,23 @@ A case's trace is the ordered list of
 * ``["upload", <block hex>]``          every ``engine._staging.upload``, with the block's bytes,
 * ``["call", <entry point>, [args]]``  every native call, with every argument,
 * ``["timed", <name>, <bytes>]``       every timing record,
+* ``["reduce_", [outs], [[clients]], [rates], {kwargs}]``  a nested ``engine.reduce_`` (``trimmed_mean``
+  sends its integer keys there through ``accumulate``), by label: ``reduce_`` has a device check of
+  its own, and what it launches is pinned by the ``reduce_*`` cases,
+* ``["return", [[shape, dtype, <hex>], ...]]``  the arrays a measuring front end returns,
 * ``["raise", <type>, <message>, <flame_partial>]``  the exception a case ends in.
 
 Addresses are position-independent: an argument equal to ``data_ptr()`` of a tensor the case
 labelled is that label; a pointer into an uploaded block is ``{"block": i, "off": n}``; a host
 block handed to a kernel-argument entry point is ``{"argmeta": <hex>}``; inside a block, a word
-equal to a labelled tensor's address is replaced by a fixed stand-in for that label.
+equal to a labelled tensor's address is replaced by a fixed stand-in for that label.  What the
+engine allocates itself is named by its place in the entry point's arguments: an output pointer is
+``{"out": <byte offset from the case's first output pointer>}``, the scratch buffer ``"scratch"``.
 
 The expected traces are ``tests/golden/engine_launch_trace.json``, written by
 ``tests/golden/make_engine_launch_trace.py`` from the engine as it stood before its launch paths
-were merged into one; the comparison is event by event, byte by byte.
+were merged into one (the ``update_stats`` / ``update_gram`` / ``trimmed_mean`` cases: before those
+three were given one front end); the comparison is event by event, byte by byte.
 """
 import contextlib
 import ctypes
@@ -35,9 +42,12 @@ FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "en
 CPU = torch.device("cpu")
 STREAM = 0x5157
 FORWARDED = ("flame_chunk_elems", "flame_scale_add_chunk_elems", "flame_agg_argmeta_max_bytes",
-             "flame_update_stats_scratch_bytes")
+             "flame_update_stats_scratch_bytes", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
+             "flame_agg_trimmed_max_k")
 # position of (host block, its byte count) in the kernel-argument entry points
 ARGMETA_AT = {"flame_agg_reduce_argmeta": 2, "flame_fedopt_reduce_adapt_argmeta": 3, "flame_hier_fedbuff_argmeta": 2}
+# position of (the output pointers, the scratch pointer) in the entry points whose caller allocates both
+SELF_ALLOCATED = {"flame_update_stats": ((6, 7), 8), "flame_update_gram": ((6, 7), 8)}
 
 
 class _Event:
@@ -62,6 +72,7 @@ class Tracer:
         self.blocks = []          # uploaded blocks (CPU tensors, kept alive: no address is reused)
         self.tensors = []
         self.fail_at, self.rc, self.n_calls = fail_at, rc, 0
+        self.out_base = None      # the first output pointer an entry point of SELF_ALLOCATED was handed
         self.real = N.lib()
 
     def t(self, label, tensor):
@@ -112,13 +123,29 @@ class Tracer:
             at = ARGMETA_AT.get(name)
             if at is not None:
                 args[at] = {"argmeta": self._hex(ctypes.string_at(args[at], args[at + 1]))}
-            self.events.append(["call", name, [a if isinstance(a, dict) else self._arg(a) for a in args]])
+            outs, scratch = SELF_ALLOCATED.get(name, ((), None))
+            for i in outs:
+                if self.out_base is None:
+                    self.out_base = args[i]
+                args[i] = {"out": args[i] - self.out_base}
+            if scratch is not None:
+                args[scratch] = "scratch"
+            self.events.append(["call", name, [a if isinstance(a, (dict, str)) else self._arg(a) for a in args]])
             self.n_calls += 1
             return self.rc if self.n_calls == self.fail_at else 0
         return call
 
     def timed(self, ev):
         self.events.append(["timed", ev[0], int(ev[3])])
+
+    def reduce_(self, outs, ins, clients, rates, **kw):
+        assert ins is outs
+        name = lambda t: self.labels[t.data_ptr()][0]     # noqa: E731
+        self.events.append(["reduce_", [name(o) for o in outs], [[name(c) for c in row] for row in clients],
+                            [float(r).hex() for r in rates], {k: v for k, v in kw.items() if v is not None}])
+
+    def returned(self, arrays):
+        self.events.append(["return", [[list(a.shape), str(a.dtype), a.tobytes().hex()] for a in arrays]])
 
 
 class _Timings(list):
@@ -156,11 +183,14 @@ def run_case(name):
         st.enter_context(_patched(engine._staging, upload=tr.upload, hold=lambda t, device: None))
         st.enter_context(_patched(engine, _stream_ptr=lambda device: STREAM, current_stream=lambda device: stream,
                                   host_device_pointer=lambda p: p, kernel_events=_Timings(tr),
+                                  _hip_device=lambda device, who, *dicts, prefer=None: CPU,
                                   ARGMETA=opts.get("argmeta", True),
                                   XCD_MAP_MIN_CHUNKS=opts.get("xcd", engine.XCD_MAP_MIN_CHUNKS)))
         st.enter_context(_patched(torch.cuda, Event=_Event))
         try:
-            fn(tr)
+            out = fn(tr)
+            if out is not None:
+                tr.returned(out)
         except Exception as e:  # noqa: BLE001 - the exception is part of the trace
             tr.events.append(["raise", type(e).__name__, str(e), bool(getattr(e, "flame_partial", False))])
     return json.loads(json.dumps(tr.events))
@@ -351,6 +381,61 @@ case("feddyn_merged")(lambda tr: _feddyn(tr, ["a", "b"], ["a", "b", "c"], {"a", 
 case("feddyn_two_phase")(lambda tr: _feddyn(tr, ["b", "a"], ["a", "b"], {"a"}, N.FLAME_F64))
 
 
+# ---- the launches that read updates and write no model: CPU tensors
+MEASURED_KEYS = [("a", torch.float32, 1), ("b", torch.float32, 1025), ("h", torch.bfloat16, 7), ("nbt", torch.int64, 1)]
+
+
+def _updates(tr, n, keys=MEASURED_KEYS, lacking=()):
+    """``n`` updates over ``keys``; ``lacking``: (update index, key name) pairs left out."""
+    return [{nm: tr.t(f"u{i}.{nm}", torch.zeros(numel, dtype=dt)) for nm, dt, numel in keys if (i, nm) not in lacking}
+            for i in range(n)]
+
+
+def _tiny(n, dt=torch.float32):
+    """``n`` one-element updates (unlabelled: a case that raises before it reads them)."""
+    return [{"w": torch.zeros(1, dtype=dt)} for _ in range(n)]
+
+
+INT_KEY = [("nbt", torch.int64, 1)]
+
+case("update_stats")(lambda tr: engine.update_stats(_updates(tr, 3), device=CPU))
+case("update_stats_ragged")(lambda tr: engine.update_stats(_updates(tr, 3, lacking=[(1, "b")]), device=CPU))
+case("update_stats_f64")(lambda tr: engine.update_stats(_updates(tr, 2, [("d", torch.float64, 3)]), device=CPU))
+case("update_stats_no_float_key")(lambda tr: engine.update_stats(_updates(tr, 3, INT_KEY), device=CPU))
+case("update_stats_no_updates")(lambda tr: engine.update_stats([], device=CPU))
+
+case("update_gram")(lambda tr: engine.update_gram(_updates(tr, 3), device=CPU))
+case("update_gram_missing_key")(lambda tr: engine.update_gram(_updates(tr, 3, lacking=[(1, "b")]), device=CPU))
+case("update_gram_dtype_mismatch")(
+    lambda tr: engine.update_gram(_updates(tr, 2) + [{nm: torch.zeros(numel, dtype=torch.float16 if nm == "h" else dt)
+                                                      for nm, dt, numel in MEASURED_KEYS}], device=CPU))
+case("update_gram_shape_mismatch")(
+    lambda tr: engine.update_gram(_updates(tr, 2) + [{nm: torch.zeros(numel + (nm == "a"), dtype=dt)
+                                                      for nm, dt, numel in MEASURED_KEYS}], device=CPU))
+case("update_gram_over_capacity")(lambda tr: engine.update_gram(_tiny(1025), device=CPU))
+case("update_gram_no_float_key")(lambda tr: engine.update_gram(_updates(tr, 3, INT_KEY), device=CPU))
+case("update_gram_no_updates")(lambda tr: engine.update_gram([], device=CPU))
+
+TRIMMED_KEYS = [("a", torch.float32, 1), ("b", torch.float32, 1025), ("h", torch.float16, 7), ("nbt", torch.int64, 1)]
+
+
+def _trimmed(tr, n=5, k=2, keys=TRIMMED_KEYS, agg_keys=None, **kw):
+    agg = {nm: tr.t(f"agg.{nm}", torch.zeros(numel, dtype=dt)) for nm, dt, numel in agg_keys or keys}
+    with _patched(engine, reduce_=tr.reduce_):
+        engine.trimmed_mean(agg, _updates(tr, n, keys), k, device=CPU, **kw)
+
+
+case("trimmed_mean")(_trimmed)
+case("trimmed_mean_init_first")(lambda tr: _trimmed(tr, keys=TRIMMED_KEYS[:3], init_first=True))
+case("trimmed_mean_init_first_int_key")(lambda tr: _trimmed(tr, init_first=True))
+case("trimmed_mean_xcd", xcd=2)(_trimmed)
+case("trimmed_mean_k_over_capacity")(
+    lambda tr: engine.trimmed_mean({"w": torch.zeros(1)}, _tiny(2 * engine.trimmed_max_k() + 3),
+                                   engine.trimmed_max_k() + 1, device=CPU))
+case("trimmed_mean_too_few_updates")(lambda tr: _trimmed(tr, n=4))
+case("trimmed_mean_wrong_key_set")(lambda tr: _trimmed(tr, keys=TRIMMED_KEYS[1:], agg_keys=TRIMMED_KEYS))
+
+
 # ------------------------------------------------------------------ the test
 def _expected():
     with open(FIXTURE) as f:
@@ -397,9 +482,32 @@ def test_xcd_map_only_on_untiled_tables():
     assert {n for n, f in flag.items() if f} == {"reduce_f32_table_xcd", "reduce_scaled_f32_xcd"}
 
 
+def test_measuring_front_ends_share_one_output_block_and_one_scratch():
+    """Slot 0 first; a second client set's sums behind the first's, the counts behind all sums."""
+    for name, want in (("update_stats", [[0, 24]] * 2), ("update_stats_ragged", [[0, 40], [24, 64], [0, 40]]),
+                       ("update_gram", [[0, 72]] * 2)):
+        calls = _calls(run_case(name))
+        assert [[a["out"] for a in c[2][6:8]] for c in calls] == want and all(c[2][8] == "scratch" for c in calls)
+    assert [e[0] for e in run_case("update_stats_no_float_key")] == ["return"]
+    assert [e[0] for e in run_case("update_gram_no_updates")] == ["return"]
+
+
+def test_trimmed_mean_counter_goes_last_with_equal_rates():
+    trace = run_case("trimmed_mean")
+    assert [e[1] for e in _calls(trace)] == ["flame_agg_trimmed"] * 2 and trace[-1][0] == "reduce_"
+    assert trace[-1][1:] == [["agg.nbt"], [[f"u{i}.nbt" for i in range(5)]], [(1.0 / 5).hex()] * 5, {}]
+    flags = {n: [c[2][1] for c in _calls(run_case(n))] for n in ("trimmed_mean", "trimmed_mean_init_first",
+                                                               "trimmed_mean_xcd")}
+    assert flags == {"trimmed_mean": [0, 0], "trimmed_mean_init_first": [N.FLAME_AGG_INIT_FIRST] * 2,
+                     "trimmed_mean_xcd": [N.FLAME_AGG_XCD_MAP, 0]}
+
+
 def test_raising_cases_upload_nothing():
     for n in ("reduce_scaled_seg_rates_raises", "reduce_scaled_i64_raises", "fedopt_chain_int64",
               "fedopt_chain_open_last_step", "scale_add_int64_base", "scale_add_numel_mismatch",
-              "fedopt_adapt_f64_needs_raw_scalars", "fedopt_chain_f64_needs_raw_scalars"):
+              "fedopt_adapt_f64_needs_raw_scalars", "fedopt_chain_f64_needs_raw_scalars",
+              "update_gram_missing_key", "update_gram_dtype_mismatch", "update_gram_shape_mismatch",
+              "update_gram_over_capacity", "trimmed_mean_init_first_int_key", "trimmed_mean_k_over_capacity",
+              "trimmed_mean_too_few_updates", "trimmed_mean_wrong_key_set"):
         trace = run_case(n)
         assert [e[0] for e in trace] == ["raise"], n
