@@ -39,6 +39,7 @@ EXPORTS = (
     "flame_abi_version", "flame_last_error", "flame_chunk_elems", "flame_scale_add_chunk_elems",
     "flame_agg_reduce", "flame_agg_reduce_argmeta", "flame_agg_argmeta_max_bytes",
     "flame_update_stats", "flame_update_stats_scratch_bytes", "flame_agg_reduce_scaled",
+    "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
     "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
     "flame_hier_resident_per_cu", "flame_feddyn_round", "flame_elementwise", "flame_elementwise_segments", "flame_synth_fill",
@@ -85,6 +86,10 @@ def lib() -> ctypes.CDLL:
     L.flame_update_stats.argtypes = [ctypes.c_int, vp, i32, i64, vp, i32, vp, vp, vp, i64, vp]
     L.flame_update_stats_scratch_bytes.restype = i64
     L.flame_update_stats_scratch_bytes.argtypes = [i64, i32]
+    L.flame_update_dist.restype = ctypes.c_int
+    L.flame_update_dist.argtypes = [ctypes.c_int, vp, i32, i64, vp, i32, vp, vp, vp, i64, vp]
+    L.flame_update_dist_scratch_bytes.restype = i64
+    L.flame_update_dist_scratch_bytes.argtypes = [i64, i32]
     L.flame_update_gram.restype = ctypes.c_int
     L.flame_update_gram.argtypes = [ctypes.c_int, vp, i32, i64, vp, i32, vp, vp, vp, i64, vp]
     L.flame_update_gram_scratch_bytes.restype = i64

@@ -1008,27 +1008,33 @@ constexpr int kWaves = kBlock / 64;
 constexpr int64_t kChunkBytes = 4096;            // one chunk of every dtype (= FLAME_TILE_BYTES)
 static_assert(kWaves == 4, "the statistics kernels add four wave sums");
 
-template <int DT>
-__device__ __forceinline__ void stat_elem(typename Tr<DT>::T x, double& acc, unsigned& bad) {
+// CEN (flame_update_dist): the term is the square of x - z, one fp64 subtract of the widened
+// values, and stays 0 for a non-finite x whatever z is; a non-finite z propagates.  With z = +-0
+// the subtract returns x (or a zero), so every bit below is the statistics'.
+template <int DT, bool CEN>
+__device__ __forceinline__ void stat_elem(typename Tr<DT>::T x, typename Tr<DT>::T z, double& acc, unsigned& bad) {
     if constexpr (DT == FLAME_F64) {
         const bool nf = !__builtin_isfinite(x);
-        acc = __dadd_rn(acc, nf ? 0.0 : __dmul_rn(x, x));
+        const double d = CEN ? __dsub_rn(x, z) : x;
+        acc = __dadd_rn(acc, nf ? 0.0 : __dmul_rn(d, d));
         bad += nf;
     } else {
         const float f = Tr<DT>::ld(x);
         const bool nf = !__builtin_isfinite(f);
-        const double d = static_cast<double>(nf ? 0.0f : f);
+        double d = static_cast<double>(nf ? 0.0f : f);
+        if constexpr (CEN) d = nf ? 0.0 : __dsub_rn(d, static_cast<double>(Tr<DT>::ld(z)));
         acc = __builtin_fma(d, d, acc);      // d * d is exact in fp64: the same bits as multiply, then add
-        bad += nf;
+        bad += nf;                           // (CEN: d has up to 53 bits, the fma rounds once)
     }
 }
-template <int DT>
-__device__ __forceinline__ void stat_vec(const V16& v, double& acc, unsigned& bad) {
+template <int DT, bool CEN>
+__device__ __forceinline__ void stat_vec(const V16& v, const V16& zv, double& acc, unsigned& bad) {
     using T = typename Tr<DT>::T;
-    T x[Tr<DT>::EPT];
+    T x[Tr<DT>::EPT], z[Tr<DT>::EPT];
     unpack<T, Tr<DT>::EPT>(v, x);
+    unpack<T, Tr<DT>::EPT>(CEN ? zv : v, z);
 #pragma unroll
-    for (int j = 0; j < Tr<DT>::EPT; ++j) stat_elem<DT>(x[j], acc, bad);
+    for (int j = 0; j < Tr<DT>::EPT; ++j) stat_elem<DT, CEN>(x[j], z[j], acc, bad);
 }
 // lane 0 receives the wave's sum, always added in the same order
 __device__ __forceinline__ double wave_sum(double x) {
@@ -1039,8 +1045,10 @@ __device__ __forceinline__ double wave_sum(double x) {
 
 // One pass of a workgroup over its chunks [c0, c1) for NC clients (cfirst ..): per chunk the NC
 // clients' vectors are loaded together (on a tiled slab they are one contiguous NC x 4 KiB run),
-// CU chunks per step.  All bounds are workgroup-uniform.
-template <int DT, int NC, int CU>
+// CU chunks per step.  All bounds are workgroup-uniform.  CEN: the segment's centre (segs[s].in,
+// contiguous, numel elements) is read beside them, once per chunk and client group -- after the
+// first group out of L2, which a workgroup's kStatR x 4 KiB never leave between groups.
+template <int DT, int NC, int CU, bool CEN>
 __device__ __forceinline__ void stat_pass(const flame_segment* __restrict__ segs, int n_segs, int s0, int64_t c0,
                                           int64_t c1, const uint64_t* __restrict__ clients, int n_clients, int cfirst,
                                           double (&acc)[NC], unsigned (&bad)[NC]) {
@@ -1072,38 +1080,48 @@ __device__ __forceinline__ void stat_pass(const flame_segment* __restrict__ segs
         const char* q[NC];
 #pragma unroll
         for (int k = 0; k < NC; ++k) q[k] = reinterpret_cast<const char*>(cp[k]) + cl * step + loff;
+        // the centre's bytes for this lane: chunk cl of the segment is at zb + cl * 4 KiB
+        const char* const zb = CEN ? static_cast<const char*>(segs[s].in) + loff : nullptr;
         int64_t off = 0;
         for (; cl + CU <= clf; cl += CU, off += CU * step) {
-            V16 x[CU][NC];
+            V16 x[CU][NC], z[CU];
 #pragma unroll
-            for (int u = 0; u < CU; ++u)
+            for (int u = 0; u < CU; ++u) {
+                if constexpr (CEN) z[u] = ld_v(zb + (cl + u) * kChunkBytes);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) x[u][k] = ld_nt(q[k] + off + u * step);
+            }
 #pragma unroll
             for (int u = 0; u < CU; ++u)
 #pragma unroll
-                for (int k = 0; k < NC; ++k) stat_vec<DT>(x[u][k], acc[k], bad[k]);
+                for (int k = 0; k < NC; ++k) stat_vec<DT, CEN>(x[u][k], z[u], acc[k], bad[k]);
         }
         for (; cl < clf; ++cl, off += step) {
-            V16 x[NC];
+            V16 x[NC], z;
+            if constexpr (CEN) z = ld_v(zb + cl * kChunkBytes);
 #pragma unroll
             for (int k = 0; k < NC; ++k) x[k] = ld_nt(q[k] + off);
 #pragma unroll
-            for (int k = 0; k < NC; ++k) stat_vec<DT>(x[k], acc[k], bad[k]);
+            for (int k = 0; k < NC; ++k) stat_vec<DT, CEN>(x[k], z, acc[k], bad[k]);
         }
         for (; cl < cle; ++cl, off += step) {
             const int64_t e = cl * CE + lane_elem;
+            T z[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                z[j] = (CEN && e + j < numel) ? ld1(reinterpret_cast<const T*>(zb + cl * kChunkBytes) + j) : T();
 #pragma unroll
             for (int k = 0; k < NC; ++k)
 #pragma unroll
                 for (int j = 0; j < EPT; ++j)
-                    if (e + j < numel) stat_elem<DT>(ld1(reinterpret_cast<const T*>(q[k] + off) + j), acc[k], bad[k]);
+                    if (e + j < numel)
+                        stat_elem<DT, CEN>(ld1(reinterpret_cast<const T*>(q[k] + off) + j), z[j], acc[k], bad[k]);
         }
         chunk = end;
     }
 }
 
-template <int DT>
+template <int DT, bool CEN>
 __global__ __launch_bounds__(kBlock) void update_stats_kernel(const flame_segment* __restrict__ segs, int n_segs,
                                                               const uint64_t* __restrict__ clients, int n_clients,
                                                               int64_t n_chunks, int64_t n_wg,
@@ -1135,7 +1153,7 @@ __global__ __launch_bounds__(kBlock) void update_stats_kernel(const flame_segmen
                 unsigned bad[kStatCB];
 #pragma unroll
                 for (int k = 0; k < kStatCB; ++k) acc[k] = 0.0, bad[k] = 0;
-                stat_pass<DT, kStatCB, (kStatUnroll / kStatCB > 1 ? kStatUnroll / kStatCB : 1)>(
+                stat_pass<DT, kStatCB, (kStatUnroll / kStatCB > 1 ? kStatUnroll / kStatCB : 1), CEN>(
                     segs, n_segs, s0, c0, c1, clients, n_clients, cb + ci, acc, bad);
 #pragma unroll
                 for (int k = 0; k < kStatCB; ++k) commit(ci + k, cb + ci + k, acc[k], bad[k]);
@@ -1145,7 +1163,7 @@ __global__ __launch_bounds__(kBlock) void update_stats_kernel(const flame_segmen
         for (; ci < nb; ++ci) {         // the clients left over, one at a time
             double acc[1] = {0.0};
             unsigned bad[1] = {0};
-            stat_pass<DT, 1, kStatUnroll>(segs, n_segs, s0, c0, c1, clients, n_clients, cb + ci, acc, bad);
+            stat_pass<DT, 1, kStatUnroll, CEN>(segs, n_segs, s0, c0, c1, clients, n_clients, cb + ci, acc, bad);
             commit(ci, cb + ci, acc[0], bad[0]);
         }
         __syncthreads();
@@ -3496,10 +3514,11 @@ int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
     return (n_chunks + kStatR - 1) / kStatR * static_cast<int64_t>(n_clients) * static_cast<int64_t>(sizeof(double));
 }
 
-int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
-                       const void* const* clients, int32_t n_clients, double* sumsq, int64_t* nonfinite,
-                       void* scratch, int64_t scratch_bytes, void* stream) {
-    const char* const who = "flame_update_stats";
+// flame_update_stats and flame_update_dist are the two instantiations of one pass (CEN: with a
+// centre); they share every check, the scratch layout and the finish kernel.
+static int launch_stats(const char* who, bool cen, int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                        const void* const* clients, int32_t n_clients, double* sums, int64_t* nonfinite, void* scratch,
+                        int64_t scratch_bytes, void* stream) {
     if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
     if (int rc = check_chunks(n_chunks)) return rc;
     if (n_clients <= 0) return set_err(FLAME_EINVAL, "%s: n_clients <= 0", who);
@@ -3507,7 +3526,7 @@ int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int
     if (dtype == FLAME_I64 || dtype == FLAME_I32)
         return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
     if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
-    if (!sumsq || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
+    if (!sums || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
     const int64_t need = flame_update_stats_scratch_bytes(n_chunks, n_clients);
     if (!scratch || scratch_bytes < need)
         return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
@@ -3515,14 +3534,35 @@ int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t n_wg = (n_chunks + kStatR - 1) / kStatR;
     dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
-        hipLaunchKernelGGL((update_stats_kernel<decltype(dt)::value>), dim3(static_cast<unsigned>(n_wg)), dim3(kBlock), 0, st,
-                           segs, n_segs, reinterpret_cast<const uint64_t*>(clients), n_clients, n_chunks, n_wg,
+        constexpr int DT = decltype(dt)::value;
+        hipLaunchKernelGGL((cen ? update_stats_kernel<DT, true> : update_stats_kernel<DT, false>),
+                           dim3(static_cast<unsigned>(n_wg)), dim3(kBlock), 0, st, segs, n_segs,
+                           reinterpret_cast<const uint64_t*>(clients), n_clients, n_chunks, n_wg,
                            static_cast<double*>(scratch), reinterpret_cast<unsigned long long*>(nonfinite));
     });
     if (int rc = check_launch(who)) return rc;
     hipLaunchKernelGGL(update_stats_finish_kernel, dim3(static_cast<unsigned>(n_clients)), dim3(kBlock), 0, st,
-                       static_cast<const double*>(scratch), n_wg, sumsq);
+                       static_cast<const double*>(scratch), n_wg, sums);
     return check_launch(who);
+}
+
+int flame_update_stats(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                       const void* const* clients, int32_t n_clients, double* sumsq, int64_t* nonfinite,
+                       void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_stats("flame_update_stats", false, dtype, segs, n_segs, n_chunks, clients, n_clients, sumsq, nonfinite,
+                        scratch, scratch_bytes, stream);
+}
+
+// The distances to a centre (RFA): the same pass with segs[s].in read as the centre of segment s.
+int64_t flame_update_dist_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
+    return flame_update_stats_scratch_bytes(n_chunks, n_clients);
+}
+
+int flame_update_dist(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                      const void* const* clients, int32_t n_clients, double* dist2, int64_t* nonfinite,
+                      void* scratch, int64_t scratch_bytes, void* stream) {
+    return launch_stats("flame_update_dist", true, dtype, segs, n_segs, n_chunks, clients, n_clients, dist2, nonfinite,
+                        scratch, scratch_bytes, stream);
 }
 
 // The Gram stands outside the launch-branch table as the statistics do: one instantiation per dtype.

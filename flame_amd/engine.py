@@ -1149,7 +1149,7 @@ def _rows(ws, fkeys, numels, dts, device, keep, per_view=True):
     return rows
 
 
-def _float_items(ws, device, keep, uniform=None):
+def _float_items(ws, device, keep, uniform=None, inp=None):
     """The FLOAT keys of the updates ``ws`` as ``(dtype, client indices, Seg)`` items, one per key,
     for the launches that read updates and write no model.  Integer and bool tensors take no part;
     an unsupported float dtype raises (:func:`dtype_code`).  Slots of one UpdateSlab take
@@ -1158,7 +1158,11 @@ def _float_items(ws, device, keep, uniform=None):
     * ragged allowed (``uniform`` None, :func:`update_stats`): a ``(key, dtype)`` is measured over
       the updates that carry it, so the client indices may differ between items;
     * uniform required (``uniform`` names the launcher, :func:`update_gram`): every update carries
-      every float key in one dtype and shape (a distance between other updates means nothing)."""
+      every float key in one dtype and shape (a distance between other updates means nothing).
+
+    ``inp(key, dtype, shape)`` (:func:`update_dist`) gives each item's ``Seg.inp``: the address of the
+    tensor the kernel reads beside the updates of that key."""
+    inp = inp or (lambda k, dt, shape: 0)
     all_cis = tuple(range(len(ws)))
     w0 = ws[0]
     if getattr(w0, "slab", None) is not None:
@@ -1167,7 +1171,8 @@ def _float_items(ws, device, keep, uniform=None):
         dts = {k: weight_dtype(w0, k) for k in fkeys}
         rows = _rows(ws, fkeys, numels, dts, device, keep, per_view=False)
         if rows is not None:
-            return [(dts[k], all_cis, Seg(numels[k], clients=rows[k][0], tile_stride=rows[k][1])) for k in fkeys]
+            return [(dts[k], all_cis, Seg(numels[k], inp=inp(k, dts[k], logical_shape(w0, k)), clients=rows[k][0],
+                                          tile_stride=rows[k][1])) for k in fkeys]
     per = collections.OrderedDict()     # first-seen order.  ragged: (key, dtype) -> client indices;
     for ci, w in enumerate(ws):         # uniform: key -> (dtype, shape) of the update that brought it first
         for k in w.keys():
@@ -1193,7 +1198,7 @@ def _float_items(ws, device, keep, uniform=None):
     for k, dt, shape, cis in keyed:
         numel = math.prod(shape)
         row, tstride = _client_row([ws[ci][k] for ci in cis], _KeyLike(numel, dt), device, keep)
-        items.append((dt, cis, Seg(numel, clients=row, tile_stride=tstride)))
+        items.append((dt, cis, Seg(numel, inp=inp(k, dt, shape), clients=row, tile_stride=tstride)))
     return items
 
 
@@ -1261,6 +1266,51 @@ def update_stats(weights_list, device=None):
         sumsq[idx] += sq[o:o + len(cis)]
         nonfinite[idx] += nf[o:o + len(cis)]
     return sumsq, nonfinite
+
+
+def update_dist(weights_list, center, device=None):
+    """Per update: the squared distance of its finite float elements to ``center`` and the count of
+    its non-finite ones (kernel: flame_update_dist, the statistics pass with one fp64 subtract per
+    element; the Weiszfeld iterations of ``optimizer/rfa.py`` measure with it).  Returns
+    ``(dist2: np.float64[n], nonfinite: np.int64[n])`` in the order of ``weights_list``.
+
+    :func:`update_stats`' front end and ragged-key policy; ``center`` is a dict that must hold every
+    float key the updates carry, in that key's dtype and shape (ValueError naming the key
+    otherwise).  A centre tensor on the host or with strides is staged to the device first; a
+    misaligned one is read element by element, as misaligned updates are.  A non-finite update
+    element adds nothing and is counted; a non-finite centre element makes the distance of every
+    update that is finite there ``+inf`` or NaN and is not counted.  With an all-zero centre the
+    result is :func:`update_stats`' bit for bit.  The call ends with one device-to-host copy of 16
+    bytes per update, which waits for the stream: this is a synchronisation point."""
+    ws = list(weights_list)
+    n = len(ws)
+    dist2, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int64)
+    if n == 0:
+        return dist2, nonfinite
+    device = _hip_device(device, "update_dist", *ws)
+    keep = []
+
+    def centre(k, dt, shape):
+        if k not in center:
+            raise ValueError(f"flame_amd.update_dist: center lacks the float key {k!r} that an update carries")
+        z = center[k]
+        if z.dtype != dt or tuple(z.shape) != tuple(shape):
+            raise ValueError(f"flame_amd.update_dist: center holds {k!r} as {z.dtype} {tuple(z.shape)}, "
+                             f"an update as {dt} {tuple(shape)}")
+        z = _staged(z, device)
+        keep.append(z)
+        return z.data_ptr()
+
+    items = _float_items(ws, device, keep, inp=centre)
+    if not items:
+        return dist2, nonfinite
+    d2, nf, slots = _measure("flame_update_dist", items, device, keep, int)
+    d2 = d2.view(np.float64)
+    for cis, (o, _) in slots.items():
+        idx = np.asarray(cis, dtype=np.int64)
+        dist2[idx] += d2[o:o + len(cis)]
+        nonfinite[idx] += nf[o:o + len(cis)]
+    return dist2, nonfinite
 
 
 def gram_max_clients() -> int:

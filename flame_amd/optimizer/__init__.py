@@ -5,6 +5,7 @@ from .fedadam import FedAdam
 from .fedavg import FedAvg
 from .fedbuff import FedBuff
 from .feddyn import FedDyn
+from .fedgeomedian import FedGeoMedian
 from .fedgft import FedGFT
 from .fedkrum import FedKrum, FedMultiKrum
 from .fedopt import FedOPT
@@ -16,4 +17,4 @@ from .train_result import TrainResult
 
 __all__ = ["AbstractOptimizer", "FedAvg", "FedOPT", "FedAdam", "FedYogi", "FedAdaGrad", "FedBuff",
            "FedProx", "FedDyn", "FedGFT", "Scaffold", "TrainResult", "FedTrimmedMean", "FedMedian",
-           "FedMultiKrum", "FedKrum"]
+           "FedMultiKrum", "FedKrum", "FedGeoMedian"]

@@ -25,12 +25,12 @@ anything reads the result (``w[k]``, ``items()``, ``load_state_dict``, ``deepcop
 (a plain dict) lags until then: read the returned object, as flame's roles do.
 
 One selection stage (``FedAvg._select``) stands between the cache and the reduction, for this class,
-FedProx, FedGFT and the FedOPT family alike, and for every combination of the three opt-in kwargs
+FedProx, FedGFT and the FedOPT family alike, and for every combination of the four opt-in kwargs
 below.  It is a straight pipeline -- refuse, pop, measure, policy, select, rates:
 what the round refuses is refused with the cache still full; the entries are popped in
 ``cache.iterkeys()`` order; the updates are measured at most once; the ``nonfinite`` policy and the
-clip scales come from the sums of squares; krum selects among what is left; rates and scales are
-formed last.  With every kwarg at its default the stage is the reference's pop loop and nothing else.
+clip scales come from the sums of squares; krum selects among what is left, rfa weights it; rates and
+scales are formed last.  With every kwarg at its default the stage is the reference's pop loop and nothing else.
 What the kwargs refuse of each other, of ``defer=True`` and of the sharded wrapper is one table,
 ``flame_amd/optimizer/refusals.py``.
 
@@ -46,11 +46,16 @@ What the kwargs refuse of each other, of ``defer=True`` and of the sharded wrapp
   is the guard's sum of squares, so the guard costs no second pass.  Every update is scored on the
   host by its distances to its nearest neighbours and the selected ones are averaged with equal
   weights through the reduction above.
+* Geometric median (``rfa=3``, ``rfa_nu=1e-6``; ``rfa.py``): measured by ``engine.update_stats``, whose
+  sums of squares are the first squared distances (the centre starts at the unchanged model); each
+  further Weiszfeld iteration is one reduction into a scratch centre and one ``engine.update_dist``
+  (kernel ``flame_update_dist``).  Every eligible update is kept, with the final weights as its rate.
 """
 import collections
 import collections.abc
 import copy
 import logging
+import math
 import weakref
 
 import torch
@@ -58,6 +63,7 @@ import torch
 from .. import engine, metrics
 from . import guard, refusals
 from . import krum as krum_
+from . import rfa as rfa_
 from . import trim as trim_
 from .abstract import AbstractOptimizer
 from .fedbuff import _own_shm_views
@@ -146,7 +152,8 @@ class FedAvg(AbstractOptimizer):
     chain_defer = False        # FedOPT's deferred eager chain (an instance attribute there)
 
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
-                 clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
+                 clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None,
+                 rfa=None, rfa_nu=None):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
@@ -159,8 +166,11 @@ class FedAvg(AbstractOptimizer):
         self.update_stats = []     # the last do()'s UpdateRecords, in cache order (empty: nothing measured)
         self.trim_k = None         # the last trimmed do()'s k
         self.krum_records = []     # the last krum do()'s KrumRecords, in cache order
+        self.rfa, self.rfa_nu = rfa_.check_kwargs(rfa, rfa_nu)
+        self.rfa_records = []      # the last rfa do()'s RfaRecords, in cache order
+        self.rfa_trace = []        # ... and its (dist2, weights) per Weiszfeld iteration run, over the eligible updates
         # every kwarg is valid: now what they refuse of each other and of a deferred queue (FedAvg's or FedOPT's)
-        refusals.check(self, *[c for c in ("clip_threshold", "trim") if refusals.is_set(self, c)],
+        refusals.check(self, *[c for c in ("clip_threshold", "trim", "krum") if refusals.is_set(self, c)],
                        *(("defer",) if defer or self.chain_defer else ()))
 
     @property
@@ -183,7 +193,7 @@ class FedAvg(AbstractOptimizer):
         ``(entries, scales)``: ``[(weights, rate)]`` in cache order -- empty when nothing is left to
         aggregate, as for an empty cache -- and the clip scales, None unless some update is clipped
         (the plain reduction then runs)."""
-        if self.krum is None and self.trim is None and not self.guarded:
+        if self.krum is None and self.trim is None and self.rfa is None and not self.guarded:
             # the plain round: after popping, the item is removed from the cache (fedavg.py:80-82);
             # rate = count / total; nothing is measured or recorded
             return [(tres.weights, tres.count / total) for tres in map(cache.pop, list(cache.iterkeys()))], None
@@ -194,7 +204,7 @@ class FedAvg(AbstractOptimizer):
         if self.krum is not None:                                       # 3. measure once
             gram, nonfinite = engine.update_gram([t.weights for t in popped])
             sumsq = gram.diagonal()                                     # the guard's sums of squares: no second pass
-        elif self.guarded:
+        elif self.guarded or self.rfa is not None:                      # (rfa: its first squared distances too)
             sumsq, nonfinite = engine.update_stats([t.weights for t in popped])
         kept, scales = list(range(n)), [1.0] * n
         if self.guarded:                                                # 4. the nonfinite policy and the clip scales
@@ -221,6 +231,14 @@ class FedAvg(AbstractOptimizer):
             if kept:
                 krum_.save_metrics(self, self.krum_records, f)
             rates = [1.0 / len(chosen) for _ in chosen]                 # 6. ... and rates: equal weights
+        elif self.rfa is not None:                                      # 5. weigh: an update with a non-finite
+            chosen = [i for i in kept if nonfinite[i] == 0 and math.isfinite(sumsq[i])]    # element is never read
+            rates, dist2 = [], []
+            if chosen:
+                rates, dist2, self.rfa_trace = rfa_.iterate([popped[i].weights for i in chosen],
+                                                            [sumsq[i] for i in chosen], self.rfa, self.rfa_nu)
+            self.rfa_records = rfa_.records(ends, sumsq, nonfinite, chosen, dist2, rates)
+            rfa_.save_metrics(self, self.rfa_trace)                     # 6. rates: the final Weiszfeld weights
         else:
             chosen = kept if total != 0 else []
             if chosen and len(chosen) != n:
@@ -235,6 +253,7 @@ class FedAvg(AbstractOptimizer):
         assert base_weights is not None
         self.update_stats = []     # this call's records only (an empty round measures nothing)
         self.krum_records = []
+        self.rfa_records, self.rfa_trace = [], []
         if isinstance(base_weights, DeferredWeights):
             base_weights = base_weights.materialize()
         pend = self._deferred

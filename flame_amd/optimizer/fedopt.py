@@ -32,9 +32,9 @@ when anything reads the results (the returned mapping, ``current_weights``, ``m_
 ``v_t``, ``agg_weights``), bit-identical to a launch per call.  Until then the base dict
 lags, as ``FedAvg(defer=True)``'s does.  ``d_t`` is not kept across a deferred queue.
 
-The update guard and ``krum`` reach the fused round through FedAvg's one selection stage
+The update guard, ``krum`` and ``rfa`` reach the fused round through FedAvg's one selection stage
 (``FedAvg._select``: refuse, pop, measure, policy, select, rates), called once by ``_do_fused`` as
-``FedAvg.do`` calls it; what a krum round refuses is also checked in ``do()`` before the deferred
+``FedAvg.do`` calls it; what a krum or rfa round refuses is also checked in ``do()`` before the deferred
 chain is flushed.  A round with clip scales takes the split launch.  ``trim`` is refused.
 """
 import collections.abc
@@ -87,7 +87,7 @@ class FedOPT(FedAvg):
     max_chain_bytes = 16 << 30
 
     def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
-                 nonfinite: str = "keep", trim=None, krum=None, krum_select=None):
+                 nonfinite: str = "keep", trim=None, krum=None, krum_select=None, rfa=None, rfa_nu=None):
         self.trim = trim_.check_kwarg(trim)
         refusals.check(self, "fedopt")      # trim: before anything else of the constructor
         self._poisoned = None
@@ -97,7 +97,8 @@ class FedOPT(FedAvg):
         self._v = None
         self._agg = None
         self.chain_defer = defer        # before FedAvg's constructor, which checks what a deferred chain refuses
-        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, krum=krum, krum_select=krum_select)
+        super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, krum=krum, krum_select=krum_select,
+                         rfa=rfa, rfa_nu=rfa_nu)
         self.current_weights = None
         self._d_t = None
         self._prev_current = None
@@ -167,7 +168,8 @@ class FedOPT(FedAvg):
         self._check_poisoned()
         self.update_stats = []
         self.krum_records = []
-        if self.krum is not None and len(cache) > 0 and total != 0:
+        self.rfa_records, self.rfa_trace = [], []
+        if (self.krum is not None or self.rfa is not None) and len(cache) > 0 and total != 0:
             self._check_round(len(cache), kwargs)   # the sharded wrapper and an impossible round, before any pop
         if self.chain_defer and not kwargs.keys() & _SHARD_KWARGS:
             ch = self._chain

@@ -41,8 +41,8 @@ class FedProx(FedAvg):
     """FedProx class (server side = FedAvg)."""
 
     def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None,
-                 krum_select=None):
+                 krum_select=None, rfa=None, rfa_nu=None):
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim, krum=krum,
-                         krum_select=krum_select)
+                         krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu)
         self.mu = mu
         self.regularizer = FedProxRegularizer(self.mu)

@@ -1,8 +1,8 @@
-"""What the update guard, ``trim`` and ``krum`` refuse, stated once: ``(feature, context) -> why``.
+"""What the update guard, ``trim``, ``krum`` and ``rfa`` refuse, stated once: ``(feature, context) -> why``.
 
-A *feature* is ``"guard"`` (``clip_threshold`` / ``nonfinite``), ``"trim"`` or ``"krum"``; a *context*
+A *feature* is ``"guard"`` (``clip_threshold`` / ``nonfinite``), ``"trim"``, ``"krum"`` or ``"rfa"``; a *context*
 is what it meets: a deferred queue (``"defer"``: ``FedAvg(defer=True)`` or FedOPT's chain), another
-kwarg (``"clip_threshold"``, ``"trim"``), the FedOPT family (``"fedopt"``), the sharded wrapper at its
+kwarg (``"clip_threshold"``, ``"trim"``, ``"krum"``), the FedOPT family (``"fedopt"``), the sharded wrapper at its
 construction (``"shard"``) or the key groups it passes to ``do()`` (``"key_groups"``).  Constructors
 set their attributes first and then call :func:`check` once; the order of the table is the order in
 which a constructor that meets several contexts reports them.  Every refusal is a
@@ -10,7 +10,8 @@ NotImplementedError; a bad value is a ValueError / TypeError from the kwarg's ow
 """
 NAME = {"guard": "clip_threshold / nonfinite (the server-side update guard) are",
         "trim": "trim (coordinate-wise trimmed-mean / median aggregation) is",
-        "krum": "krum (Krum / Multi-Krum aggregation) is"}
+        "krum": "krum (Krum / Multi-Krum aggregation) is",
+        "rfa": "rfa (geometric-median aggregation, RFA) is"}
 
 # (feature, context) -> (who refuses, ``{cls}`` the optimizer's class; why)
 TABLE = {
@@ -33,6 +34,16 @@ TABLE = {
     ("trim", "shard"): ("ShardedOptimizer", "the selection kernel takes no key groups yet (a follow-up)"),
     ("krum", "shard"): ("ShardedOptimizer", "each rank's partial Gram matrix would need an all-reduce before the "
                         "selection (a follow-up)"),
+    ("rfa", "defer"): ("{cls}(defer=True)", "a Weiszfeld iteration needs the round's other updates at once; use "
+                       "defer=False"),
+    ("rfa", "trim"): ("{cls}(trim=...)", "two robust rules in one round have no stated meaning; choose trim or rfa"),
+    ("rfa", "krum"): ("{cls}(krum=...)", "two robust rules in one round have no stated meaning; choose krum or rfa"),
+    ("rfa", "clip_threshold"): ("{cls}(clip_threshold=...)", "the distance kernel reads no per-client scale, so a "
+                                "clipped update would be measured unclipped (a follow-up); use nonfinite= alone with rfa"),
+    ("rfa", "key_groups"): ("ShardedOptimizer", "each rank holds a slice of every update; its partial distances would "
+                            "need an all-reduce of n doubles between measure and weights (a follow-up)"),
+    ("rfa", "shard"): ("ShardedOptimizer", "each rank's partial distances would need an all-reduce of n doubles "
+                       "between measure and weights (a follow-up)"),
 }
 
 

@@ -600,7 +600,7 @@ class ShardedOptimizer:
     def __init__(self, inner, group=None, device: Optional[torch.device] = None, accumulate_only: bool = False,
                  *, waves: Optional[bool] = None, fracs=DEFAULT_FRACS, align: int = ALIGN_ELEMS,
                  plan: Optional[ShardPlan] = None, gather: bool = True):
-        refusals.check(inner, "shard")      # the update guard, trim and krum: each rank sees only its slices
+        refusals.check(inner, "shard")      # the update guard, trim, krum and rfa: each rank sees only its slices
         self.inner = inner
         # gather=False (FedAvg / FedProx): no all-gathers -- each rank's base_weights is current on its
         # owned ranges (and the replicated tails) only, one launch over them; for a caller whose next

@@ -31,6 +31,8 @@
  *                               scaffold.py:141-150, feddyn.py:90-113,125-139
  *   flame_update_stats          privacy/differential_privacy.py:68-76 (the update's total norm), as
  *                               per-update sums of squares and non-finite counts on the aggregator
+ *   flame_update_dist           (no reference counterpart: squared distances to a centre for the
+ *                               geometric median of Pillutla et al., IEEE TSP 2022, on the same pass)
  *   flame_agg_reduce_scaled     privacy/differential_privacy.py:79-82 (torch.mul(d_w, scale)) followed
  *                               by optimizer/fedavg.py:93-104, in one pass
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
@@ -196,6 +198,38 @@ int flame_update_stats(int dtype, const flame_segment *segs, int32_t n_segs, int
                        const void *const *clients, int32_t n_clients, double *sumsq, int64_t *nonfinite,
                        void *scratch, int64_t scratch_bytes, void *stream);
 int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients);
+
+/*
+ * Squared distances of a round's updates to a centre: what the smoothed Weiszfeld iterations of
+ * the geometric median (RFA: Pillutla, Kakade, Harchaoui, "Robust Aggregation for Federated
+ * Learning", IEEE Transactions on Signal Processing 70, 2022) need of the device.  flame has no
+ * counterpart file.  It is flame_update_stats' pass with one subtraction per element.
+ *   segs, clients : the tables flame_update_stats takes; besides numel, chunk_begin, flags and
+ *                   client_tile_stride, each segment's `in` is read: the centre z of that segment,
+ *                   numel contiguous elements of the segment's dtype.  FLAME_SEG_UNALIGNED on a
+ *                   segment: its client views AND its centre are read element by element;
+ *                   otherwise `in` is 16-byte aligned.
+ *   dist2         : device double [n_clients];  dist2[i] += sum over every element e of every segment
+ *                   of t(e):  t = 0 when x_i[e] is NaN or +-inf (whatever z[e] is); otherwise
+ *                   d = fp64(x_i[e]) - fp64(z[e]) (one IEEE fp64 subtract), t = d * d, squared and
+ *                   added as flame_update_stats does for the dtype (f32 / bf16 / f16: one fma;
+ *                   f64: the square rounds, then the add).  A non-finite z[e] propagates by IEEE
+ *                   arithmetic: dist2[i] becomes +inf or NaN.
+ *   nonfinite     : device int64 [n_clients];  nonfinite[i] += number of NaN / +-inf elements of
+ *                   x_i (non-finite centre elements are not counted).
+ *   scratch       : device buffer of >= flame_update_dist_scratch_bytes(n_chunks, n_clients) bytes
+ *                   (scratch_bytes: its size), overwritten.
+ * With an all-zero centre (+0 or -0) dist2 is flame_update_stats' sumsq bit for bit and nonfinite
+ * is equal: the two are one kernel template.  Both outputs are accumulated into: zero them, then
+ * launch once per float dtype of a model on one stream.  No floating-point atomics: partial sums
+ * are combined in a fixed order, so the same launch on the same data gives the same bits.  dtype
+ * FLAME_F32, FLAME_BF16, FLAME_F16 or FLAME_F64 (integer dtypes: FLAME_ENOTSUP); n_clients >= 1,
+ * no upper limit.  Not a launch branch of flame_launch_branches().
+ */
+int flame_update_dist(int dtype, const flame_segment *segs, int32_t n_segs, int64_t n_chunks,
+                      const void *const *clients, int32_t n_clients, double *dist2, int64_t *nonfinite,
+                      void *scratch, int64_t scratch_bytes, void *stream);
+int64_t flame_update_dist_scratch_bytes(int64_t n_chunks, int32_t n_clients);
 
 /*
  * Pairwise Gram matrix of a round's updates: what Krum / Multi-Krum (Blanchard, El Mhamdi,
