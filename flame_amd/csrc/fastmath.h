@@ -8,7 +8,8 @@
 // caller takes the general sequence for a lane where any operand is not admitted.
 // tools/fp_probe.py checks this on the MI355X: exhaustively for sqrt_rn (every admitted x, and
 // every v below 2^-96 through sqrt(v) + tau) and rcp_rn (every admitted b), and on counter-drawn
-// admitted pairs for div_rn.
+// admitted pairs for div_rn.  tests/test_gpu_fedopt_sweep{16,32}.py run the shipped kernels that
+// call these over every 16-bit operand and over stratified fp32 / fp64 grids.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -355,9 +355,12 @@ __device__ __forceinline__ uint32_t pk_h2(f2 x) {
 // torch.sign of an fp16 pair as FedYogi's t * sign(x) uses it: +-1 for a nonzero x, +0 for +-0.
 // x + 0 turns -0 into +0; x * 65504 * 65504 carries the smallest subnormal (2^-24) past 1 and
 // overflows the rest to inf; the clamp to [-1, 1] keeps +-1 / +0.  A NaN x clamps to +1 (minNum),
-// not to torch's 0 -- but a NaN x = v - d^2 means v or d^2 is a NaN (t * sign is then NaN either
-// way) or v = d^2 = +inf (t = inf: inf * 0 and inf - inf * 1 are both NaN), so v's new value is a
-// NaN on both ways.
+// not to torch's 0.  With torch's 0 v's new value is always a NaN there: a NaN x = v - d^2 means v
+// or d^2 is a NaN (t * sign is then NaN either way) or v = d^2 = +inf, where t = (1 - beta_2) * inf
+// is a NaN or +-inf and t * 0 a NaN.  With +1 it is v - t: a NaN too for t = NaN or +inf, but +inf
+// for t = -inf, which a beta_2 above 1 gives (tests/test_gpu_fedopt_sweep16.py found it).  So this
+// is torch's result only while 1 - beta_2 >= 0: fedopt_chain_kernel keeps FedYogi off the packed
+// body otherwise.
 __device__ __forceinline__ h2 sign_h2(h2 x) {
     const h2 z = x + h2{0, 0};
     const h2 big = (z * h2{65504, 65504}) * h2{65504, 65504};
@@ -1962,7 +1965,7 @@ __device__ __forceinline__ void fedopt_chain_body_f16(const flame_segment& sg, i
                 vn = h2_of(smul_h2(b2, v[p])) + h2_of(smul_h2(omb2, u_of(d2)));
             } else if constexpr (VARIANT == FLAME_FEDYOGI) {
                 const h2 t = h2_of(smul_h2(omb2, u_of(d2)));
-                vn = vo - t * sign_h2(vo - d2);      // t * (+-1 or +0) is exact
+                vn = vo - t * sign_h2(vo - d2);      // t * (+-1 or +0) is exact (omb2 >= 0, see sign_h2)
             } else {
                 vn = vo + d2;
             }
@@ -2069,7 +2072,11 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel(const flame_segmen
     if (e0 >= sg.numel) return;
     const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
     const int64_t coff = client_offset<DT>(sg, chunk);
-    if (c0 + chunk_elems<DT>() <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {   // workgroup-uniform
+    bool full = c0 + chunk_elems<DT>() <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED);   // workgroup-uniform
+    // the packed fp16 body's FedYogi sign is torch's only while 1 - beta_2 >= 0 (sign_h2): a beta_2
+    // above 1 takes the per-element body for every chunk (a kernel argument: uniform)
+    if constexpr (DT == FLAME_F16 && kF16Native && VARIANT == FLAME_FEDYOGI) full &= !(omb2 < 0.f);
+    if (full) {
         if constexpr (DT == FLAME_F16 && kF16Native)
             fedopt_chain_body_f16<VARIANT, CU>(sg, e0, cp, coff, n_clients, r32, step_end, flags, b1, omb1, b2, omb2,
                                                eta, tau);

@@ -2,8 +2,9 @@
 long eager run in which weights stop moving -- a client average that stays put lets the current
 weight converge to it, d becomes exactly 0 and m decays by beta_1 per step, in bf16 down through
 [2^-133, 2^-85], the range the fp32 step's admission sends to the general divide.  The bf16 step
-now keeps those lanes on v_rcp_f32 (tools/fp_probe.py: equal under the bf16 rounding on every
-bf16 numerator but NaN), fp16's m never gets there (its smallest nonzero value is 2^-24).
+now keeps those lanes on v_rcp_f32 (tests/test_gpu_fedopt_sweep16.py's quotient sweep: equal under
+the bf16 rounding on every bf16 numerator but NaN, through the shipped kernels), fp16's m never
+gets there (its smallest nonzero value is 2^-24).
 
 Every arrival's result, m_t and v_t are compared BITWISE with the reference's own op sequence
 (OracleFedOPT: fedopt.py:58-129 as torch-CPU ops in the dtype, each op rounded to it), every

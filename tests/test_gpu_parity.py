@@ -699,8 +699,9 @@ def test_fedopt_fused_reduced_precision_vs_reference_ops(sort, dtype):
     """bf16 / fp16 FedOPT keys take the fused kernel; compare with the reference's own torch-CPU
     op sequence (oracle._adapt_torch) over 3 rounds: the reduction is bitwise, and so is the
     adaptive step -- current, m and v.  (torch-CPU's fp32 sqrt is not always correctly rounded,
-    but an fp32 root within an ulp rounds to the same bf16 / fp16 value: tools/fp_probe.py checks
-    that exhaustively for the hardware root)"""
+    but an fp32 root within an ulp rounds to the same bf16 / fp16 value:
+    tests/test_gpu_fedopt_sweep16.py runs every 16-bit v through the shipped kernels' root, and
+    tests/test_fedopt_sweep_ref.py holds torch-CPU's side to a float64 reference)"""
     O = _oracle()
     g = torch.Generator().manual_seed(17)
     P, n = 20_011, 8
