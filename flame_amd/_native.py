@@ -43,6 +43,7 @@ EXPORTS = (
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
     "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
     "flame_hier_resident_per_cu", "flame_feddyn_round", "flame_elementwise", "flame_elementwise_segments", "flame_synth_fill",
+    "flame_noise_fill",
     "flame_host_register", "flame_host_unregister", "flame_host_device_pointer",
     "flame_slab_write", "flame_slab_write_2d",
     "flame_launch_branches", "flame_launch_branch_name", "flame_launch_branch_count",
@@ -131,6 +132,8 @@ def lib() -> ctypes.CDLL:
     L.flame_elementwise_segments.argtypes = [vp, i32, vp, i32, vp, i32, i64, vp]
     L.flame_synth_fill.restype = ctypes.c_int
     L.flame_synth_fill.argtypes = [ctypes.c_int, vp, i64, u64, u64, i64, f32, vp]
+    L.flame_noise_fill.restype = ctypes.c_int
+    L.flame_noise_fill.argtypes = [ctypes.c_int, vp, i32, i64, vp, vp, u64, u32, f64, vp]
     L.flame_host_register.restype = ctypes.c_int
     L.flame_host_register.argtypes = [vp, u64]
     L.flame_host_unregister.restype = ctypes.c_int

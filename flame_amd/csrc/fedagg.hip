@@ -2807,6 +2807,161 @@ __global__ __launch_bounds__(kEwBlock) void synth_kernel(void* out, int64_t nume
     }
 }
 
+// ---------------------------------------------------------------- server-side Gaussian noise
+// flame's DifferentialPrivacy adds torch.normal(0, noise_factor) to every element of a trainer's
+// delta (privacy/differential_privacy.py:55-61); here the aggregator draws the noise of the whole
+// round once ("the noise contract").  The generator is a pure function of
+// (seed, round, stream, index): Philox4x32-10 (Salmon et al., SC'11) gives four words per block b,
+// counter (b lo, b hi, stream, round), key (seed lo, seed hi); (x0, x1) and (x2, x3) each give two
+// unit normals by Box-Muller.  Every floating-point step is ONE fp32 operation written as an
+// intrinsic -- no fma, no hardware log / sin / cos, no device libm -- in the order
+// tests/noise_ref.py restates them in numpy float32, so the two agree bit for bit.  (The root is
+// __builtin_sqrtf, which is correctly rounded; the __fsqrt_rn builtin lowers to the 1-ulp v_sqrt_f32.)
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+        const uint32_t n0 = static_cast<uint32_t>(p1 >> 32) ^ c[1] ^ k0;
+        const uint32_t n2 = static_cast<uint32_t>(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0; c[1] = static_cast<uint32_t>(p1); c[2] = n2; c[3] = static_cast<uint32_t>(p0);
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// -2 ln u for u in (0, 1]: u = 2^e m with m in (sqrt(1/2), sqrt 2], ln m = 2 atanh(s), s = f / (2 + f),
+// f = m - 1 (exact), the series to s^11; e ln 2 with ln 2 split so that e * HI is exact
+__device__ __forceinline__ float noise_neg2ln(float u) {
+    const uint32_t bits = __float_as_uint(u);
+    int e = static_cast<int>(bits >> 23) - 127;
+    float m = __uint_as_float((bits & 0x7FFFFFu) | 0x3F800000u);
+    if (m > 0x1.6a09e6p+0f) { m = __fmul_rn(m, 0.5f); e += 1; }
+    const float f = __fadd_rn(m, -1.0f);
+    const float s = __fdiv_rn(f, __fadd_rn(f, 2.0f));
+    const float z = __fmul_rn(s, s);
+    float p = 0x1.745d18p-4f;
+    p = __fadd_rn(__fmul_rn(p, z), 0x1.c71c72p-4f);
+    p = __fadd_rn(__fmul_rn(p, z), 0x1.24924ap-3f);
+    p = __fadd_rn(__fmul_rn(p, z), 0x1.99999ap-3f);
+    p = __fadd_rn(__fmul_rn(p, z), 0x1.555556p-2f);
+    p = __fmul_rn(p, z);
+    const float t = __fadd_rn(s, s);
+    const float lg = __fadd_rn(t, __fmul_rn(t, p));
+    const float ef = static_cast<float>(e);
+    const float ln = __fadd_rn(__fmul_rn(ef, 0x1.62e4p-1f), __fadd_rn(lg, __fmul_rn(ef, 0x1.7f7d1cp-20f)));
+    return __fmul_rn(-2.0f, ln);
+}
+
+// (cos, sin) of 2 pi k / 2^24: the octant from the integer, the angle inside it mirrored onto
+// [0, pi/4], the Taylor polynomials to phi^9 / phi^10 there
+__device__ __forceinline__ void noise_sincos(uint32_t k, float& co, float& si) {
+    const uint32_t o = k >> 21, j = k & 0x1FFFFFu;
+    const uint32_t jj = (o & 1u) ? 0x200000u - j : j;
+    const float phi = __fmul_rn(static_cast<float>(jj), 0x1.921fb6p-22f);
+    const float z = __fmul_rn(phi, phi);
+    float ps = 0x1.71de3ap-19f;
+    ps = __fadd_rn(__fmul_rn(ps, z), -0x1.a01a02p-13f);
+    ps = __fadd_rn(__fmul_rn(ps, z), 0x1.111112p-7f);
+    ps = __fadd_rn(__fmul_rn(ps, z), -0x1.555556p-3f);
+    const float s = __fadd_rn(phi, __fmul_rn(__fmul_rn(phi, z), ps));
+    float pc = -0x1.27e4fcp-22f;
+    pc = __fadd_rn(__fmul_rn(pc, z), 0x1.a01a02p-16f);
+    pc = __fadd_rn(__fmul_rn(pc, z), -0x1.6c16c2p-10f);
+    pc = __fadd_rn(__fmul_rn(pc, z), 0x1.555556p-5f);
+    pc = __fadd_rn(__fmul_rn(pc, z), -0x1p-1f);
+    const float c = __fadd_rn(1.0f, __fmul_rn(z, pc));
+    const bool swap = ((o + 1u) >> 1) & 1u, cneg = ((o + 2u) >> 2) & 1u, sneg = o >> 2;
+    const float c0 = swap ? s : c, s0 = swap ? c : s;
+    co = __uint_as_float(__float_as_uint(c0) ^ (cneg ? 0x80000000u : 0u));
+    si = __uint_as_float(__float_as_uint(s0) ^ (sneg ? 0x80000000u : 0u));
+}
+
+// two unit normals from two words: u1 = RNE_f32(2 xu + 1) * 2^-33 in (0, 1] (the 33-bit odd integer as
+// an exact 16-bit high part and an exact 17-bit low part: the one rounding is the add's), k = xk >> 8
+__device__ __forceinline__ void noise_pair(uint32_t xu, uint32_t xk, float& ze, float& zo) {
+    const uint64_t v = 2ull * xu + 1ull;
+    const float hi = static_cast<float>(static_cast<uint32_t>(v >> 17));
+    const float lo = static_cast<float>(static_cast<uint32_t>(v & 0x1FFFFu));
+    const float u = __fmul_rn(__fadd_rn(__fmul_rn(hi, 131072.0f), lo), 0x1p-33f);
+    const float r = __builtin_sqrtf(noise_neg2ln(u));
+    float co, si;
+    noise_sincos(xk >> 8, co, si);
+    ze = __fmul_rn(r, co);
+    zo = __fmul_rn(r, si);
+}
+
+// the four unit normals of block b of key `stream` in round `round`
+__device__ __forceinline__ void noise_block(uint32_t k0, uint32_t k1, uint32_t round, uint32_t stream, uint64_t b,
+                                            float (&z)[4]) {
+    uint32_t c[4] = {static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32), stream, round};
+    philox4x32_10(c, k0, k1);
+    noise_pair(c[0], c[1], z[0], z[1]);
+    noise_pair(c[2], c[3], z[2], z[3]);
+}
+
+// noise[e] = round_dtype(z * std): f32 / bf16 / f16 one fp32 product by the fp32 std (16-bit: then one
+// RNE rounding); f64 widens z and takes one fp64 product by the double
+template <int DT>
+__device__ __forceinline__ typename Tr<DT>::T noise_value(float z, float std32, double std64) {
+    if constexpr (DT == FLAME_F64) return __dmul_rn(static_cast<double>(z), std64);
+    else if constexpr (DT == FLAME_F32) return __fmul_rn(z, std32);
+    else if constexpr (DT == FLAME_BF16) return f32_to_bf16_exact(bf16_round(__fmul_rn(z, std32)));
+    else return f32_to_f16_bits(__fmul_rn(z, std32));
+}
+
+// Write-only fill over a segment table (only out, numel, chunk_begin and flags are read); element e
+// of segment s is the generator's value at global index starts[s] + e of key streams[s].  A lane
+// covers EPT consecutive elements; an aligned segment with starts % 4 == 0 stores them as one
+// 16-byte vector (whole Philox blocks), anything else element by element.  The value of an element
+// depends on (seed, round, stream, index) alone, never on the launch geometry.
+template <int DT>
+__global__ __launch_bounds__(kBlock) void noise_fill_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                          const uint32_t* __restrict__ streams,
+                                                          const int64_t* __restrict__ starts, uint32_t k0, uint32_t k1,
+                                                          uint32_t round, float std32, double std64) {
+    using T = typename Tr<DT>::T;
+    constexpr int EPT = Tr<DT>::EPT;
+    const int64_t chunk = blockIdx.x;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;
+    const uint32_t stream = streams[s];
+    const uint64_t start = static_cast<uint64_t>(starts[s]);
+    const uint64_t g0 = start + static_cast<uint64_t>(e0);
+    T* op = reinterpret_cast<T*>(sg.out) + e0;
+    float z[4];
+    if ((e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED) && !(start & 3u)) {
+        T x[EPT];
+        if constexpr (EPT >= 4) {
+#pragma unroll
+            for (int q = 0; q < EPT / 4; ++q) {
+                noise_block(k0, k1, round, stream, (g0 >> 2) + q, z);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[4 * q + j] = noise_value<DT>(z[j], std32, std64);
+            }
+        } else {            // f64: half a block per lane
+            noise_block(k0, k1, round, stream, g0 >> 2, z);
+            const bool up = g0 & 2u;
+            x[0] = noise_value<DT>(up ? z[2] : z[0], std32, std64);
+            x[1] = noise_value<DT>(up ? z[3] : z[1], std32, std64);
+        }
+        st_v(op, pack<T, EPT>(x));
+        return;
+    }
+    uint64_t have = ~0ull;
+    for (int j = 0; j < EPT; ++j) {
+        if (e0 + j >= sg.numel) break;
+        const uint64_t g = g0 + static_cast<uint64_t>(j);
+        if ((g >> 2) != have) {
+            have = g >> 2;
+            noise_block(k0, k1, round, stream, have, z);
+        }
+        const uint32_t l = static_cast<uint32_t>(g) & 3u;
+        const float zl = l == 0 ? z[0] : l == 1 ? z[1] : l == 2 ? z[2] : z[3];
+        st1(op + j, noise_value<DT>(zl, std32, std64));
+    }
+}
+
 // ---------------------------------------------------------------- slab insert (tiling copy)
 // The role's `self.cache[end] = tres` (syncfl/top_aggregator.py:154-156) lands one update
 // in a slab slot: each key's contiguous bytes are cut into 4 KiB tiles (one reduction
@@ -3848,6 +4003,34 @@ int flame_synth_fill(int dtype, void* out, int64_t numel, uint64_t seed, uint64_
     });
     if (!known) return set_err(FLAME_ENOTSUP, "flame_synth_fill: dtype %d not supported", dtype);
     return check_launch("flame_synth_fill");
+}
+
+// Outside the launch-branch table, as flame_update_stats and flame_synth_fill are: one instantiation
+// per dtype, nothing to pick.
+int flame_noise_fill(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks, const uint32_t* streams,
+                     const int64_t* starts, uint64_t seed, uint32_t round, double std, void* stream) {
+    const char* const who = "flame_noise_fill";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll)
+        return set_err(FLAME_EINVAL, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: float dtypes only (integer and bool tensors get no noise), got dtype %d", who, dtype);
+    if (dtype != FLAME_F32 && dtype != FLAME_BF16 && dtype != FLAME_F16 && dtype != FLAME_F64)
+        return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (!(std >= 0.0) || std > 1.7976931348623157e308)
+        return set_err(FLAME_EINVAL, "%s: std must be a finite number >= 0, got %g", who, std);
+    if (dtype != FLAME_F64 && std >= 0x1.ffffffp127)       // FLT_MAX + half an ulp: rounds to an infinite fp32
+        return set_err(FLAME_EINVAL, "%s: std %g rounds to an infinite fp32", who, std);
+    if (!streams || !starts) return set_err(FLAME_EINVAL, "%s: the streams / starts array is NULL", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+    const float std32 = dtype == FLAME_F64 ? 0.f : static_cast<float>(std);
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((noise_fill_kernel<decltype(dt)::value>), grid, block, 0, st, segs, n_segs, streams, starts, k0,
+                           k1, round, std32, std);
+    });
+    return check_launch(who);
 }
 
 static int ew_check(const flame_ew_op* prog, int32_t n_ops, void* const* bufs, int32_t n_bufs, int64_t numel);

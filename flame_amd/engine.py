@@ -4,8 +4,8 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``synth_fill_``) need the native library and a
-HIP device.
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``synth_fill_``) need the native
+library and a HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
 segments, a metadata block from one of the plan functions (all built on ``_Block``), then
@@ -994,6 +994,94 @@ def synth_fill_(out: torch.Tensor, seed: int, stream_id: int, start: int, sigma:
     assert out.is_cuda and out.is_contiguous()
     N.check(N.lib().flame_synth_fill(dtype_code(out.dtype), out.data_ptr(), out.numel(), seed, stream_id,
                                      start, float(scale_for_sigma(sigma)), _stream_ptr(out.device)))
+
+
+# ------------------------------------------------------------------ server-side Gaussian noise
+def plan_noise(code: int, segs: Sequence[Seg], streams: Sequence[int], starts: Sequence[int],
+               chunk: Optional[int] = None):
+    """[segments (10 words)] [streams u32 S] [starts i64 S] -> (meta, n_chunks, byte offsets): the
+    metadata block of one flame_noise_fill launch (no GPU needed).  The two arrays live in device
+    memory, where the library cannot look before it launches: a negative start or a stream outside
+    32 bits is refused here."""
+    S = len(segs)
+    if S == 0:
+        raise ValueError("empty segment list")
+    if len(streams) != S or len(starts) != S:
+        raise ValueError("noise: one stream and one start per segment")
+    for st in streams:
+        if isinstance(st, bool) or not isinstance(st, (int, np.integer)) or not 0 <= int(st) < 1 << 32:
+            raise ValueError(f"noise: a stream is the key's position in the model, an int in [0, 2^32), not {st!r}")
+    for st in starts:
+        if isinstance(st, bool) or not isinstance(st, (int, np.integer)) or not 0 <= int(st) < 1 << 62:
+            raise ValueError(f"noise: a start is an element index >= 0 (below 2^62), not {st!r}")
+    b = _Block(chunk or chunk_elems(code))
+    head = np.zeros((S, SEG_WORDS), dtype=np.uint64)
+    for i, s in enumerate(segs):
+        head[i, 0] = s.out
+        head[i, 6:9] = (s.numel, b.chunk_begin(s.numel), b.unaligned((s.out,)))
+    b.add("segs", head)
+    b.add("streams", np.asarray([int(x) for x in streams], dtype=np.uint32))
+    b.add("starts", np.asarray([int(x) for x in starts], dtype=np.int64))
+    meta, n_chunks = b.finish()
+    return meta, n_chunks, b.offs
+
+
+def check_noise_args(seed, rnd, std):
+    """``(seed, round mod 2^32, std)`` as flame_noise_fill takes them; a bad value raises before any launch."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"noise: seed must be an int in [0, 2^64), not {seed!r}")
+    if isinstance(rnd, bool) or not isinstance(rnd, (int, np.integer)) or int(rnd) < 0:
+        raise ValueError(f"noise: round must be an int >= 0, not {rnd!r}")
+    std = float(std)
+    if not (std >= 0.0) or math.isinf(std):
+        raise ValueError(f"noise: std must be a finite number >= 0, not {std!r}")
+    return int(seed), int(rnd) & 0xFFFFFFFF, std
+
+
+def noise_fill_(outs: List[torch.Tensor], streams: Sequence[int], starts: Sequence[int], seed: int, rnd: int,
+                std: float) -> None:
+    """outs[s][e] = round_dtype(z(seed, rnd, streams[s], starts[s] + e) * std), written in place
+    (kernel: flame_noise_fill; Philox4x32-10 + Box-Muller, DESIGN.md §2 "the noise contract").  ``outs``
+    are contiguous device tensors of f32 / bf16 / f16 / f64 (a view one element off alignment is
+    written element by element); one launch per dtype on torch's current stream."""
+    if not outs:
+        return
+    seed, rnd, std = check_noise_args(seed, rnd, std)
+    device = outs[0].device
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.noise_fill_: output tensors must live on the GPU (no CPU fallback)")
+    L = N.lib()
+    keep = []
+    for code, idx in by_dtype(range(len(outs)), lambda s: outs[s].dtype).items():
+        if code not in FLOAT_CODES:
+            raise TypeError(f"flame_amd.noise_fill_: {outs[idx[0]].dtype} tensors get no noise (float dtypes only)")
+        for s in idx:
+            assert outs[s].is_contiguous() and outs[s].device == device
+        segs = [Seg(outs[s].numel(), out=outs[s].data_ptr() if outs[s].numel() else 0) for s in idx]
+        meta, n_chunks, offs = plan_noise(code, segs, [streams[s] for s in idx], [starts[s] for s in idx])
+        _launch("flame_noise_fill", sum(sg.numel for sg in segs) * ITEMSIZE[code], device, keep, meta,
+                lambda b: L.flame_noise_fill(code, b + offs["segs"], len(segs), n_chunks, b + offs["streams"],
+                                             b + offs["starts"], seed, rnd, std, _stream_ptr(device)))
+    _keepalive(keep + list(outs), device)
+
+
+def noise_fill(like: dict, seed: int, rnd: int, std: float, *, device=None) -> dict:
+    """``{key: noise}`` for the FLOAT keys of ``like`` (a model's state_dict): new device tensors of each
+    key's dtype and shape, ``noise[e] = round_dtype(z[e] * std)`` with ``z`` the fp32 unit normal of
+    ``(seed, rnd, stream, e)`` and ``stream`` the key's position in ``like``'s iteration order, counting
+    every key.  Integer and bool keys get no noise and are absent.  One flame_noise_fill launch per
+    dtype on torch's current stream; nothing is read back."""
+    seed, rnd, std = check_noise_args(seed, rnd, std)
+    device = _hip_device(device, "noise_fill", prefer=like)
+    keys, outs, streams = [], [], []
+    for pos, (k, t) in enumerate(like.items()):
+        if isinstance(t, torch.Tensor) and t.is_floating_point():
+            dtype_code(t.dtype)                 # an unsupported float dtype raises
+            keys.append(k)
+            outs.append(torch.empty(t.shape, dtype=t.dtype, device=device))
+            streams.append(pos)
+    noise_fill_(outs, streams, [0] * len(outs), seed, rnd, std)
+    return collections.OrderedDict(zip(keys, outs))
 
 
 # ------------------------------------------------------------------ dict-level helpers used by the optimizers

@@ -50,6 +50,11 @@ What the kwargs refuse of each other, of ``defer=True`` and of the sharded wrapp
   sums of squares are the first squared distances (the centre starts at the unchanged model); each
   further Weiszfeld iteration is one reduction into a scratch centre and one ``engine.update_dist``
   (kernel ``flame_update_dist``).  Every eligible update is kept, with the final weights as its rate.
+
+Behind the stage and the reduction, server-side Gaussian noise (``noise_factor=s``, ``noise_seed=``;
+``noise.py``): one draw per round of standard deviation ``s * sqrt(fsum(rate^2))`` over the entries
+actually aggregated (``engine.noise_fill``, kernel ``flame_noise_fill``), accumulated into the float
+keys as one more update with rate 1 behind the last entry.  ``noise_round`` counts the noised rounds.
 """
 import collections
 import collections.abc
@@ -63,6 +68,7 @@ import torch
 from .. import engine, metrics
 from . import guard, refusals
 from . import krum as krum_
+from . import noise as noise_
 from . import rfa as rfa_
 from . import trim as trim_
 from .abstract import AbstractOptimizer
@@ -153,7 +159,7 @@ class FedAvg(AbstractOptimizer):
 
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
                  clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None,
-                 rfa=None, rfa_nu=None):
+                 rfa=None, rfa_nu=None, noise_factor=None, noise_seed=None):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
@@ -169,8 +175,11 @@ class FedAvg(AbstractOptimizer):
         self.rfa, self.rfa_nu = rfa_.check_kwargs(rfa, rfa_nu)
         self.rfa_records = []      # the last rfa do()'s RfaRecords, in cache order
         self.rfa_trace = []        # ... and its (dist2, weights) per Weiszfeld iteration run, over the eligible updates
+        self.noise_factor, self.noise_seed = noise_.check_kwargs(noise_factor, noise_seed)
+        self.noise_round = 0       # the round counter fed to the generator: one per noised round
+        self.noise_std = None      # the last noised round's standard deviation
         # every kwarg is valid: now what they refuse of each other and of a deferred queue (FedAvg's or FedOPT's)
-        refusals.check(self, *[c for c in ("clip_threshold", "trim", "krum") if refusals.is_set(self, c)],
+        refusals.check(self, *[c for c in ("clip_threshold", "trim", "krum", "rfa") if refusals.is_set(self, c)],
                        *(("defer",) if defer or self.chain_defer else ()))
 
     @property
@@ -266,6 +275,8 @@ class FedAvg(AbstractOptimizer):
         self.agg_weights = base_weights
         if len(cache) == 0 or total == 0:
             return None
+        if self.noise_factor is not None and "flame_amd_key_groups" in kwargs:
+            refusals.check(self, "key_groups")      # the sharded wrapper, with the cache still full
         entries, scales = self._select(cache, total, kwargs)
         if not entries:                # nothing left to aggregate: as for an empty cache
             return None
@@ -287,4 +298,24 @@ class FedAvg(AbstractOptimizer):
         extra = {} if scales is None else {"scales": scales}     # only a clipped round names them
         engine.accumulate(self.agg_weights, entries, key_groups=kwargs.get("flame_amd_key_groups"),
                           after_group=kwargs.get("flame_amd_after_group"), **extra)
+        if self.noise_factor is not None:
+            # one more update with rate 1 and scale 1 after the last entry, as a second reduction on the
+            # same stream: the same bits as one launch over entries + [(noise, 1.0)], the slab fast path kept
+            std, noise = self._draw_noise(self.agg_weights, entries)
+            if noise:
+                engine.accumulate(self.agg_weights, [(noise, 1.0)])
+            self._noise_drawn(std)
         return self.agg_weights
+
+    def _draw_noise(self, base_weights, entries, device=None):
+        """This round's noise (the noise contract): ``std = s * sqrt(fsum(rate^2))`` over the
+        entries actually aggregated, and ``{float key: round_dtype(z * std)}`` from ``engine.noise_fill`` for
+        ``(noise_seed, noise_round)``."""
+        std = noise_.std_of(self.noise_factor, [r for _, r in entries])
+        return std, engine.noise_fill(base_weights, self.noise_seed, self.noise_round, std, device=device)
+
+    def _noise_drawn(self, std):
+        """A noised round has been issued: its metrics, and the counter moves on."""
+        self.noise_std = std
+        noise_.save_metrics(self, std, self.noise_round)
+        self.noise_round += 1

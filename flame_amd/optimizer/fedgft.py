@@ -140,9 +140,11 @@ class FedGFT(FedAvg):
     """FedGFT class: FedAvg aggregation (HIP kernel) + server-side fairness bias."""
 
     def __init__(self, fair, gamma, reg="l2", *, clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None,
-                 krum_select=None, rfa=None, rfa_nu=None):
+                 krum_select=None, rfa=None, rfa_nu=None, noise_factor=None,
+                 noise_seed=None):
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim, krum=krum,
-                         krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu)
+                         krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu,
+                         noise_factor=noise_factor, noise_seed=noise_seed)
         self.fair = fair
         self.regularizer = FedGFTRegularizer(fair, gamma, reg)
         self.bias = Bias(fair=self.fair, local=False)

@@ -87,7 +87,8 @@ class FedOPT(FedAvg):
     max_chain_bytes = 16 << 30
 
     def __init__(self, beta_1, beta_2, eta, tau, defer: bool = False, *, clip_threshold=None,
-                 nonfinite: str = "keep", trim=None, krum=None, krum_select=None, rfa=None, rfa_nu=None):
+                 nonfinite: str = "keep", trim=None, krum=None, krum_select=None, rfa=None, rfa_nu=None,
+                 noise_factor=None, noise_seed=None):
         self.trim = trim_.check_kwarg(trim)
         refusals.check(self, "fedopt")      # trim: before anything else of the constructor
         self._poisoned = None
@@ -98,7 +99,8 @@ class FedOPT(FedAvg):
         self._agg = None
         self.chain_defer = defer        # before FedAvg's constructor, which checks what a deferred chain refuses
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, krum=krum, krum_select=krum_select,
-                         rfa=rfa, rfa_nu=rfa_nu)
+                         rfa=rfa, rfa_nu=rfa_nu,
+                         noise_factor=noise_factor, noise_seed=noise_seed)
         self.current_weights = None
         self._d_t = None
         self._prev_current = None
@@ -205,6 +207,8 @@ class FedOPT(FedAvg):
         key_groups, after_group = kwargs.get("flame_amd_key_groups"), kwargs.get("flame_amd_after_group")
         alloc = kwargs.get("flame_amd_out_alloc")
         self.agg_weights = base_weights
+        if self.noise_factor is not None and key_groups is not None:
+            refusals.check(self, "key_groups")      # the sharded wrapper, with the cache still full
         entries, scales = self._select(cache, total, kwargs)
         if not entries:         # nothing left to aggregate: FedAvg.do returns None (fedopt.py:80-85)
             self.agg_weights = None
@@ -234,14 +238,22 @@ class FedOPT(FedAvg):
                 if k not in base_weights:
                     raise KeyError(k)
 
+        noise = std = None
+        if self.noise_factor is not None:
+            # the noise is the round's last update (rate 1, scale 1): the adaptive step reads the noised average
+            std, noise = self._draw_noise(base_weights, entries, device)
         state_zero = self.m_t is None
         if state_zero:
             self.m_t, self.v_t = {}, {}
         new_cur = {}
         if generic:       # first, so every key of a group is final when its group is handed on
             sub = {k: base_weights[k] for k in generic}
-            engine.accumulate(sub, [({k: w[k] for k in generic if k in w}, r) for w, r in entries], device=device,
-                              **({} if scales is None else {"scales": scales}))
+            g_entries, g_scales = entries, scales
+            if noise is not None:
+                g_entries = entries + [(noise, 1.0)]
+                g_scales = None if scales is None else list(scales) + [1.0]
+            engine.accumulate(sub, [({k: w[k] for k in generic if k in w}, r) for w, r in g_entries], device=device,
+                              **({} if g_scales is None else {"scales": g_scales}))
             res = self._adapt_generic(generic, base_weights, current, state_zero, device)
             if alloc is not None:
                 for k, v in res.items():
@@ -253,19 +265,24 @@ class FedOPT(FedAvg):
             ks = [k for k in group if k in in_fused]
             if ks:
                 self._launch_fused(ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur,
-                                   scales)
+                                   scales, **({} if noise is None else {"noise": noise}))     # only a noised round names it
             if after_group is not None:
                 after_group(gi)
+        if noise is not None:
+            self._noise_drawn(std)
         self._prev_current = current
         self._d_t = None
         self.current_weights = OrderedDict((k, new_cur[k]) for k in current.keys() if k in new_cur)
         return self.current_weights
 
     def _launch_fused(self, ks, base_weights, current, entries, device, hyper, state_zero, alloc, new_cur,
-                      scales=None):
+                      scales=None, noise=None):
         """One flame_fedopt_reduce_adapt launch per dtype over keys ``ks``.  A round with clip
         ``scales`` (the update guard) takes the split path: the scaled reduction, then the
-        adaptive step with no clients."""
+        adaptive step with no clients.  ``noise`` (``noise_factor``) is the last client of the fused
+        launch, with rate 1; on the split path, and when the updates are slab slots (a dense tensor
+        among tiled views would have every view copied out), it is a reduction of its own between
+        the two launches -- the same bits, the adaptive step reads the noised average either way."""
         targets = [engine._Target(base_weights[k], device) for k in ks]
         alias = [_same_storage(current[k], base_weights[k]) for k in ks]
         # an aliased key's current is the FedAvg result itself: the kernel takes cur = avg
@@ -287,7 +304,17 @@ class FedOPT(FedAvg):
         avgs = [t.dev for t in targets]
         clients = [[w[k] for w, _ in entries] for k in ks]
         rates = [r for _, r in entries]
-        if scales is not None:
+        if noise is not None:
+            if scales is not None or self.split_launch or any(getattr(w, "slab", None) is not None for w, _ in entries):
+                engine.reduce_(avgs, avgs, clients, rates, scales=scales)
+                engine.reduce_(avgs, avgs, [[noise[k]] for k in ks], [1.0])
+                engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
+                                            [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
+            else:
+                engine.fedopt_reduce_adapt_(self.variant, avgs, avgs, curs, outs, ms, vs,
+                                            [row + [noise[k]] for row, k in zip(clients, ks)], rates + [1.0], hyper,
+                                            state_zero, cur_is_avg=alias)
+        elif scales is not None:
             engine.reduce_(avgs, avgs, clients, rates, scales=scales)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)

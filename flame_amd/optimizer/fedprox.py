@@ -41,8 +41,10 @@ class FedProx(FedAvg):
     """FedProx class (server side = FedAvg)."""
 
     def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None,
-                 krum_select=None, rfa=None, rfa_nu=None):
+                 krum_select=None, rfa=None, rfa_nu=None, noise_factor=None,
+                 noise_seed=None):
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim, krum=krum,
-                         krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu)
+                         krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu,
+                         noise_factor=noise_factor, noise_seed=noise_seed)
         self.mu = mu
         self.regularizer = FedProxRegularizer(self.mu)

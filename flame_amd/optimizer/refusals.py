@@ -1,8 +1,9 @@
-"""What the update guard, ``trim``, ``krum`` and ``rfa`` refuse, stated once: ``(feature, context) -> why``.
+"""What the update guard, ``trim``, ``krum``, ``rfa`` and ``noise_factor`` refuse, stated once: ``(feature, context) -> why``.
 
-A *feature* is ``"guard"`` (``clip_threshold`` / ``nonfinite``), ``"trim"``, ``"krum"`` or ``"rfa"``; a *context*
+A *feature* is ``"guard"`` (``clip_threshold`` / ``nonfinite``), ``"trim"``, ``"krum"``, ``"rfa"`` or ``"noise"``
+(``noise_factor``); a *context*
 is what it meets: a deferred queue (``"defer"``: ``FedAvg(defer=True)`` or FedOPT's chain), another
-kwarg (``"clip_threshold"``, ``"trim"``, ``"krum"``), the FedOPT family (``"fedopt"``), the sharded wrapper at its
+kwarg (``"clip_threshold"``, ``"trim"``, ``"krum"``, ``"rfa"``), the FedOPT family (``"fedopt"``), the sharded wrapper at its
 construction (``"shard"``) or the key groups it passes to ``do()`` (``"key_groups"``).  Constructors
 set their attributes first and then call :func:`check` once; the order of the table is the order in
 which a constructor that meets several contexts reports them.  Every refusal is a
@@ -11,7 +12,8 @@ NotImplementedError; a bad value is a ValueError / TypeError from the kwarg's ow
 NAME = {"guard": "clip_threshold / nonfinite (the server-side update guard) are",
         "trim": "trim (coordinate-wise trimmed-mean / median aggregation) is",
         "krum": "krum (Krum / Multi-Krum aggregation) is",
-        "rfa": "rfa (geometric-median aggregation, RFA) is"}
+        "rfa": "rfa (geometric-median aggregation, RFA) is",
+        "noise": "noise_factor (server-side Gaussian noise) is"}
 
 # (feature, context) -> (who refuses, ``{cls}`` the optimizer's class; why)
 TABLE = {
@@ -44,6 +46,16 @@ TABLE = {
                             "need an all-reduce of n doubles between measure and weights (a follow-up)"),
     ("rfa", "shard"): ("ShardedOptimizer", "each rank's partial distances would need an all-reduce of n doubles "
                        "between measure and weights (a follow-up)"),
+    ("noise", "defer"): ("{cls}(defer=True)", "the noise of a round is scaled by the rates of everything aggregated "
+                         "in it, which are not known when an arrival is queued; use defer=False"),
+    ("noise", "trim"): ("{cls}(trim=...)", "the trimmed path forms no entries and no rates, so the noise has no "
+                        "stated scale there"),
+    ("noise", "krum"): ("{cls}(krum=...)", "noise on a selected subset has no stated privacy meaning"),
+    ("noise", "rfa"): ("{cls}(rfa=...)", "noise on data-dependent Weiszfeld weights has no stated privacy meaning"),
+    ("noise", "key_groups"): ("ShardedOptimizer", "each rank would draw the noise of its own slices, which needs the "
+                              "slice offsets as the generator's starts (a follow-up)"),
+    ("noise", "shard"): ("ShardedOptimizer", "each rank would draw the noise of its own slices, which needs the slice "
+                         "offsets as the generator's starts (a follow-up)"),
 }
 
 
@@ -57,6 +69,8 @@ def is_set(opt, what: str) -> bool:
     """Is feature (or kwarg) ``what`` set on ``opt`` (any optimizer: one without the kwargs has none)?"""
     if what == "guard":
         return bool(getattr(opt, "guarded", False))
+    if what == "noise":
+        return getattr(opt, "noise_factor", None) is not None
     return getattr(opt, what, None) is not None
 
 

@@ -37,6 +37,8 @@
  *                               by optimizer/fedavg.py:93-104, in one pass
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
+ *   flame_noise_fill            privacy/differential_privacy.py:55-61 (torch.normal(0, noise_factor)),
+ *                               drawn once per round on the aggregator: Philox4x32-10 + Box-Muller
  *   flame_synth_fill            (bench/test plumbing: counter-based synthetic updates)
  *   flame_hier_resident_per_cu  (no reference counterpart: occupancy query the parameter
  *                               shard uses to size its waves, flame_amd/shard.py)
@@ -611,6 +613,40 @@ int flame_host_device_pointer(void *host, void **device);
  */
 int flame_synth_fill(int dtype, void *out, int64_t numel, uint64_t seed, uint64_t stream_id,
                      int64_t start, float scale, void *stream);
+
+/*
+ * Server-side Gaussian noise: the reference's trainer-side statement
+ * privacy/differential_privacy.py:55-61 (torch.normal(0, noise_factor) added to every element
+ * of a trainer's delta), drawn once per round on the aggregator for the weighted average.
+ * Write-only over a segment table: of each flame_segment only out, numel, chunk_begin and flags
+ * (FLAME_SEG_UNALIGNED) are read.  Element e of segment s receives
+ *   out[e] = round_dtype(z(seed, round, streams[s], starts[s] + e) * std)
+ * where z is an fp32 unit normal, a pure function of its four arguments:
+ *   bits      Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
+ *             1, 2, 3", SC'11), key (seed & 0xffffffff, seed >> 32), counter (b & 0xffffffff,
+ *             b >> 32, stream, round) with b = g >> 2 for global index g; the output words
+ *             x0..x3 serve elements 4b .. 4b+3
+ *   uniforms  u1 = RNE_f32(2 x + 1) * 2^-33 in (0, 1] from x0 (x2), the angle 2 pi k / 2^24
+ *             with k = x1 >> 8 (x3 >> 8)
+ *   transform Box-Muller (Box, Muller: "A note on the generation of random normal deviates",
+ *             Ann. Math. Statist. 29, 1958): r = sqrt(-2 ln u1), z_even = r cos, z_odd = r sin,
+ *             as explicit fp32 multiplies, adds, one divide and one correctly rounded root
+ *             (no fma, no hardware log / sin / cos), restated op for op by tests/noise_ref.py
+ * FLAME_F32 / FLAME_BF16 / FLAME_F16 take std rounded to fp32 and one fp32 multiply (16-bit:
+ * then one RNE rounding); FLAME_F64 widens z and takes one fp64 multiply by std itself.
+ *   streams : device uint32[n_segs], the key's position in the model's iteration order
+ *   starts  : device int64[n_segs], >= 0 (the caller's to guarantee: the array lives in device
+ *             memory), the global index of the segment's first element inside its key, so a
+ *             sub-range of a key can be generated alone; a segment with starts % 4 == 0 and
+ *             aligned `out` is written in 16-byte vectors, any other element by element
+ * The result does not depend on the launch geometry.  Refused before any HIP call: a NULL
+ * table or array, n_segs <= 0, n_chunks outside [1, 2^31), an integer (FLAME_ENOTSUP, "float
+ * dtypes only") or unknown dtype, std negative, NaN or infinite (or, for the fp32-std dtypes,
+ * rounding to an infinite fp32).
+ */
+int flame_noise_fill(int dtype, const flame_segment *segs, int32_t n_segs, int64_t n_chunks,
+                     const uint32_t *streams, const int64_t *starts, uint64_t seed, uint32_t round,
+                     double std, void *stream);
 
 /*
  * Slab insert: the aggregator role's `self.cache[end] = tres` (mode/horizontal/syncfl/
