@@ -41,7 +41,7 @@ EXPORTS = (
     "flame_update_stats", "flame_update_stats_scratch_bytes", "flame_agg_reduce_scaled",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
-    "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
+    "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_agg_select", "flame_agg_select_max_clients", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
     "flame_hier_resident_per_cu", "flame_feddyn_round", "flame_elementwise", "flame_elementwise_segments", "flame_synth_fill",
     "flame_noise_fill",
     "flame_host_register", "flame_host_unregister", "flame_host_device_pointer",
@@ -103,6 +103,10 @@ def lib() -> ctypes.CDLL:
     L.flame_agg_trimmed.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, i32, i32, vp]
     L.flame_agg_trimmed_max_k.restype = ctypes.c_int
     L.flame_agg_trimmed_max_k.argtypes = []
+    L.flame_agg_select.restype = ctypes.c_int
+    L.flame_agg_select.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, i32, i32, vp]
+    L.flame_agg_select_max_clients.restype = ctypes.c_int
+    L.flame_agg_select_max_clients.argtypes = []
     L.flame_fedopt_reduce_adapt.restype = ctypes.c_int
     L.flame_fedopt_reduce_adapt.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp, i32, vp] + [f32] * 6 + [vp]
     L.flame_fedopt_chain.restype = ctypes.c_int

@@ -982,6 +982,228 @@ __global__ __launch_bounds__(kBlock) void agg_trimmed_kernel(const flame_segment
         if (e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
 }
 
+// ---------------------------------------------------------------- trimmed mean / median by radix selection
+// The same statement for any k (flame_agg_select; DESIGN.md §2 is the contract): the chains above
+// hold 2k keys per element in registers and stop at k = 16.  Here a lane finds, per element, the
+// two order statistics lo = sorted[k] and hi = sorted[n - k - 1] by an MSB-first radix search on the
+// same integer keys, 4 bits per pass: every pass re-reads the chunk's n x 4 KiB (ordinary cached
+// loads) and counts, per element, the digits of the keys that carry the prefix found so far; the
+// digit at which the running count crosses the rank extends the prefix.  The counters are
+// lane-private histograms in LDS, [bin][lane] with dword stride (bank = lane: no conflict, no
+// atomic, no barrier), one array per element of the group so that the group's read-modify-writes
+// are independent; a dword packs the count for lo's prefix (low half) and for hi's (high half),
+// so a key costs one read-modify-write per element and a median's two ranks, whose prefixes
+// agree almost to the end, share it.  16-bit counts bound n_clients by 65,535.  A group is 4
+// elements (2 for f64): 4 arrays x 16 bins x 256 lanes x 4 B = 64 KiB; bf16 / f16 search their 8
+// elements as two groups one after the other.  The last pass (nontemporal loads) adds the values
+// strictly between lo and hi in client order and counts the ties at both ends; what the kept
+// multiset holds of lo and hi enters as count x value.  Nothing depends on the launch geometry.
+constexpr int kSelectMaxClients = 65535;
+constexpr int kSelBins = 16;                     // 4-bit digits
+#ifndef FLAME_T_SEL_UNROLL
+#define FLAME_T_SEL_UNROLL 8
+#endif
+
+// The keys of TrimK<DT> one per register, and a key decoded and widened to fp64 (exact).
+template <int DT> struct SelK {
+    using U = std::conditional_t<DT == FLAME_F64, uint64_t, uint32_t>;
+    static constexpr int BITS = DT == FLAME_F64 ? 64 : DT == FLAME_F32 ? 32 : 16;
+    static constexpr int EPT = Tr<DT>::EPT;
+    static constexpr int GE = EPT < 4 ? EPT : 4;     // elements searched side by side
+    __device__ static void keys(const V16& v, U (&k)[EPT]) {
+        using K = TrimK<DT>;
+        typename K::R r[K::NR];
+        K::keys(v, r);
+        if constexpr (BITS == 16) {
+#pragma unroll
+            for (int i = 0; i < K::NR; ++i) {
+                k[2 * i] = r[i].x;
+                k[2 * i + 1] = r[i].y;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < K::NR; ++i) k[i] = r[i];
+        }
+    }
+    __device__ static double value(U k) {
+        if constexpr (DT == FLAME_F64) {
+            const uint64_t m = ~static_cast<uint64_t>(static_cast<int64_t>(k) >> 63) | 0x8000000000000000ull;
+            return __longlong_as_double(static_cast<long long>(k ^ m));
+        } else if constexpr (DT == FLAME_F32) {
+            const uint32_t m = ~static_cast<uint32_t>(static_cast<int32_t>(k) >> 31) | 0x80000000u;
+            return static_cast<double>(__uint_as_float(k ^ m));
+        } else {
+            const uint32_t m = (k & 0x8000u) ? 0x8000u : 0xFFFFu;
+            return static_cast<double>(Tr<DT>::ld(static_cast<uint16_t>(k ^ m)));
+        }
+    }
+};
+
+// One lane vector of every client through the search and the summing pass; acc leaves as the fp64
+// sum of the kept multiset.  h[j]: this lane's column of element j's histogram.  VEC as in
+// reduce_clients.
+template <int DT, bool VEC>
+__device__ __forceinline__ void select_clients(double (&acc)[Tr<DT>::EPT], uint32_t* const (&h)[4],
+                                               const uint64_t* __restrict__ cp, int n, int k, int64_t e0, int64_t numel,
+                                               int64_t coff) {
+    using X = Tr<DT>;
+    using T = typename X::T;
+    using S = SelK<DT>;
+    using U = typename S::U;
+    constexpr int EPT = X::EPT, GE = S::GE, NG = EPT / GE, CU = FLAME_T_SEL_UNROLL;
+    auto load_client = [&](int c, auto last) -> V16 {
+        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
+        if constexpr (VEC) {
+            if constexpr (decltype(last)::value) return ld_nt(p);
+            else return ld_v(p);
+        } else {
+            T x[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
+            return pack<T, EPT>(x);
+        }
+    };
+    auto each_client = [&](auto last, auto&& f) {
+        int i = 0;
+        for (; i + CU <= n; i += CU) {
+            V16 v[CU];
+#pragma unroll
+            for (int u = 0; u < CU; ++u) v[u] = load_client(i + u, last);
+#pragma unroll
+            for (int u = 0; u < CU; ++u) f(v[u]);
+        }
+        for (; i < n; ++i) f(load_client(i, last));
+    };
+    U klo[EPT], khi[EPT];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        U ulo[GE], uhi[GE];                          // the prefixes found so far, right-aligned
+        uint32_t rlo[GE], rhi[GE];                   // the ranks among the keys that carry them
+#pragma unroll
+        for (int j = 0; j < GE; ++j) {
+            ulo[j] = uhi[j] = 0;
+            rlo[j] = static_cast<uint32_t>(k);
+            rhi[j] = static_cast<uint32_t>(n - k - 1);
+        }
+#pragma unroll 1
+        for (int shift = S::BITS - 4; shift >= 0; shift -= 4) {
+#pragma unroll
+            for (int b = 0; b < kSelBins; ++b)
+#pragma unroll
+                for (int j = 0; j < GE; ++j) h[j][b * kBlock] = 0u;
+            each_client(ic_<0>{}, [&](const V16& v) {
+                U key[EPT];
+                S::keys(v, key);
+#pragma unroll
+                for (int j = 0; j < GE; ++j) {
+                    const U hb = key[g * GE + j] >> shift;
+                    const uint32_t d = static_cast<uint32_t>(hb) & (kSelBins - 1);
+                    const U up = hb >> 4;
+                    h[j][d * kBlock] += (up == ulo[j] ? 1u : 0u) | (up == uhi[j] ? 0x10000u : 0u);
+                }
+            });
+            // the digit: the number of bins whose running count stays at or below the rank
+#pragma unroll
+            for (int j = 0; j < GE; ++j) {
+                uint32_t cl = 0, ch = 0, dl = 0, dh = 0, bl = 0, bh = 0;
+#pragma unroll
+                for (int b = 0; b < kSelBins; ++b) {
+                    const uint32_t w = h[j][b * kBlock];
+                    cl += w & 0xFFFFu;
+                    ch += w >> 16;
+                    const bool tl = cl <= rlo[j], th = ch <= rhi[j];
+                    dl += tl;
+                    dh += th;
+                    bl = tl ? cl : bl;
+                    bh = th ? ch : bh;
+                }
+                ulo[j] = (ulo[j] << 4) | dl;
+                uhi[j] = (uhi[j] << 4) | dh;
+                rlo[j] -= bl;
+                rhi[j] -= bh;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < GE; ++j) {
+            klo[g * GE + j] = ulo[j];
+            khi[g * GE + j] = uhi[j];
+        }
+    }
+    // the summing pass: strictly-inside values in client order; the ties at lo and hi are counted
+    uint32_t nle[EPT], nge[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) nle[j] = nge[j] = 0;
+    each_client(ic_<1>{}, [&](const V16& v) {
+        U key[EPT];
+        S::keys(v, key);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            nle[j] += key[j] <= klo[j];
+            nge[j] += key[j] >= khi[j];
+            const double s = __dadd_rn(acc[j], S::value(key[j]));
+            acc[j] = (klo[j] < key[j] && key[j] < khi[j]) ? s : acc[j];
+        }
+    });
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const bool one = klo[j] == khi[j];
+        const double c_lo = static_cast<double>(one ? static_cast<uint32_t>(n - 2 * k) : nle[j] - static_cast<uint32_t>(k));
+        const double c_hi = static_cast<double>(nge[j] - static_cast<uint32_t>(k));
+        acc[j] = __dadd_rn(acc[j], __dmul_rn(c_lo, S::value(klo[j])));
+        const double t = __dadd_rn(acc[j], __dmul_rn(c_hi, S::value(khi[j])));
+        acc[j] = one ? acc[j] : t;
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kBlock) void agg_select_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                            const uint64_t* __restrict__ clients, int n_clients,
+                                                            int trim_k, unsigned flags, int64_t n_chunks) {
+    using X = Tr<DT>;
+    using T = typename X::T;
+    using A = typename X::A;
+    constexpr int EPT = X::EPT;
+    static_assert(kVPT == 1, "agg_select_kernel: one lane vector per chunk");
+    __shared__ uint32_t h0[kSelBins * kBlock], h1[kSelBins * kBlock], h2[kSelBins * kBlock], h3[kSelBins * kBlock];
+    static_assert(4 * sizeof(h0) <= 64 * 1024, "agg_select_kernel: the histograms exceed 64 KiB");
+    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;                      // no barrier below: the histograms are lane-private
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const int64_t coff = client_offset<DT>(sg, chunk);
+    const bool init_first = (flags & FLAME_AGG_INIT_FIRST) != 0;
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const double kept = static_cast<double>(n_clients - 2 * trim_k);
+    const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
+    T* op = reinterpret_cast<T*>(sg.out) + e0;
+    uint32_t* const h[4] = {h0 + threadIdx.x, h1 + threadIdx.x, h2 + threadIdx.x, h3 + threadIdx.x};
+    double acc[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) acc[j] = 0.0;
+    auto result = [&](double a, T b) -> T {          // as agg_trimmed_kernel's
+        const A mean = trim_round<DT>(a / kept);
+        return X::st(init_first ? mean : X::add(X::ld(b), mean));
+    };
+    if (vec) {
+        select_clients<DT, true>(acc, h, cp, n_clients, trim_k, e0, sg.numel, coff);
+        T b[EPT], o[EPT];
+        if (!init_first) unpack<T, EPT>(ld_v(bp), b);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
+        V16 ov[kVPT];
+        ov[0] = pack<T, EPT>(o);
+        store_chunk(op, ov);
+        return;
+    }
+    select_clients<DT, false>(acc, h, cp, n_clients, trim_k, e0, sg.numel, coff);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
+}
+
 // ---------------------------------------------------------------- update statistics (update guard)
 // Per client: the sum of squares of its finite elements and the count of its non-finite ones, over
 // every segment (differential_privacy.py:68-76 is the norm this feeds).  The only kernel that
@@ -3667,6 +3889,36 @@ int flame_agg_trimmed(int dtype, unsigned flags, const flame_segment* segs, int3
                                dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0, st, segs, n_segs,
                                reinterpret_cast<const uint64_t*>(clients), n_clients, trim_k, flags, n_chunks);
         });
+    });
+    return check_launch(who);
+}
+
+// The selection by radix passes: one instantiation per dtype, any trim_k; the client count is
+// bounded by the histograms' 16-bit counters.
+int flame_agg_select_max_clients(void) { return kSelectMaxClients; }
+
+int flame_agg_select(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                     const void* const* clients, int32_t n_clients, int32_t trim_k, void* stream) {
+    const char* const who = "flame_agg_select";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = check_chunks(n_chunks)) return rc;
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (trim_k < 0) return set_err(FLAME_EINVAL, "%s: trim_k %d is negative", who, trim_k);
+    if (n_clients > kSelectMaxClients)
+        return set_err(FLAME_ENOTSUP, "%s: n_clients %d exceeds %d (flame_agg_select_max_clients)", who, n_clients,
+                       kSelectMaxClients);
+    if (static_cast<int64_t>(n_clients) <= 2 * static_cast<int64_t>(trim_k))
+        return set_err(FLAME_EINVAL, "%s: n_clients %d must exceed 2 * trim_k = %lld", who, n_clients,
+                       2 * static_cast<long long>(trim_k));
+    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = check_flags(who, flags, FLAME_AGG_INIT_FIRST | FLAME_AGG_XCD_MAP)) return rc;
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((agg_select_kernel<decltype(dt)::value>), dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0,
+                           st, segs, n_segs, reinterpret_cast<const uint64_t*>(clients), n_clients, trim_k, flags, n_chunks);
     });
     return check_launch(who);
 }

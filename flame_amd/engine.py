@@ -1451,15 +1451,42 @@ def trimmed_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, d
     existing statement with equal weights, ``accumulate`` with rate ``1 / n`` -- no robustness is
     claimed for counters.  Counts play no part: a weighted trimmed mean would let a liar choose
     its own weight.  The updates are only read."""
+    def capacity(n, k):
+        if k > trimmed_max_k():
+            raise NotImplementedError(f"trimmed_mean: k = {k} exceeds the kernels' chain capacity {trimmed_max_k()}")
+    _trimmed("trimmed_mean", "flame_agg_trimmed", capacity, agg, weights_list, k, init_first, device)
+
+
+def select_max_clients() -> int:
+    """The most updates a selected round takes (flame_agg_select_max_clients)."""
+    return int(N.lib().flame_agg_select_max_clients())
+
+
+def selected_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, device=None) -> None:
+    """``trimmed_mean`` for any ``k`` with ``n > 2k`` (kernel: flame_agg_select): the two order
+    statistics that bound the kept values are found per element by a radix search over the keys,
+    the values strictly between them are summed in fp64 in client order and the ties at both ends
+    enter as count x value.  The kept multiset is ``trimmed_mean``'s; the order of
+    the fp64 adds is not, so the two can differ in the last bit where the sum is inexact.  ``n`` is
+    at most ``select_max_clients()`` (NotImplementedError beyond).  Grouping, checks and the
+    integer / bool / narrow keys are ``trimmed_mean``'s."""
+    def capacity(n, k):
+        if n > select_max_clients():
+            raise NotImplementedError(f"selected_mean: {n} updates exceed the selection kernel's capacity of "
+                                      f"{select_max_clients()} (select_max_clients)")
+    _trimmed("selected_mean", "flame_agg_select", capacity, agg, weights_list, k, init_first, device)
+
+
+def _trimmed(who, symbol, capacity, agg, weights_list, k, init_first, device) -> None:
+    """The one body of ``trimmed_mean`` and ``selected_mean``: checks, grouping, plan / stage / launch."""
     ws = list(weights_list)
     n = len(ws)
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-        raise TypeError(f"trimmed_mean: k must be an int, not {type(k).__name__}")
+        raise TypeError(f"{who}: k must be an int, not {type(k).__name__}")
     k = int(k)
     if k < 0 or n <= 2 * k:
-        raise ValueError(f"trimmed_mean: need 0 <= k and n > 2k, got k = {k} with {n} update(s)")
-    if k > trimmed_max_k():
-        raise NotImplementedError(f"trimmed_mean: k = {k} exceeds the kernels' chain capacity {trimmed_max_k()}")
+        raise ValueError(f"{who}: need 0 <= k and n > 2k, got k = {k} with {n} update(s)")
+    capacity(n, k)
     fkeys = [key for key, t in agg.items() if t.is_floating_point()]
     others = [key for key in agg if key not in fkeys]
     want = {key: agg[key].dtype for key in fkeys}
@@ -1467,10 +1494,10 @@ def trimmed_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, d
         have = {key: weight_dtype(w, key) for key in w.keys()}
         if {key for key, dt in have.items() if dt.is_floating_point} != set(fkeys) or \
                 any(have[key] != dt for key, dt in want.items()):
-            raise ValueError("trimmed_mean: every update must carry the aggregate's float keys in the aggregate's dtypes")
+            raise ValueError(f"{who}: every update must carry the aggregate's float keys in the aggregate's dtypes")
     if init_first and others:
-        raise ValueError(f"trimmed_mean: init_first covers float keys only; {others!r} need a base")
-    device = _hip_device(device, "trimmed_mean", *ws, prefer=agg)
+        raise ValueError(f"{who}: init_first covers float keys only; {others!r} need a base")
+    device = _hip_device(device, who, *ws, prefer=agg)
     if fkeys:
         for key in fkeys:
             dtype_code(want[key])               # an unsupported float dtype raises
@@ -1491,8 +1518,8 @@ def trimmed_mean(agg: dict, weights_list, k: int, *, init_first: bool = False, d
             if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs):
                 flags |= N.FLAME_AGG_XCD_MAP
             nbytes = sum(s.numel for s in segs) * ITEMSIZE[code] * (n + (1 if init_first else 2))
-            _launch("flame_agg_trimmed", nbytes, device, keep, p.meta,
-                    lambda b: L.flame_agg_trimmed(code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
+            _launch(symbol, nbytes, device, keep, p.meta,
+                    lambda b: getattr(L, symbol)(code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients, p.n_clients,
                                                   k, _stream_ptr(device)))
         _keepalive(keep, device)
         for t in targets.values():

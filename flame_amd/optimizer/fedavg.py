@@ -41,6 +41,8 @@ What the kwargs refuse of each other, of ``defer=True`` and of the sharded wrapp
 * Trimmed mean / median (``trim=2``, ``trim=0.1``, ``trim="median"``; ``trim.py``): the weighted
   average of the float keys is replaced by the coordinate-wise trimmed mean of what the stage left
   (``engine.trimmed_mean``, kernel ``flame_agg_trimmed``), added onto ``base_weights`` in place.
+  ``trim_method="select"`` / ``"auto"`` lifts the chain kernel's ``k <= 16`` by the radix-selection
+  kernel (``engine.selected_mean``, kernel ``flame_agg_select``).
 * Krum / Multi-Krum (``krum=2``, ``krum=0.2``, ``krum_select=1``; ``krum.py``): measured by
   ``engine.update_gram`` (the pairwise Gram matrix, kernel ``flame_update_gram``) instead; its diagonal
   is the guard's sum of squares, so the guard costs no second pass.  Every update is scored on the
@@ -159,7 +161,7 @@ class FedAvg(AbstractOptimizer):
 
     def __init__(self, defer: bool = False, max_pending: int = 256, max_pending_bytes: int = 16 << 30, *,
                  clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None, krum_select=None,
-                 rfa=None, rfa_nu=None, noise_factor=None, noise_seed=None):
+                 rfa=None, rfa_nu=None, noise_factor=None, noise_seed=None, trim_method=None):
         self.agg_weights = None
         self.regularizer = Regularizer()
         self.defer = defer
@@ -168,9 +170,11 @@ class FedAvg(AbstractOptimizer):
         self._deferred = None      # the DeferredWeights the last deferred do() returned
         self.clip_threshold, self.nonfinite = guard.check_kwargs(clip_threshold, nonfinite)
         self.trim = trim_.check_kwarg(trim)
+        self.trim_method = trim_.check_method(trim_method, self.trim)
         self.krum, self.krum_select = krum_.check_kwargs(krum, krum_select)
         self.update_stats = []     # the last do()'s UpdateRecords, in cache order (empty: nothing measured)
         self.trim_k = None         # the last trimmed do()'s k
+        self.trim_kernel = None    # ... and its kernel, "chain" or "select"
         self.krum_records = []     # the last krum do()'s KrumRecords, in cache order
         self.rfa, self.rfa_nu = rfa_.check_kwargs(rfa, rfa_nu)
         self.rfa_records = []      # the last rfa do()'s RfaRecords, in cache order
@@ -194,7 +198,13 @@ class FedAvg(AbstractOptimizer):
         if self.krum is not None:
             return krum_.check_round(self.krum, self.krum_select, n, engine.gram_max_clients())
         if self.trim is not None:
-            trim_.check_round(self.trim, n, engine.trimmed_max_k())
+            self._trim_route(n)
+
+    def _trim_route(self, n):
+        """``(k, kernel)`` of a trimmed round of ``n`` updates, or its refusal (``trim.py``)."""
+        if self.trim_method is None:
+            return trim_.check_round(self.trim, n, engine.trimmed_max_k()), trim_.CHAIN
+        return trim_.route(self.trim, self.trim_method, n, engine.trimmed_max_k, engine.select_max_clients)
 
     def _select(self, cache, total, kwargs=()):
         """THE selection stage of a round, for every class and every combination of the update guard,
@@ -282,10 +292,13 @@ class FedAvg(AbstractOptimizer):
             return None
         if self.trim is not None:
             # base_weights += the coordinate-wise trimmed mean of what the stage left (n of them)
-            k = trim_.count(self.trim, len(entries))
-            engine.trimmed_mean(base_weights, [w for w, _ in entries], k)
-            self.trim_k = k
-            trim_.save_metrics(self, k, len(entries))
+            k, kernel = trim_.count(self.trim, len(entries)), trim_.CHAIN
+            if self.trim_method is not None:
+                k, kernel = self._trim_route(len(entries))
+            mean = engine.selected_mean if kernel == trim_.SELECT else engine.trimmed_mean
+            mean(base_weights, [w for w, _ in entries], k)
+            self.trim_k, self.trim_kernel = k, kernel
+            trim_.save_metrics(self, k, len(entries), kernel if self.trim_method is not None else None)
             return base_weights
         if self.defer and "flame_amd_key_groups" not in kwargs:
             if pend is None:

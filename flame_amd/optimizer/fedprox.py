@@ -42,9 +42,9 @@ class FedProx(FedAvg):
 
     def __init__(self, mu, *, clip_threshold=None, nonfinite: str = "keep", trim=None, krum=None,
                  krum_select=None, rfa=None, rfa_nu=None, noise_factor=None,
-                 noise_seed=None):
+                 noise_seed=None, trim_method=None):
         super().__init__(clip_threshold=clip_threshold, nonfinite=nonfinite, trim=trim, krum=krum,
                          krum_select=krum_select, rfa=rfa, rfa_nu=rfa_nu,
-                         noise_factor=noise_factor, noise_seed=noise_seed)
+                         noise_factor=noise_factor, noise_seed=noise_seed, trim_method=trim_method)
         self.mu = mu
         self.regularizer = FedProxRegularizer(self.mu)

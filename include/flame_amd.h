@@ -37,6 +37,8 @@
  *                               by optimizer/fedavg.py:93-104, in one pass
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
+ *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
+ *                               trim count, by radix selection)
  *   flame_noise_fill            privacy/differential_privacy.py:55-61 (torch.normal(0, noise_factor)),
  *                               drawn once per round on the aggregator: Philox4x32-10 + Box-Muller
  *   flame_synth_fill            (bench/test plumbing: counter-based synthetic updates)
@@ -312,6 +314,35 @@ int flame_agg_trimmed(int dtype, unsigned flags, const flame_segment *segs, int3
                       int64_t n_chunks, const void *const *clients, int32_t n_clients, int32_t trim_k,
                       void *stream);
 int flame_agg_trimmed_max_k(void);
+
+/*
+ * The same trimmed mean / median for ANY trim_k, by radix selection instead of register chains
+ * (DESIGN.md §2 and §4).  Tables, flags, dtypes and refusals as flame_agg_trimmed.
+ *   trim_k    : 0 <= trim_k and n_clients > 2 * trim_k (FLAME_EINVAL otherwise); no cap.
+ *   n_clients : at most flame_agg_select_max_clients() (65,535: the kernel counts in 16 bits);
+ *               more is FLAME_ENOTSUP.
+ * Per element e, with x_i = v_i[e] in client order, on the keys and the order of flame_agg_trimmed
+ * (every NaN the all-ones key, -0 < +0); s = sorted(keys), k = trim_k, n = n_clients:
+ *   select  lo = s[k] and hi = s[n - k - 1], found by an MSB-first radix search on the keys;
+ *           c_lo = #{key <= lo} - k and c_hi = #{key >= hi} - k (both >= 1); if lo == hi,
+ *           c_lo = n - 2k and there is no hi term;
+ *   sum     acc starts at +0.0; for i in client order, if lo < key_i < hi: acc += widen(x_i), one
+ *           IEEE fp64 add each; then acc += double(c_lo) * widen(value(lo)) and, if lo != hi,
+ *           acc += double(c_hi) * widen(value(hi)): one fp64 multiply, then one fp64 add, no fma.
+ *           value(all-ones key) is the quiet NaN 0x7f..f.  The kept multiset is
+ *           sorted(x)[k : n - k] as for flame_agg_trimmed; the ORDER of the adds differs from the
+ *           chains', so the two entry points can differ in the last bit (they agree bit for bit
+ *           whenever the fp64 sum is exact).  A function of the values and the client order only,
+ *           never of the launch geometry;
+ *   mean, out[e] : as flame_agg_trimmed.
+ * No floating-point atomics: equal launches give equal bits.  Float dtypes only (FLAME_ENOTSUP
+ * otherwise); flags FLAME_AGG_INIT_FIRST and FLAME_AGG_XCD_MAP (FLAME_AGG_SEG_RATES: FLAME_ENOTSUP);
+ * device tables only.  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_select(int dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                     int64_t n_chunks, const void *const *clients, int32_t n_clients, int32_t trim_k,
+                     void *stream);
+int flame_agg_select_max_clients(void);
 
 /*
  * Fused FedAvg + FedOPT adaptive step (dtype FLAME_F32, FLAME_BF16 or FLAME_F16; base,

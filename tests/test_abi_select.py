@@ -1,0 +1,82 @@
+"""flame_agg_select / flame_agg_select_max_clients on the host: the symbols resolve, the header and
+the export list agree, the launch-branch table and the chain kernel's capacity are unchanged, every
+invalid call is refused with a code and a message before any HIP call.  Then the same validation
+under ASan + UBSan from a stand-alone C driver (tests/abi_asan_select).  No GPU call, and no
+sanitizer inside Python."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _lib():
+    from flame_amd import _native
+    return _native, _native.lib()
+
+
+def test_symbols_resolve_and_table_unchanged():
+    N, L = _lib()
+    for name in ("flame_agg_select", "flame_agg_select_max_clients"):
+        assert name in N.EXPORTS and hasattr(L, name)
+    hdr = open(os.path.join(ROOT, "include", "flame_amd.h")).read()
+    bare = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert sorted(set(re.findall(r"\b(flame_[a-z0-9_]+)\s*\(", bare))) == sorted(N.EXPORTS)
+    assert L.flame_agg_select.restype is ctypes.c_int and L.flame_agg_select.argtypes == L.flame_agg_trimmed.argtypes
+    assert L.flame_launch_branches() == 100 and L.flame_abi_version() == 1
+    assert not any("select" in n for n in N.launch_branch_counts())
+    assert L.flame_agg_select_max_clients() >= 4096 and L.flame_agg_trimmed_max_k() == 16
+    assert "int flame_agg_select(" in hdr and "int flame_agg_select_max_clients(void);" in hdr
+    assert "radix" in hdr and "c_lo = #{key <= lo} - k" in hdr
+
+
+def test_engine_reports_the_cap():
+    from flame_amd import engine
+    _, L = _lib()
+    assert engine.select_max_clients() == L.flame_agg_select_max_clients() >= 4096
+
+
+def test_select_validates_without_gpu():
+    N, L = _lib()
+    fake = ctypes.c_void_p(4096)    # never dereferenced: every call below fails on the host
+    cap = L.flame_agg_select_max_clients()
+
+    def call(dtype=0, flags=0, segs=fake, n_segs=1, n_chunks=1, clients=fake, n_clients=64, k=31):
+        return L.flame_agg_select(dtype, flags, segs, n_segs, n_chunks, clients, n_clients, k, None)
+    err = L.flame_last_error
+    assert call(segs=None) == N.FLAME_EINVAL and b"segment" in err() and b"flame_agg_select" in err()
+    assert call(n_segs=0) == N.FLAME_EINVAL and b"segment" in err()
+    assert call(clients=None) == N.FLAME_EINVAL and b"client pointer" in err()
+    assert call(n_chunks=0) == N.FLAME_EINVAL and b"n_chunks" in err()
+    assert call(n_chunks=-4) == N.FLAME_EINVAL and b"n_chunks" in err()
+    assert call(k=-1) == N.FLAME_EINVAL and b"trim_k" in err()
+    assert call(k=32, n_clients=64) == N.FLAME_EINVAL and b"2 * trim_k" in err()     # n == 2k: nothing kept
+    assert call(k=17, n_clients=33) == N.FLAME_EINVAL and b"2 * trim_k" in err()
+    assert call(k=0, n_clients=0) == N.FLAME_EINVAL and b"n_clients" in err()
+    assert call(k=0, n_clients=-3) == N.FLAME_EINVAL
+    assert call(k=2 ** 31 - 1, n_clients=4096) == N.FLAME_EINVAL and b"2 * trim_k" in err()
+    for n in (cap + 1, 2 ** 31 - 1):
+        assert call(k=17, n_clients=n) == N.FLAME_ENOTSUP
+        assert b"flame_agg_select_max_clients" in err() and str(cap).encode() in err()
+    for dt in (N.FLAME_I64, N.FLAME_I32):
+        assert call(dtype=dt) == N.FLAME_ENOTSUP and b"float dtypes only" in err()
+    assert call(dtype=21) == N.FLAME_ENOTSUP and b"unknown dtype" in err()
+    assert call(dtype=-1) == N.FLAME_ENOTSUP and b"unknown dtype" in err()
+    assert call(flags=8) == N.FLAME_EINVAL and b"unknown flags" in err()
+    assert call(flags=1 << 20) == N.FLAME_EINVAL and b"unknown flags" in err()
+    assert call(flags=N.FLAME_AGG_SEG_RATES) == N.FLAME_ENOTSUP and b"SEG_RATES" in err()
+    assert call(flags=N.FLAME_AGG_SEG_RATES | N.FLAME_AGG_INIT_FIRST) == N.FLAME_ENOTSUP
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
+                    reason="hipcc / make not available")
+def test_select_abi_validation_under_asan_ubsan(tmp_path):
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_select"), f"OUT={tmp_path}"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "select abi asan OK" in r.stdout
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
