@@ -503,8 +503,10 @@ __device__ __forceinline__ int64_t client_offset(const SEG& sg, int64_t chunk) {
 // aligned; else element-wise with bounds (tails / unaligned views).  SCALED (flame_agg_reduce_scaled
 // only; a template parameter, so no other kernel carries the branch): client i's value is first
 // multiplied by its clip scale, tmp = round(round(v * scale_i) * rate_i).
-template <int DT, int CU, bool VEC, bool SCALED = false>
-__device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][Tr<DT>::EPT], bool init_first,
+// AD (flame_agg_reduce_mixed only; DT everywhere else): the accumulator's dtype where it differs from
+// the clients' -- tmp is still formed and rounded in DT, the sum is AD's.
+template <int DT, int CU, bool VEC, bool SCALED = false, int AD = DT>
+__device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[kVPT][Tr<DT>::EPT], bool init_first,
                                                const uint64_t* __restrict__ cp, int n,
                                                const float* __restrict__ r32, const double* __restrict__ r64,
                                                int64_t e0, int64_t numel, int64_t coff,
@@ -545,7 +547,7 @@ __device__ __forceinline__ void reduce_clients(typename Tr<DT>::A (&acc)[kVPT][T
 #pragma unroll
         for (int v = 0; v < kVPT; ++v)
 #pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = X::add(acc[v][j], tmp_of(c, r, rd, x[v][j]));
+            for (int j = 0; j < EPT; ++j) acc[v][j] = Tr<AD>::add(acc[v][j], tmp_of(c, r, rd, x[v][j]));
     };
     if (init_first && n > 0) {
         T x[kVPT][EPT];
@@ -746,6 +748,52 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_scaled_kernel(const flame_s
     T* op;
     if (reduce_chunk<DT, CU, true>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op, s32, s64))
         store_chunk(op, ov);
+}
+
+// ---------------------------------------------------------------- 16-bit updates into an fp32 aggregate
+// flame_agg_reduce_mixed: bf16 / f16 client values (CD) summed into an fp32 base, the reference's
+// `tmp = (v * rate)` in v's dtype and `agg += tmp` in the promoted one (fedavg.py:93-104).  The
+// chunk is the clients': 2,048 elements, one 16-byte client vector per lane and client, eight fp32
+// accumulators per lane, two 16-byte vectors of in / out.  One chunk per workgroup at full
+// residency; SCALED as in agg_reduce_scaled_kernel.
+template <int CD, int CU, bool SCALED>
+__global__ __launch_bounds__(kBlock) void agg_reduce_mixed_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                  const uint64_t* __restrict__ clients, int n_clients,
+                                                                  const float* __restrict__ r32,
+                                                                  const float* __restrict__ s32, unsigned flags,
+                                                                  int64_t n_chunks) {
+    static_assert((CD == FLAME_BF16 || CD == FLAME_F16) && kVPT == 1,"16-bit clients, one client vector per lane");
+    constexpr int EPT = Tr<CD>::EPT;        // 8 client values = 2 fp32 vectors of 4
+    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<CD>() + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const int64_t coff = client_offset<CD>(sg, chunk);
+    const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
+    float* op = reinterpret_cast<float*>(sg.out) + e0;
+    float acc[kVPT][EPT];
+    if (e0 + EPT <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
+        float b[2][4];
+        unpack<float, 4>(ld_v(bp), b[0]);
+        unpack<float, 4>(ld_v(bp + 4), b[1]);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) acc[0][j] = b[j / 4][j % 4];
+        reduce_clients<CD, CU, true, SCALED, FLAME_F32>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff, s32);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) b[j / 4][j % 4] = acc[0][j];
+        st_v(op, pack<float, 4>(b[0]));
+        st_v(op + 4, pack<float, 4>(b[1]));
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) acc[0][j] = (e0 + j < sg.numel) ? ld1(bp + j) : 0.f;
+    reduce_clients<CD, 1, false, SCALED, FLAME_F32>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff, s32);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, acc[0][j]);
 }
 
 // ---------------------------------------------------------------- trimmed mean / median
@@ -3854,6 +3902,39 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment* segs
                            scales64, flags, n_chunks);
     });
     if (!known) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    return check_launch(who);
+}
+
+// 16-bit updates into an fp32 aggregate: outside the launch-branch table as well, one
+// instantiation per client dtype and SCALED.  Every refusal comes before the first HIP call.
+int flame_agg_reduce_mixed(int client_dtype, int agg_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs,
+                           int64_t n_chunks, const void* const* clients, int32_t n_clients, const float* rates32,
+                           const float* scales32, void* stream) {
+    const char* const who = "flame_agg_reduce_mixed";
+    if (!is16(client_dtype) || agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: client dtype %d into aggregate dtype %d is not supported (bf16 or f16 into f32 only)",
+                       who, client_dtype, agg_dtype);
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if (flags & FLAME_AGG_INIT_FIRST)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (a None-start aggregate takes the update's dtype)", who);
+    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = check_flags(who, flags, FLAME_AGG_XCD_MAP)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t* cl = reinterpret_cast<const uint64_t*>(clients);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    dispatch<FLAME_BF16, FLAME_F16>(client_dtype, [&](auto dt) {
+        constexpr int CD = decltype(dt)::value;
+        if (scales32)
+            hipLaunchKernelGGL((agg_reduce_mixed_kernel<CD, kClientUnroll16, true>), grid, block, 0, st, segs, n_segs, cl,
+                               n_clients, rates32, scales32, flags, n_chunks);
+        else
+            hipLaunchKernelGGL((agg_reduce_mixed_kernel<CD, kClientUnroll16, false>), grid, block, 0, st, segs, n_segs, cl,
+                               n_clients, rates32, scales32, flags, n_chunks);
+    });
     return check_launch(who);
 }
 

@@ -44,6 +44,10 @@ FLOAT_CODES = (N.FLAME_F32, N.FLAME_BF16, N.FLAME_F16, N.FLAME_F64)
 NARROW = (torch.bool, torch.uint8, torch.int8, torch.int16)
 VEC_BYTES = 16
 ITEMSIZE = {N.FLAME_F32: 4, N.FLAME_BF16: 2, N.FLAME_F16: 2, N.FLAME_F64: 8, N.FLAME_I64: 8, N.FLAME_I32: 4}
+# update dtypes that one launch sums into an fp32 aggregate (flame_agg_reduce_mixed): a trainer's
+# 16-bit deltas into the server's fp32 model.  Every other pair of differing dtypes stays on
+# _accumulate_mixed / _accumulate_promoted.
+UPLINK16 = (torch.bfloat16, torch.float16)
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -418,14 +422,28 @@ def slice_elems(t: torch.Tensor, lo: int, hi: int, numel: int) -> torch.Tensor:
     return t.reshape(-1)[lo:hi]
 
 
-def _client_row(cs, o: torch.Tensor, device, keep):
+def uplink16_dtype(out_dtype, client_dtypes):
+    """The clients' dtype where it differs from the aggregate's and one launch still takes them:
+    an fp32 aggregate whose clients ALL hold bf16 or ALL hold f16 (:data:`UPLINK16`).  None for
+    every other case, the same-dtype one included."""
+    if out_dtype != torch.float32:
+        return None
+    it = iter(client_dtypes)
+    first = next(it, None)
+    if first not in UPLINK16 or any(dt != first for dt in it):
+        return None
+    return first
+
+
+def _client_row(cs, o: torch.Tensor, device, keep, cdt=None):
     """Device pointers of one segment's clients + the segment's client_tile_stride.
 
     If every client is a tiled slab view with the same stride, the kernel reads
     them tiled; otherwise every client is read contiguous (tiled views that are
-    mixed with other layouts in one call are copied out -- rare)."""
+    mixed with other layouts in one call are copied out -- rare).  ``cdt``: the clients' dtype
+    where it is not the aggregate's (:func:`uplink16_dtype`); the tile-stride test is in it."""
     n = o.numel()
-    dt = o.dtype
+    dt = cdt or o.dtype
     for c in cs:
         if c.dtype != dt:
             raise NotImplementedError(
@@ -435,7 +453,7 @@ def _client_row(cs, o: torch.Tensor, device, keep):
         if ts0:
             sh, st = cs[0].shape, cs[0].stride()
             if all(c.stride() == st and c.shape == sh and c.device == device for c in cs):
-                if ts0 == chunk_elems(dtype_code(dt)) * o.element_size():
+                if ts0 == chunk_elems(dtype_code(dt)) * ITEMSIZE[dtype_code(dt)]:
                     keep.extend(cs)   # ordinary contiguous (k, T) tensors: keep allocator bookkeeping
                 # else: UpdateSlab views -- the slab outlives them, slot reuse is event-guarded
                 return [c.data_ptr() for c in cs], ts0
@@ -474,6 +492,11 @@ def host_device_pointer(host_ptr: int) -> int:
     return int(out.value or 0)
 
 
+def _require_hip(device, who) -> None:
+    if device.type != "cuda":
+        raise RuntimeError(f"flame_amd.{who}: output tensors must live on the GPU (no CPU fallback)")
+
+
 def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients: List[List[torch.Tensor]],
             rates: Optional[Sequence[float]], *, init_first: bool = False,
             seg_rates: Optional[Sequence[Sequence[float]]] = None,
@@ -491,15 +514,17 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
     if not outs:
         return
     device = outs[0].device
-    if device.type != "cuda":
-        raise RuntimeError("flame_amd.reduce_: output tensors must live on the GPU (no CPU fallback)")
+    _require_hip(device, "reduce_")
     keep = []
-    for code, idx in by_dtype(range(len(outs)), lambda s: outs[s].dtype).items():
+    # a segment of 16-bit clients under an fp32 output is grouped by both dtypes (ccode: the clients')
+    cdts = [uplink16_dtype(o.dtype, (c.dtype for c in cs)) for o, cs in zip(outs, clients)]
+    for (code, ccode), idx in by_dtype(range(len(outs)), lambda s: outs[s].dtype,
+                                       also=lambda s: cdts[s] and dtype_code(cdts[s])).items():
         segs = []
         for s in idx:
             o = outs[s]
             assert o.is_contiguous() and o.device == device
-            row, tstride = _client_row(clients[s], o, device, keep)
+            row, tstride = _client_row(clients[s], o, device, keep, cdts[s])
             inp = 0
             if not init_first:
                 i_t = ins[s]
@@ -507,14 +532,30 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
                 inp = i_t.data_ptr()
             segs.append(Seg(o.numel(), out=o.data_ptr(), inp=inp, clients=row, tile_stride=tstride))
         _launch_reduce(code, segs, rates if seg_rates is None else [seg_rates[s] for s in idx], device, keep,
-                       init_first=init_first, seg_rates=seg_rates is not None, scales=scales)
+                       init_first=init_first, seg_rates=seg_rates is not None, scales=scales, ccode=ccode)
     _keepalive(keep, device)
 
 
-def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rates=False, scales=None) -> None:
+def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rates=False, scales=None,
+                   ccode=None) -> None:
     """One flame_agg_reduce launch over prepared segments (``keep`` holds what must outlive it);
-    with ``scales`` one flame_agg_reduce_scaled launch (device tables only)."""
+    with ``scales`` one flame_agg_reduce_scaled launch (device tables only).  ``ccode``: the
+    clients' dtype code where it differs from ``code`` -- one flame_agg_reduce_mixed launch
+    (device tables only, chunks of the clients' dtype, ``scales`` inside the same entry point)."""
     L = N.lib()
+    if ccode is not None and ccode != code:
+        if init_first or seg_rates:
+            raise NotImplementedError("flame_amd: 16-bit updates into an fp32 aggregate take neither init_first "
+                                      "(a None-start aggregate has the update's dtype) nor seg_rates")
+        n_cl = _n_clients(rates, False)
+        nbytes = sum(s.numel for s in segs) * (n_cl * ITEMSIZE[ccode] + 2 * ITEMSIZE[code])
+        p = plan(ccode, segs, rates, scales=scales)
+        flags = N.FLAME_AGG_XCD_MAP if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs) else 0
+        _launch("flame_agg_reduce_mixed", nbytes, device, keep, p.meta,
+                lambda b: L.flame_agg_reduce_mixed(ccode, code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients,
+                                                   p.n_clients, b + p.off_r32,
+                                                   b + p.off_s32 if scales is not None else None, _stream_ptr(device)))
+        return
     flags = N.FLAME_AGG_INIT_FIRST if init_first else 0
     if seg_rates:
         flags |= N.FLAME_AGG_SEG_RATES
@@ -1176,8 +1217,11 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         if k in per_key:
             groups.setdefault(tuple(per_key[k]), []).append(k)
     for cis, ks in groups.items():
+        # same: one reduction launch per dtype pair -- the aggregate's own dtype, or bf16 / f16
+        # updates under an fp32 aggregate (reduce_ groups those into flame_agg_reduce_mixed)
         same = [k for k in ks if agg[k].dtype in DTYPE_CODE
-                and all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)]
+                and (all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)
+                     or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None)]
         mixed = [k for k in ks if k not in same]
         # with clip scales the float keys take the scaled kernel; integer keys are never scaled
         parts = [(same, None)] if scales is None else [
@@ -1609,21 +1653,29 @@ def _accumulate_slab(agg: dict, entries, device, key_groups=None, after_group=No
     w0 = entries[0][0]
     if getattr(w0, "slab", None) is None or len(w0) != len(agg):
         return False
-    rows = slab_rows([w for w, _ in entries], list(agg.keys()), {k: agg[k].numel() for k in agg},
-                     {k: agg[k].dtype for k in agg}, device)
+    # the slab's dtype of a key may be bf16 / f16 under an fp32 aggregate (flame_agg_reduce_mixed)
+    dts = {}
+    for k in agg:
+        dts[k] = agg[k].dtype
+        if dts[k] == torch.float32:
+            try:
+                dts[k] = uplink16_dtype(dts[k], (weight_dtype(w0, k),)) or dts[k]
+            except KeyError:
+                return False
+    rows = slab_rows([w for w, _ in entries], list(agg.keys()), {k: agg[k].numel() for k in agg}, dts, device)
     if rows is None:
         return False
     rates = [r for _, r in entries]
     targets = {k: _Target(agg[k], device) for k in agg.keys()}
     keep = []
     for gi, g in enumerate(key_groups if key_groups is not None else [list(agg.keys())]):
-        for code, ks in by_dtype(g, lambda k: agg[k].dtype).items():
+        for (code, ccode), ks in by_dtype(g, lambda k: agg[k].dtype, also=lambda k: dtype_code(dts[k])).items():
             segs = []
             for k in ks:
                 ptrs, tile_bytes = rows[k]
                 o = targets[k].dev
                 segs.append(Seg(o.numel(), out=o.data_ptr(), inp=o.data_ptr(), clients=ptrs, tile_stride=tile_bytes))
-            _launch_reduce(code, segs, rates, device, keep, scales=scales if code in FLOAT_CODES else None)
+            _launch_reduce(code, segs, rates, device, keep, scales=scales if code in FLOAT_CODES else None, ccode=ccode)
         if after_group is not None:
             after_group(gi)
     _keepalive(keep, device)

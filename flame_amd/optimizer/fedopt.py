@@ -229,7 +229,11 @@ class FedOPT(FedAvg):
                        and _overlaps(current[k], base_weights[k]))
             ok = (dt in float_dts and k in current and not partial
                   and current[k].dtype == dt and current[k].shape == base_weights[k].shape
-                  and all(k in w and w[k].dtype == dt for w, _ in entries)
+                  and all(k in w for w, _ in entries)
+                  # the updates in the key's own dtype, or all bf16 / all f16 under an fp32 key
+                  # (flame_agg_reduce_mixed, then the adaptive step on fp32 tensors)
+                  and (all(w[k].dtype == dt for w, _ in entries)
+                       or engine.uplink16_dtype(dt, (w[k].dtype for w, _ in entries)) is not None)
                   and (self.m_t is None or (k in self.m_t and self.m_t[k].dtype == dt
                                             and self.v_t[k].dtype == dt)))
             (fused if ok else generic).append(k)
@@ -282,7 +286,9 @@ class FedOPT(FedAvg):
         adaptive step with no clients.  ``noise`` (``noise_factor``) is the last client of the fused
         launch, with rate 1; on the split path, and when the updates are slab slots (a dense tensor
         among tiled views would have every view copied out), it is a reduction of its own between
-        the two launches -- the same bits, the adaptive step reads the noised average either way."""
+        the two launches -- the same bits, the adaptive step reads the noised average either way.
+        Keys whose updates are bf16 / f16 under an fp32 base take the split path as well: the
+        reduction is flame_agg_reduce_mixed, the adaptive step runs on the fp32 tensors."""
         targets = [engine._Target(base_weights[k], device) for k in ks]
         alias = [_same_storage(current[k], base_weights[k]) for k in ks]
         # an aliased key's current is the FedAvg result itself: the kernel takes cur = avg
@@ -304,8 +310,11 @@ class FedOPT(FedAvg):
         avgs = [t.dev for t in targets]
         clients = [[w[k] for w, _ in entries] for k in ks]
         rates = [r for _, r in entries]
+        split = self.split_launch or any(
+            engine.uplink16_dtype(base_weights[k].dtype, (c.dtype for c in row)) is not None
+            for k, row in zip(ks, clients))
         if noise is not None:
-            if scales is not None or self.split_launch or any(getattr(w, "slab", None) is not None for w, _ in entries):
+            if scales is not None or split or any(getattr(w, "slab", None) is not None for w, _ in entries):
                 engine.reduce_(avgs, avgs, clients, rates, scales=scales)
                 engine.reduce_(avgs, avgs, [[noise[k]] for k in ks], [1.0])
                 engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
@@ -318,7 +327,7 @@ class FedOPT(FedAvg):
             engine.reduce_(avgs, avgs, clients, rates, scales=scales)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
-        elif self.split_launch:
+        elif split:
             engine.reduce_(avgs, avgs, clients, rates)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)

@@ -35,6 +35,8 @@
  *                               geometric median of Pillutla et al., IEEE TSP 2022, on the same pass)
  *   flame_agg_reduce_scaled     privacy/differential_privacy.py:79-82 (torch.mul(d_w, scale)) followed
  *                               by optimizer/fedavg.py:93-104, in one pass
+ *   flame_agg_reduce_mixed      optimizer/fedavg.py:93-104 with bf16 / f16 updates into an fp32 model:
+ *                               `tmp = v * rate` in v's dtype, `agg += tmp` in the promoted fp32
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -281,6 +283,34 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment *segs
                             int64_t n_chunks, const void *const *clients, int32_t n_clients,
                             const float *rates32, const double *rates64, const float *scales32,
                             const double *scales64, void *stream);
+
+/*
+ * 16-bit updates into an fp32 aggregate in one launch (optimizer/fedavg.py:93-104 when a trainer
+ * sends bf16 / f16 deltas to an fp32 server model: `tmp = (v * rate)` stays in v's dtype, torch
+ * computes `agg += tmp` in the promoted dtype; with scales32 the clipped round's
+ * torch.mul(d_w, scale) of differential_privacy.py:79-82 comes first, as in flame_agg_reduce_scaled).
+ *   client_dtype : C, FLAME_BF16 or FLAME_F16: every client tensor of every segment.
+ *   agg_dtype    : FLAME_F32: every segment's in / out.
+ *   segs         : chunk_begin counts chunks of flame_chunk_elems(client_dtype) = 2,048 elements
+ *                  (one 4,096-byte slab tile); client_tile_stride is in client bytes.
+ *   rates32      : device [n_clients]; scales32: device [n_clients], or NULL for the plain round.
+ * Per element e, clients in order, no FMA:
+ *   acc = in[e]                                                  (fp32)
+ *   t   = round_C(f32(v_i[e]) * rate_i)
+ *         with scales32: t = round_C(f32(round_C(f32(v_i[e]) * scale_i)) * rate_i)
+ *   acc = round_f32(acc + f32(t))
+ *   out[e] = acc
+ * scale_i == 1 reproduces the plain round bit for bit.  Refusals, each before any HIP call and
+ * named in flame_last_error: a pair other than (bf16 | f16, f32) is FLAME_ENOTSUP (the message
+ * names both dtypes); FLAME_AGG_INIT_FIRST is FLAME_ENOTSUP (a None-start aggregate takes the
+ * update's dtype in the reference, so there is no statement to restate); FLAME_AGG_SEG_RATES is
+ * FLAME_ENOTSUP; any flag beyond FLAME_AGG_XCD_MAP, a NULL table or rate array, n_segs <= 0,
+ * n_clients < 1 or n_chunks outside [1, 2^31) is FLAME_EINVAL.  Device tables only (no
+ * kernel-argument variant).  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_reduce_mixed(int client_dtype, int agg_dtype, unsigned flags, const flame_segment *segs,
+                           int32_t n_segs, int64_t n_chunks, const void *const *clients,
+                           int32_t n_clients, const float *rates32, const float *scales32, void *stream);
 
 /*
  * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,
