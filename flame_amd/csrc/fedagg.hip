@@ -52,7 +52,6 @@ namespace {
 // (tools/hier_sweep.py, tools/chain_sweep.py, ...) build variants of THIS source with -DFLAME_T_*
 // overrides into build/, so a sweep always measures the shipped code with one knob moved.
 constexpr int kBlock = 256;          // lanes per workgroup of the reduction kernels
-constexpr int kVPT = 1;              // 16-byte vectors per lane per client
 #ifndef FLAME_T_CLIENT_UNROLL
 #define FLAME_T_CLIENT_UNROLL 8
 #endif
@@ -422,7 +421,12 @@ template <> struct Tr<FLAME_I32> {
     __device__ static A add(A a, A t) { return static_cast<int32_t>(static_cast<uint32_t>(a) + static_cast<uint32_t>(t)); }
 };
 
-template <int DT> constexpr int64_t chunk_elems() { return static_cast<int64_t>(kBlock) * kVPT * Tr<DT>::EPT; }
+// A chunk is one slab tile: each of the kBlock lanes owns one 16-byte vector of it.
+template <int DT> constexpr int64_t chunk_elems() { return static_cast<int64_t>(kBlock) * Tr<DT>::EPT; }
+template <int DT> constexpr bool chunk_is_tile() { return chunk_elems<DT>() * sizeof(typename Tr<DT>::T) == FLAME_TILE_BYTES; }
+static_assert(chunk_is_tile<FLAME_F32>() && chunk_is_tile<FLAME_BF16>() && chunk_is_tile<FLAME_F16>() &&
+              chunk_is_tile<FLAME_F64>() && chunk_is_tile<FLAME_I64>() && chunk_is_tile<FLAME_I32>(),
+              "a chunk of every dtype is FLAME_TILE_BYTES bytes");
 
 // ---------------------------------------------------------------- memory helpers
 // All device data is accessed through address_space(1) (global) pointers so the
@@ -498,15 +502,15 @@ __device__ __forceinline__ int64_t client_offset(const SEG& sg, int64_t chunk) {
 }
 
 // ---------------------------------------------------------------- reduction core
-// A lane owns VPT 16-byte vectors of the chunk, at elements e0 + v*kBlock*EPT.
-// Reduce clients [0, n) into acc for those slots.  VEC: every vector whole and
+// A lane owns one 16-byte vector of the chunk, at elements e0 .. e0 + EPT - 1.
+// Reduce clients [0, n) into acc for those slots.  VEC: the vector whole and
 // aligned; else element-wise with bounds (tails / unaligned views).  SCALED (flame_agg_reduce_scaled
 // only; a template parameter, so no other kernel carries the branch): client i's value is first
 // multiplied by its clip scale, tmp = round(round(v * scale_i) * rate_i).
 // AD (flame_agg_reduce_mixed only; DT everywhere else): the accumulator's dtype where it differs from
 // the clients' -- tmp is still formed and rounded in DT, the sum is AD's.
 template <int DT, int CU, bool VEC, bool SCALED = false, int AD = DT>
-__device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[kVPT][Tr<DT>::EPT], bool init_first,
+__device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[Tr<DT>::EPT], bool init_first,
                                                const uint64_t* __restrict__ cp, int n,
                                                const float* __restrict__ r32, const double* __restrict__ r64,
                                                int64_t e0, int64_t numel, int64_t coff,
@@ -515,20 +519,16 @@ __device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[kVPT][T
     using X = Tr<DT>;
     using T = typename X::T;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;  // vector stride in elements
     int i = 0;
     auto rate32 = [&](int c) -> float { if constexpr (DT == FLAME_F64) return 0.f; else return r32[c]; };
     auto rate64 = [&](int c) -> double { if constexpr (DT == FLAME_F64) return r64[c]; else return 0.0; };
-    auto load_client = [&](int c, T (&x)[kVPT][EPT]) {
+    auto load_client = [&](int c, T (&x)[EPT]) {
         const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
+        if constexpr (VEC) {
+            unpack<T, EPT>(ld_nt(p), x);
+        } else {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            if constexpr (VEC) {
-                unpack<T, EPT>(ld_nt(p + v * VS), x[v]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < EPT; ++j) x[v][j] = (e0 + v * VS + j < numel) ? ld1(p + v * VS + j) : T(0);
-            }
+            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
         }
     };
     // tmp of client c's element: the rate product, after the scale product when SCALED
@@ -541,54 +541,49 @@ __device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[kVPT][T
             return X::tmp(xv, r, rd);
         }
     };
-    auto combine = [&](int c, const T (&x)[kVPT][EPT]) {
+    auto combine = [&](int c, const T (&x)[EPT]) {
         const float r = rate32(c);
         const double rd = rate64(c);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = Tr<AD>::add(acc[v][j], tmp_of(c, r, rd, x[v][j]));
+        for (int j = 0; j < EPT; ++j) acc[j] = Tr<AD>::add(acc[j], tmp_of(c, r, rd, x[j]));
     };
     if (init_first && n > 0) {
-        T x[kVPT][EPT];
+        T x[EPT];
         load_client(0, x);
         const float r = rate32(0);
         const double rd = rate64(0);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = tmp_of(0, r, rd, x[v][j]);
+        for (int j = 0; j < EPT; ++j) acc[j] = tmp_of(0, r, rd, x[j]);
         i = 1;
     }
     for (; i + CU <= n; i += CU) {
-        T x[CU][kVPT][EPT];
+        T x[CU][EPT];
 #pragma unroll
         for (int u = 0; u < CU; ++u) load_client(i + u, x[u]);
 #pragma unroll
         for (int u = 0; u < CU; ++u) combine(i + u, x[u]);
     }
     for (; i < n; ++i) {
-        T x[kVPT][EPT];
+        T x[EPT];
         load_client(i, x);
         combine(i, x);
     }
 }
 
 // One chunk of one segment: acc = base (or client 0), reduce every client in order.
-// Full, aligned chunks hand their output vectors back (ov / op) so the caller can
-// store them; tails and misaligned views store element-wise here.
+// Full, aligned chunks hand their output vector back (ov / op) so the caller can
+// store it; tails and misaligned views store element-wise here.
 template <int DT, int CU, bool SCALED = false>
 __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ segs, int n_segs,
                                              const uint64_t* __restrict__ clients, int n_clients,
                                              const float* __restrict__ r32, const double* __restrict__ r64,
-                                             unsigned flags, int64_t chunk, V16 (&ov)[kVPT],
+                                             unsigned flags, int64_t chunk, V16& ov,
                                              typename Tr<DT>::T*& op, const float* __restrict__ s32 = nullptr,
                                              const double* __restrict__ s64 = nullptr) {
     using X = Tr<DT>;
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_segment sg = segs[s];
     const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
@@ -600,51 +595,39 @@ __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ s
         if (r32) r32 += static_cast<int64_t>(s) * n_clients;
         if (r64) r64 += static_cast<int64_t>(s) * n_clients;
     }
-    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    A acc[kVPT][EPT];
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    A acc[EPT];
     const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
     op = reinterpret_cast<T*>(sg.out) + e0;
     if (vec) {
         if (!init_first) {
+            T b[EPT];
+            unpack<T, EPT>(ld_v(bp), b);
 #pragma unroll
-            for (int v = 0; v < kVPT; ++v) {
-                T b[EPT];
-                unpack<T, EPT>(ld_v(bp + v * VS), b);
-#pragma unroll
-                for (int j = 0; j < EPT; ++j) acc[v][j] = X::ld(b[j]);
-            }
+            for (int j = 0; j < EPT; ++j) acc[j] = X::ld(b[j]);
         }
         reduce_clients<DT, CU, true, SCALED>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff, s32, s64);
+        T o[EPT];
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            T o[EPT];
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) o[j] = X::st(acc[v][j]);
-            ov[v] = pack<T, EPT>(o);
-        }
+        for (int j = 0; j < EPT; ++j) o[j] = X::st(acc[j]);
+        ov = pack<T, EPT>(o);
         return true;
     }
     if (!init_first) {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j)
-                acc[v][j] = X::ld((e0 + v * VS + j < sg.numel) ? ld1(bp + v * VS + j) : T(0));
+        for (int j = 0; j < EPT; ++j)
+            acc[j] = X::ld((e0 + j < sg.numel) ? ld1(bp + j) : T(0));
     }
     reduce_clients<DT, 1, false, SCALED>(acc, init_first, cp, n_clients, r32, r64, e0, sg.numel, coff, s32, s64);
 #pragma unroll
-    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j)
-            if (e0 + v * VS + j < sg.numel) st1(op + v * VS + j, X::st(acc[v][j]));
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, X::st(acc[j]));
     return false;
 }
 
 template <typename T>
-__device__ __forceinline__ void store_chunk(T* op, const V16 (&ov)[kVPT]) {
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * (16 / sizeof(T));
-#pragma unroll
-    for (int v = 0; v < kVPT; ++v) st_v(op + v * VS, ov[v]);
+__device__ __forceinline__ void store_chunk(T* op, const V16& ov) {
+    st_v(op, ov);
 }
 
 // Workgroup slot of block b when the 8 XCDs (dispatched round-robin) each take one
@@ -666,23 +649,21 @@ __device__ __forceinline__ void agg_reduce_body(const flame_segment* __restrict_
     const int64_t slot = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
     if constexpr (G == 1) {
         if (slot >= n_chunks) return;
-        V16 ov[kVPT];
+        V16 ov;
         T* op;
         if (reduce_chunk<DT, CU>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op)) store_chunk(op, ov);
     } else {
-        static_assert(G <= 32 && G * kVPT * kBlock * sizeof(V16) <= 128 * 1024, "agg_reduce_body: G chunks' outputs exceed the LDS");
-        constexpr int64_t VS = static_cast<int64_t>(kBlock) * Tr<DT>::EPT;
-        __shared__ V16 held[G * kVPT * kBlock];
+        static_assert(G <= 32 && G * kBlock * sizeof(V16) <= 128 * 1024, "agg_reduce_body: G chunks' outputs exceed the LDS");
+        __shared__ V16 held[G][kBlock];
         unsigned pending = 0;
 #pragma unroll 1
         for (int g = 0; g < G; ++g) {
             const int64_t chunk = slot * G + g;
             if (chunk >= n_chunks) break;
-            V16 ov[kVPT];
+            V16 ov;
             T* op;
             if (reduce_chunk<DT, CU>(segs, n_segs, clients, n_clients, r32, r64, flags, chunk, ov, op)) {
-#pragma unroll
-                for (int v = 0; v < kVPT; ++v) held[(g * kVPT + v) * kBlock + threadIdx.x] = ov[v];
+                held[g][threadIdx.x] = ov;
                 pending |= 1u << g;
             }
         }
@@ -693,8 +674,7 @@ __device__ __forceinline__ void agg_reduce_body(const flame_segment* __restrict_
             const flame_segment& sg = segs[find_segment(segs, n_segs, chunk)];
             T* op = reinterpret_cast<T*>(sg.out) + (chunk - sg.chunk_begin) * chunk_elems<DT>() +
                     static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
-#pragma unroll
-            for (int v = 0; v < kVPT; ++v) st_v(op + v * VS, held[(g * kVPT + v) * kBlock + threadIdx.x]);
+            st_v(op, held[g][threadIdx.x]);
         }
     }
 }
@@ -744,7 +724,7 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_scaled_kernel(const flame_s
     using T = typename Tr<DT>::T;
     const int64_t slot = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
     if (slot >= n_chunks) return;
-    V16 ov[kVPT];
+    V16 ov;
     T* op;
     if (reduce_chunk<DT, CU, true>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op, s32, s64))
         store_chunk(op, ov);
@@ -762,7 +742,7 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mixed_kernel(const flame_se
                                                                   const float* __restrict__ r32,
                                                                   const float* __restrict__ s32, unsigned flags,
                                                                   int64_t n_chunks) {
-    static_assert((CD == FLAME_BF16 || CD == FLAME_F16) && kVPT == 1,"16-bit clients, one client vector per lane");
+    static_assert(CD == FLAME_BF16 || CD == FLAME_F16, "16-bit clients, one client vector per lane");
     constexpr int EPT = Tr<CD>::EPT;        // 8 client values = 2 fp32 vectors of 4
     const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
     if (chunk >= n_chunks) return;
@@ -774,26 +754,26 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mixed_kernel(const flame_se
     const int64_t coff = client_offset<CD>(sg, chunk);
     const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
     float* op = reinterpret_cast<float*>(sg.out) + e0;
-    float acc[kVPT][EPT];
+    float acc[EPT];
     if (e0 + EPT <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
         float b[2][4];
         unpack<float, 4>(ld_v(bp), b[0]);
         unpack<float, 4>(ld_v(bp + 4), b[1]);
 #pragma unroll
-        for (int j = 0; j < EPT; ++j) acc[0][j] = b[j / 4][j % 4];
+        for (int j = 0; j < EPT; ++j) acc[j] = b[j / 4][j % 4];
         reduce_clients<CD, CU, true, SCALED, FLAME_F32>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff, s32);
 #pragma unroll
-        for (int j = 0; j < EPT; ++j) b[j / 4][j % 4] = acc[0][j];
+        for (int j = 0; j < EPT; ++j) b[j / 4][j % 4] = acc[j];
         st_v(op, pack<float, 4>(b[0]));
         st_v(op + 4, pack<float, 4>(b[1]));
         return;
     }
 #pragma unroll
-    for (int j = 0; j < EPT; ++j) acc[0][j] = (e0 + j < sg.numel) ? ld1(bp + j) : 0.f;
+    for (int j = 0; j < EPT; ++j) acc[j] = (e0 + j < sg.numel) ? ld1(bp + j) : 0.f;
     reduce_clients<CD, 1, false, SCALED, FLAME_F32>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff, s32);
 #pragma unroll
     for (int j = 0; j < EPT; ++j)
-        if (e0 + j < sg.numel) st1(op + j, acc[0][j]);
+        if (e0 + j < sg.numel) st1(op + j, acc[j]);
 }
 
 // ---------------------------------------------------------------- trimmed mean / median
@@ -991,7 +971,6 @@ __global__ __launch_bounds__(kBlock) void agg_trimmed_kernel(const flame_segment
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    static_assert(kVPT == 1, "agg_trimmed_kernel: one lane vector per chunk");
     const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
     if (chunk >= n_chunks) return;
     const int s = find_segment(segs, n_segs, chunk);
@@ -1019,9 +998,7 @@ __global__ __launch_bounds__(kBlock) void agg_trimmed_kernel(const flame_segment
         if (!init_first) unpack<T, EPT>(ld_v(bp), b);
 #pragma unroll
         for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
-        V16 ov[kVPT];
-        ov[0] = pack<T, EPT>(o);
-        store_chunk(op, ov);
+        store_chunk(op, pack<T, EPT>(o));
         return;
     }
     trimmed_clients<DT, KT, 1, false>(acc, cp, n_clients, trim_k, e0, sg.numel, coff);
@@ -1211,7 +1188,6 @@ __global__ __launch_bounds__(kBlock) void agg_select_kernel(const flame_segment*
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    static_assert(kVPT == 1, "agg_select_kernel: one lane vector per chunk");
     __shared__ uint32_t h0[kSelBins * kBlock], h1[kSelBins * kBlock], h2[kSelBins * kBlock], h3[kSelBins * kBlock];
     static_assert(4 * sizeof(h0) <= 64 * 1024, "agg_select_kernel: the histograms exceed 64 KiB");
     const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -1241,9 +1217,7 @@ __global__ __launch_bounds__(kBlock) void agg_select_kernel(const flame_segment*
         if (!init_first) unpack<T, EPT>(ld_v(bp), b);
 #pragma unroll
         for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
-        V16 ov[kVPT];
-        ov[0] = pack<T, EPT>(o);
-        store_chunk(op, ov);
+        store_chunk(op, pack<T, EPT>(o));
         return;
     }
     select_clients<DT, false>(acc, h, cp, n_clients, trim_k, e0, sg.numel, coff);
@@ -1876,7 +1850,7 @@ __device__ __forceinline__ void adapt_vec(const float (&avg)[EPT], const float (
 }
 
 // One chunk of a FedOPT round.  held != nullptr: a full-vector chunk leaves its avg / m / v /
-// cur blocks in LDS (held[(o * kVPT + v) * kBlock + lane], o = avg, m, v, cur) for the caller
+// cur blocks in LDS (held[o * kBlock + lane], o = avg, m, v, cur) for the caller
 // to store, and returns true; otherwise everything is stored here and it returns false.
 template <int DT, int VARIANT, int CU>
 __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ segs, int n_segs, int64_t chunk,
@@ -1887,7 +1861,6 @@ __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ s
     using X = Tr<DT>;
     using T = typename X::T;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_segment sg = segs[s];
     const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
@@ -1896,8 +1869,8 @@ __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ s
     const int64_t coff = client_offset<DT>(sg, chunk);
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const bool cur_avg = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;   // cur IS the FedAvg result
-    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    float acc[kVPT][EPT];
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    float acc[EPT];
     const T* base = reinterpret_cast<const T*>(sg.in) + e0;
     const T* curp = reinterpret_cast<const T*>(sg.cur) + e0;
     T* mp = reinterpret_cast<T*>(sg.m) + e0;
@@ -1905,21 +1878,21 @@ __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ s
     T* ap = sg.out ? reinterpret_cast<T*>(sg.out) + e0 : nullptr;
     T* cop = reinterpret_cast<T*>(sg.cur_out) + e0;
     if (vec) {
+        T b[EPT];
+        unpack<T, EPT>(ld_v(base), b);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            T b[EPT];
-            unpack<T, EPT>(ld_v(base + v * VS), b);
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = X::ld(b[j]);
-        }
+        for (int j = 0; j < EPT; ++j) acc[j] = X::ld(b[j]);
         reduce_clients<DT, CU, true>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff);
+        // A one-trip loop on purpose: written as straight-line code with an early return the step
+        // compiles to a different schedule, measured 2 % slower on config 4 (DESIGN.md §4,
+        // profiles/vpt_isa_diff.log); with the loop the listing is the one that was tuned.
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
+        for (int once = 0; once < 1; ++once) {
             T cur_t[EPT], m_t[EPT], v_t[EPT], avg_o[EPT], m_o[EPT], v_o[EPT], c_o[EPT];
-            if (!cur_avg) unpack<T, EPT>(ld_v(curp + v * VS), cur_t);
+            if (!cur_avg) unpack<T, EPT>(ld_v(curp), cur_t);
             if (!zero_state) {
-                unpack<T, EPT>(ld_v(mp + v * VS), m_t);
-                unpack<T, EPT>(ld_v(vp + v * VS), v_t);
+                unpack<T, EPT>(ld_v(mp), m_t);
+                unpack<T, EPT>(ld_v(vp), v_t);
             }
             float cf[EPT], mf[EPT], vf[EPT], co[EPT];
 #pragma unroll
@@ -1928,49 +1901,44 @@ __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ s
                 mf[j] = zero_state ? 0.f : X::ld(m_t[j]);
                 vf[j] = zero_state ? 0.f : X::ld(v_t[j]);
             }
-            adapt_vec<DT, VARIANT, EPT>(acc[v], cf, cur_avg, mf, vf, co, b1, omb1, b2, omb2, eta, tau);
+            adapt_vec<DT, VARIANT, EPT>(acc, cf, cur_avg, mf, vf, co, b1, omb1, b2, omb2, eta, tau);
 #pragma unroll
             for (int j = 0; j < EPT; ++j) {
-                avg_o[j] = X::st(acc[v][j]);
+                avg_o[j] = X::st(acc[j]);
                 m_o[j] = X::st(mf[j]);
                 v_o[j] = X::st(vf[j]);
                 c_o[j] = X::st(co[j]);
             }
             if (held) {
-                V16* h = held + v * kBlock + threadIdx.x;
-                h[0 * kVPT * kBlock] = pack<T, EPT>(avg_o);
-                h[1 * kVPT * kBlock] = pack<T, EPT>(m_o);
-                h[2 * kVPT * kBlock] = pack<T, EPT>(v_o);
-                h[3 * kVPT * kBlock] = pack<T, EPT>(c_o);
+                V16* h = held + threadIdx.x;
+                h[0 * kBlock] = pack<T, EPT>(avg_o);
+                h[1 * kBlock] = pack<T, EPT>(m_o);
+                h[2 * kBlock] = pack<T, EPT>(v_o);
+                h[3 * kBlock] = pack<T, EPT>(c_o);
                 continue;
             }
-            if (ap) st_v(ap + v * VS, pack<T, EPT>(avg_o));
-            st_v(mp + v * VS, pack<T, EPT>(m_o));
-            st_v(vp + v * VS, pack<T, EPT>(v_o));
-            st_v(cop + v * VS, pack<T, EPT>(c_o));
+            if (ap) st_v(ap, pack<T, EPT>(avg_o));
+            st_v(mp, pack<T, EPT>(m_o));
+            st_v(vp, pack<T, EPT>(v_o));
+            st_v(cop, pack<T, EPT>(c_o));
         }
         return held != nullptr;
     } else {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j)
-                acc[v][j] = (e0 + v * VS + j < sg.numel) ? X::ld(ld1(base + v * VS + j)) : 0.f;
+        for (int j = 0; j < EPT; ++j)
+            acc[j] = (e0 + j < sg.numel) ? X::ld(ld1(base + j)) : 0.f;
         reduce_clients<DT, 1, false>(acc, false, cp, n_clients, r32, nullptr, e0, sg.numel, coff);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) {
-                const int64_t o = v * VS + j;
-                if (e0 + o >= sg.numel) continue;
-                float mj = zero_state ? 0.f : X::ld(ld1(mp + o)), vj = zero_state ? 0.f : X::ld(ld1(vp + o)), cj;
-                adapt_elem<DT, VARIANT>(acc[v][j], cur_avg ? acc[v][j] : X::ld(ld1(curp + o)), mj, vj, cj, b1, omb1,
-                                        b2, omb2, eta, tau);
-                if (ap) st1(ap + o, X::st(acc[v][j]));
-                st1(mp + o, X::st(mj));
-                st1(vp + o, X::st(vj));
-                st1(cop + o, X::st(cj));
-            }
+        for (int j = 0; j < EPT; ++j) {
+            if (e0 + j >= sg.numel) continue;
+            float mj = zero_state ? 0.f : X::ld(ld1(mp + j)), vj = zero_state ? 0.f : X::ld(ld1(vp + j)), cj;
+            adapt_elem<DT, VARIANT>(acc[j], cur_avg ? acc[j] : X::ld(ld1(curp + j)), mj, vj, cj, b1, omb1,
+                                    b2, omb2, eta, tau);
+            if (ap) st1(ap + j, X::st(acc[j]));
+            st1(mp + j, X::st(mj));
+            st1(vp + j, X::st(vj));
+            st1(cop + j, X::st(cj));
+        }
     }
     return false;
 }
@@ -1990,16 +1958,15 @@ __device__ __forceinline__ void fedopt_body(const flame_segment* __restrict__ se
                                       omb2, eta, tau, nullptr);
     } else {
         using T = typename Tr<DT>::T;
-        constexpr int64_t VS = static_cast<int64_t>(kBlock) * Tr<DT>::EPT;
-        static_assert(G * 4 * kVPT * kBlock * sizeof(V16) <= 160 * 1024, "kOptWGC: outputs exceed the LDS");
-        __shared__ V16 held[G * 4 * kVPT * kBlock];
+        static_assert(G * 4 * kBlock * sizeof(V16) <= 160 * 1024, "kOptWGC: outputs exceed the LDS");
+        __shared__ V16 held[G * 4 * kBlock];
         unsigned pending = 0;
 #pragma unroll 1
         for (int g = 0; g < G; ++g) {
             const int64_t chunk = wg * G + g;
             if (chunk >= n_chunks) break;
             if (fedopt_chunk<DT, VARIANT, CU>(segs, n_segs, chunk, clients, n_clients, r32, flags, b1, omb1, b2, omb2,
-                                              eta, tau, held + g * 4 * kVPT * kBlock))
+                                              eta, tau, held + g * 4 * kBlock))
                 pending |= 1u << g;
         }
 #pragma unroll 1
@@ -2014,9 +1981,7 @@ __device__ __forceinline__ void fedopt_body(const flame_segment* __restrict__ se
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 if (!outs[o]) continue;
-#pragma unroll
-                for (int v = 0; v < kVPT; ++v)
-                    st_v(outs[o] + v * VS, held[((g * 4 + o) * kVPT + v) * kBlock + threadIdx.x]);
+                st_v(outs[o], held[(g * 4 + o) * kBlock + threadIdx.x]);
             }
         }
     }
@@ -2333,7 +2298,6 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel(const flame_segmen
                                                               const uint8_t* __restrict__ step_end, unsigned flags,
                                                               float b1, float omb1, float b2, float omb2, float eta,
                                                               float tau) {
-    static_assert(kVPT == 1, "fedopt_chain_kernel: a lane handles one 16-byte vector of its chunk");
     const int64_t chunk = blockIdx.x;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_segment sg = segs[s];
@@ -2402,7 +2366,6 @@ __device__ __forceinline__ void fedopt_chunk_f64(const flame_segment* __restrict
                                                  const double* __restrict__ r64, unsigned flags, const Hyper64& h) {
     constexpr int DT = FLAME_F64;
     constexpr int EPT = Tr<DT>::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_segment sg = segs[s];
     const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
@@ -2411,8 +2374,8 @@ __device__ __forceinline__ void fedopt_chunk_f64(const flame_segment* __restrict
     const int64_t coff = client_offset<DT>(sg, chunk);
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const bool cur_avg = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;   // cur IS the FedAvg result
-    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    double acc[kVPT][EPT];
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    double acc[EPT];
     const double* base = reinterpret_cast<const double*>(sg.in) + e0;
     const double* curp = reinterpret_cast<const double*>(sg.cur) + e0;
     double* mp = reinterpret_cast<double*>(sg.m) + e0;
@@ -2420,47 +2383,38 @@ __device__ __forceinline__ void fedopt_chunk_f64(const flame_segment* __restrict
     double* ap = sg.out ? reinterpret_cast<double*>(sg.out) + e0 : nullptr;
     double* cop = reinterpret_cast<double*>(sg.cur_out) + e0;
     if (vec) {
-#pragma unroll
-        for (int v = 0; v < kVPT; ++v) unpack<double, EPT>(ld_v(base + v * VS), acc[v]);
+        unpack<double, EPT>(ld_v(base), acc);
         reduce_clients<DT, CU, true>(acc, false, cp, n_clients, nullptr, r64, e0, sg.numel, coff);
-#pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            double c[EPT], m[EPT], vv[EPT], co[EPT];
-            if (!cur_avg) unpack<double, EPT>(ld_v(curp + v * VS), c);
-            if (!zero_state) {
-                unpack<double, EPT>(ld_v(mp + v * VS), m);
-                unpack<double, EPT>(ld_v(vp + v * VS), vv);
-            }
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) {
-                if (cur_avg) c[j] = acc[v][j];
-                if (zero_state) m[j] = vv[j] = 0.0;
-                adapt_elem_f64<VARIANT>(acc[v][j], c[j], m[j], vv[j], co[j], h);
-            }
-            if (ap) st_v(ap + v * VS, pack<double, EPT>(acc[v]));
-            st_v(mp + v * VS, pack<double, EPT>(m));
-            st_v(vp + v * VS, pack<double, EPT>(vv));
-            st_v(cop + v * VS, pack<double, EPT>(co));
+        double c[EPT], m[EPT], vv[EPT], co[EPT];
+        if (!cur_avg) unpack<double, EPT>(ld_v(curp), c);
+        if (!zero_state) {
+            unpack<double, EPT>(ld_v(mp), m);
+            unpack<double, EPT>(ld_v(vp), vv);
         }
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            if (cur_avg) c[j] = acc[j];
+            if (zero_state) m[j] = vv[j] = 0.0;
+            adapt_elem_f64<VARIANT>(acc[j], c[j], m[j], vv[j], co[j], h);
+        }
+        if (ap) st_v(ap, pack<double, EPT>(acc));
+        st_v(mp, pack<double, EPT>(m));
+        st_v(vp, pack<double, EPT>(vv));
+        st_v(cop, pack<double, EPT>(co));
     } else {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) acc[v][j] = (e0 + v * VS + j < sg.numel) ? ld1(base + v * VS + j) : 0.0;
+        for (int j = 0; j < EPT; ++j) acc[j] = (e0 + j < sg.numel) ? ld1(base + j) : 0.0;
         reduce_clients<DT, 1, false>(acc, false, cp, n_clients, nullptr, r64, e0, sg.numel, coff);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) {
-                const int64_t o = v * VS + j;
-                if (e0 + o >= sg.numel) continue;
-                double mj = zero_state ? 0.0 : ld1(mp + o), vj = zero_state ? 0.0 : ld1(vp + o), cj;
-                adapt_elem_f64<VARIANT>(acc[v][j], cur_avg ? acc[v][j] : ld1(curp + o), mj, vj, cj, h);
-                if (ap) st1(ap + o, acc[v][j]);
-                st1(mp + o, mj);
-                st1(vp + o, vj);
-                st1(cop + o, cj);
-            }
+        for (int j = 0; j < EPT; ++j) {
+            if (e0 + j >= sg.numel) continue;
+            double mj = zero_state ? 0.0 : ld1(mp + j), vj = zero_state ? 0.0 : ld1(vp + j), cj;
+            adapt_elem_f64<VARIANT>(acc[j], cur_avg ? acc[j] : ld1(curp + j), mj, vj, cj, h);
+            if (ap) st1(ap + j, acc[j]);
+            st1(mp + j, mj);
+            st1(vp + j, vj);
+            st1(cop + j, cj);
+        }
     }
 }
 
@@ -2568,7 +2522,6 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel_f64(const flame_se
                                                                   const uint8_t* __restrict__ step_end,
                                                                   unsigned flags, const Hyper64 h) {
     constexpr int DT = FLAME_F64;
-    static_assert(kVPT == 1, "fedopt_chain_kernel_f64: a lane handles one 16-byte vector of its chunk");
     const int64_t chunk = blockIdx.x;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_segment sg = segs[s];
@@ -2684,69 +2637,56 @@ __device__ __forceinline__ void hier_tail(const flame_hier_segment& sg, int64_t 
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     (void)wrow;
-    A top[kVPT][EPT];
+    A top[EPT];
     bool have_top = (flags & FLAME_HIER_TOP_ACCUM) != 0;
     const T* tin = reinterpret_cast<const T*>(sg.top_agg_in) + e0;
 #pragma unroll
-    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int64_t o = v * VS + j;
-            if (have_top && e0 + o < sg.numel) top[v][j] = X::ld(ld1(tin + o));
-        }
+    for (int j = 0; j < EPT; ++j)
+        if (have_top && e0 + j < sg.numel) top[j] = X::ld(ld1(tin + j));
 #pragma unroll 1
     for (int m = 0; m < n_mids; ++m) {
-        A acc[kVPT][EPT];
+        A acc[EPT];
         T* wp = mid_ptr(m);
         if constexpr (SYNC) {
 #pragma unroll
-            for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-                for (int j = 0; j < EPT; ++j)
-                    acc[v][j] = (e0 + v * VS + j < sg.numel) ? X::ld(ld1(wp + v * VS + j)) : A(0);
+            for (int j = 0; j < EPT; ++j)
+                acc[j] = (e0 + j < sg.numel) ? X::ld(ld1(wp + j)) : A(0);
         }
         reduce_clients<DT, 1, false>(acc, !SYNC, crow + static_cast<int64_t>(m) * n_clients, n_clients,
                                      mid_rates + static_cast<int64_t>(m) * n_clients, nullptr, e0, sg.numel, coff);
         T* dp = (drow && drow[m]) ? reinterpret_cast<T*>(drow[m]) + e0 : nullptr;
         const float g = mid_goal[m], rt = top_rates[m];
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) {
-                const int64_t o = v * VS + j;
-                if (e0 + o >= sg.numel) continue;
-                T w = ld1(wp + o), d;
-                if constexpr (SYNC) {
-                    const T wn = X::st(acc[v][j]);
-                    d = X::st(rnd<DT>(__fsub_rn(X::ld(wn), X::ld(w))));
-                    w = wn;
-                } else {
-                    S::op(w, X::st(acc[v][j]), g, static_cast<double>(g), &d);
-                }
-                if (!(flags & FLAME_HIER_MID_READONLY)) st1(wp + o, w);
-                if (dp) st1(dp + o, d);
-                const A t = X::tmp(d, rt, 0.0);
-                top[v][j] = have_top ? X::add(top[v][j], t) : t;
+        for (int j = 0; j < EPT; ++j) {
+            if (e0 + j >= sg.numel) continue;
+            T w = ld1(wp + j), d;
+            if constexpr (SYNC) {
+                const T wn = X::st(acc[j]);
+                d = X::st(rnd<DT>(__fsub_rn(X::ld(wn), X::ld(w))));
+                w = wn;
+            } else {
+                S::op(w, X::st(acc[j]), g, static_cast<double>(g), &d);
             }
+            if (!(flags & FLAME_HIER_MID_READONLY)) st1(wp + j, w);
+            if (dp) st1(dp + j, d);
+            const A t = X::tmp(d, rt, 0.0);
+            top[j] = have_top ? X::add(top[j], t) : t;
+        }
         have_top = true;
     }
 #pragma unroll
-    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int64_t o = v * VS + j;
-            if (e0 + o >= sg.numel) continue;
-            const T t = X::st(top[v][j]);
-            if (sg.top_agg_out) st1(reinterpret_cast<T*>(sg.top_agg_out) + e0 + o, t);
-            if (flags & FLAME_HIER_TOP_APPLY) {
-                T* gp = reinterpret_cast<T*>(sg.top_w) + e0 + o;
-                T gw = ld1(gp);
-                S::op(gw, t, top_goal, static_cast<double>(top_goal), nullptr);
-                st1(gp, gw);
-            }
+    for (int j = 0; j < EPT; ++j) {
+        if (e0 + j >= sg.numel) continue;
+        const T t = X::st(top[j]);
+        if (sg.top_agg_out) st1(reinterpret_cast<T*>(sg.top_agg_out) + e0 + j, t);
+        if (flags & FLAME_HIER_TOP_APPLY) {
+            T* gp = reinterpret_cast<T*>(sg.top_w) + e0 + j;
+            T gw = ld1(gp);
+            S::op(gw, t, top_goal, static_cast<double>(top_goal), nullptr);
+            st1(gp, gw);
         }
+    }
 }
 
 // (HL instantiations: the middle loop stays rolled -- its group lives in LDS, not registers)
@@ -2766,7 +2706,6 @@ __device__ __forceinline__ void hier_fedbuff_body(const flame_hier_segment* __re
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     const int64_t chunk = blockIdx.x;
     const int s = find_segment(segs, n_segs, chunk);
     const flame_hier_segment sg = segs[s];
@@ -2776,76 +2715,72 @@ __device__ __forceinline__ void hier_fedbuff_body(const flame_hier_segment* __re
     const uint64_t* wrow = mid_w + static_cast<int64_t>(s) * n_mids;
     const uint64_t* drow = mid_delta ? mid_delta + static_cast<int64_t>(s) * n_mids : nullptr;
     const uint64_t* crow = clients + static_cast<int64_t>(s) * n_mids * n_clients;
-    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
     // byte offset of this lane's elements inside every middle's weights: contiguous or tiled
     const int64_t woff = sg.mid_tile_stride
         ? (chunk - sg.chunk_begin) * sg.mid_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * sizeof(T)
         : e0 * static_cast<int64_t>(sizeof(T));
     auto mid_ptr = [&](int m) { return reinterpret_cast<T*>(reinterpret_cast<char*>(wrow[m]) + woff); };
-    A top[kVPT][EPT];
+    A top[EPT];
     bool have_top = (flags & FLAME_HIER_TOP_ACCUM) != 0;
     const T* tin = reinterpret_cast<const T*>(sg.top_agg_in) + e0;
     if (vec) {
         if (have_top) {
+            T b[EPT];
+            unpack<T, EPT>(ld_v(tin), b);
 #pragma unroll
-            for (int v = 0; v < kVPT; ++v) {
-                T b[EPT];
-                unpack<T, EPT>(ld_v(tin + v * VS), b);
-#pragma unroll
-                for (int j = 0; j < EPT; ++j) top[v][j] = X::ld(b[j]);
-            }
+            for (int j = 0; j < EPT; ++j) top[j] = X::ld(b[j]);
         }
         // middles in groups of HB: a group's middle-weight stores are issued together after its
         // reductions (1 = store each middle's weights right after its reduction).  HL: the group's
         // weights wait in LDS (lane-private slots, no barrier) rather than in registers -- long
         // store bursts at 2 workgroups per CU
-        __shared__ V16 held[HL ? HB * kVPT * kBlock : 1];
+        __shared__ V16 held[HL ? HB * kBlock : 1];
 #pragma unroll 1
         for (int m0 = 0; m0 < n_mids; m0 += HB) {
-            V16 pend[HL ? 1 : HB][kVPT];
+            V16 pend[HL ? 1 : HB];
             const int nb = n_mids - m0 < HB ? n_mids - m0 : HB;   // middles in this group
 #pragma unroll
             for (int u = 0; u < HB; ++u) {
             const int m = m0 + u;
             if (HB > 1 && m >= n_mids) break;
             T* wp = mid_ptr(m);
-            A acc[kVPT][EPT];
-            T wo[SYNC ? kVPT : 1][EPT];
+            A acc[EPT];
+            T wo[EPT];
             if constexpr (SYNC) {     // FedAvg starts from the middle's weights (deepcopy(self.weights))
+                unpack<T, EPT>(ld_v(wp), wo);
 #pragma unroll
-                for (int v = 0; v < kVPT; ++v) {
-                    unpack<T, EPT>(ld_v(wp + v * VS), wo[v]);
-#pragma unroll
-                    for (int j = 0; j < EPT; ++j) acc[v][j] = X::ld(wo[v][j]);
-                }
+                for (int j = 0; j < EPT; ++j) acc[j] = X::ld(wo[j]);
             }
             reduce_clients<DT, CU, true>(acc, !SYNC, crow + static_cast<int64_t>(m) * n_clients, n_clients,
                                          mid_rates + static_cast<int64_t>(m) * n_clients, nullptr, e0, sg.numel,
                                          coff);
             T* dp = (drow && drow[m]) ? reinterpret_cast<T*>(drow[m]) + e0 : nullptr;
             const float g = mid_goal[m], rt = top_rates[m];
+            // A one-trip loop on purpose (as in fedopt_chunk): without it the group loop compiles to
+            // another schedule, measured 0.4 % slower on config 5 (profiles/vpt_isa_diff.log)
 #pragma unroll
-            for (int v = 0; v < kVPT; ++v) {
+            for (int once = 0; once < 1; ++once) {
                 T w[EPT], d[EPT];
                 if constexpr (SYNC) {
 #pragma unroll
                     for (int j = 0; j < EPT; ++j) {
-                        w[j] = X::st(acc[v][j]);
-                        d[j] = X::st(rnd<DT>(__fsub_rn(X::ld(w[j]), X::ld(wo[v][j]))));
-                        top[v][j] = X::add(top[v][j], X::tmp(d[j], rt, 0.0));
+                        w[j] = X::st(acc[j]);
+                        d[j] = X::st(rnd<DT>(__fsub_rn(X::ld(w[j]), X::ld(wo[j]))));
+                        top[j] = X::add(top[j], X::tmp(d[j], rt, 0.0));
                     }
                 } else {
-                    unpack<T, EPT>(ld_v(wp + v * VS), w);
+                    unpack<T, EPT>(ld_v(wp), w);
 #pragma unroll
                     for (int j = 0; j < EPT; ++j) {
-                        S::op(w[j], X::st(acc[v][j]), g, static_cast<double>(g), &d[j]);
+                        S::op(w[j], X::st(acc[j]), g, static_cast<double>(g), &d[j]);
                         const A t = X::tmp(d[j], rt, 0.0);
-                        top[v][j] = have_top ? X::add(top[v][j], t) : t;
+                        top[j] = have_top ? X::add(top[j], t) : t;
                     }
                 }
-                if constexpr (HL) held[(u * kVPT + v) * kBlock + threadIdx.x] = pack<T, EPT>(w);
-                else pend[u][v] = pack<T, EPT>(w);
-                if (dp) st_v(dp + v * VS, pack<T, EPT>(d));
+                if constexpr (HL) held[u * kBlock + threadIdx.x] = pack<T, EPT>(w);
+                else pend[u] = pack<T, EPT>(w);
+                if (dp) st_v(dp, pack<T, EPT>(d));
             }
             have_top = true;
             }
@@ -2854,30 +2789,24 @@ __device__ __forceinline__ void hier_fedbuff_body(const flame_hier_segment* __re
                 for (int u = 0; u < HB; ++u) {
                     if (u >= nb) break;
                     T* wp = mid_ptr(m0 + u);       // re-read from the (scalar) pointer table
-#pragma unroll
-                    for (int v = 0; v < kVPT; ++v) {
-                        V16 pv;
-                        if constexpr (HL) pv = held[(u * kVPT + v) * kBlock + threadIdx.x];
-                        else pv = pend[u][v];
-                        st_v(wp + v * VS, pv);
-                    }
+                    V16 pv;
+                    if constexpr (HL) pv = held[u * kBlock + threadIdx.x];
+                    else pv = pend[u];
+                    st_v(wp, pv);
                 }
             }
         }
+        T o[EPT];
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            T o[EPT];
+        for (int j = 0; j < EPT; ++j) o[j] = X::st(top[j]);
+        if (sg.top_agg_out) st_v(reinterpret_cast<T*>(sg.top_agg_out) + e0, pack<T, EPT>(o));
+        if (flags & FLAME_HIER_TOP_APPLY) {
+            T* gp = reinterpret_cast<T*>(sg.top_w) + e0;
+            T gw[EPT];
+            unpack<T, EPT>(ld_v(gp), gw);
 #pragma unroll
-            for (int j = 0; j < EPT; ++j) o[j] = X::st(top[v][j]);
-            if (sg.top_agg_out) st_v(reinterpret_cast<T*>(sg.top_agg_out) + e0 + v * VS, pack<T, EPT>(o));
-            if (flags & FLAME_HIER_TOP_APPLY) {
-                T* gp = reinterpret_cast<T*>(sg.top_w) + e0 + v * VS;
-                T gw[EPT];
-                unpack<T, EPT>(ld_v(gp), gw);
-#pragma unroll
-                for (int j = 0; j < EPT; ++j) S::op(gw[j], o[j], top_goal, static_cast<double>(top_goal), nullptr);
-                st_v(gp, pack<T, EPT>(gw));
-            }
+            for (int j = 0; j < EPT; ++j) S::op(gw[j], o[j], top_goal, static_cast<double>(top_goal), nullptr);
+            st_v(gp, pack<T, EPT>(gw));
         }
         return;
     }
@@ -2935,41 +2864,32 @@ __device__ __forceinline__ void feddyn_chunk(const flame_dyn_segment& sg, const 
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     const int64_t ooff = e0 * static_cast<int64_t>(sizeof(T));   // base / average / cld: contiguous
-    auto load = [&](uint64_t base, int64_t off, T (&x)[kVPT][EPT]) {
+    auto load = [&](uint64_t base, int64_t off, T (&x)[EPT]) {
         const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+        if constexpr (VEC) {
+            unpack<T, EPT>(ld_nt(p), x);
+        } else {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            if constexpr (VEC) {
-                unpack<T, EPT>(ld_nt(p + v * VS), x[v]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < EPT; ++j) x[v][j] = (e0 + v * VS + j < sg.numel) ? ld1(p + v * VS + j) : T(0);
-            }
+            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < sg.numel) ? ld1(p + j) : T(0);
         }
     };
-    auto store = [&](void* base, int64_t off, const T (&x)[kVPT][EPT]) {
+    auto store = [&](void* base, int64_t off, const T (&x)[EPT]) {
         T* p = reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off);
+        if constexpr (VEC) {
+            st_v(p, pack<T, EPT>(x));
+        } else {
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v) {
-            if constexpr (VEC) {
-                st_v(p + v * VS, pack<T, EPT>(x[v]));
-            } else {
-#pragma unroll
-                for (int j = 0; j < EPT; ++j)
-                    if (e0 + v * VS + j < sg.numel) st1(p + v * VS + j, x[v][j]);
-            }
+            for (int j = 0; j < EPT; ++j)
+                if (e0 + j < sg.numel) st1(p + j, x[j]);
         }
     };
-    A avg[kVPT][EPT], mean[kVPT][EPT];
+    A avg[EPT], mean[EPT];
     {
-        T b[kVPT][EPT];
+        T b[EPT];
         load(reinterpret_cast<uint64_t>(sg.in), ooff, b);
 #pragma unroll
-        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) { avg[v][j] = X::ld(b[v][j]); mean[v][j] = A(0); }
+        for (int j = 0; j < EPT; ++j) { avg[j] = X::ld(b[j]); mean[j] = A(0); }
     }
 #pragma unroll 1
     for (int phase = 0; phase < 2; ++phase) {
@@ -2977,7 +2897,7 @@ __device__ __forceinline__ void feddyn_chunk(const flame_dyn_segment& sg, const 
 #pragma unroll 1
         for (int k = phase ? n_phase1 : 0; k < end; k += CU) {
             const int nb = (end - k < CU) ? end - k : CU;
-            T w[CU][kVPT][EPT], h[CU][kVPT][EPT];
+            T w[CU][EPT], h[CU][EPT];
 #pragma unroll
             for (int u = 0; u < CU; ++u) {
                 if (u >= nb) break;
@@ -2992,38 +2912,28 @@ __device__ __forceinline__ void feddyn_chunk(const flame_dyn_segment& sg, const 
                 const uint32_t f = sflags[k + u];
                 if (f & FLAME_DYN_AVG) {
 #pragma unroll
-                    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-                        for (int j = 0; j < EPT; ++j) avg[v][j] = X::add(avg[v][j], X::tmp(w[u][v][j], ra32, ra64));
+                    for (int j = 0; j < EPT; ++j) avg[j] = X::add(avg[j], X::tmp(w[u][j], ra32, ra64));
                 }
                 if (f & FLAME_DYN_HOUT) {
                     if (f & FLAME_DYN_HIN) {
 #pragma unroll
-                        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-                            for (int j = 0; j < EPT; ++j) h[u][v][j] = X::st(X::add(X::ld(h[u][v][j]), X::ld(w[u][v][j])));
+                        for (int j = 0; j < EPT; ++j) h[u][j] = X::st(X::add(X::ld(h[u][j]), X::ld(w[u][j])));
                     } else {
 #pragma unroll
-                        for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-                            for (int j = 0; j < EPT; ++j) h[u][v][j] = w[u][v][j];
+                        for (int j = 0; j < EPT; ++j) h[u][j] = w[u][j];
                     }
                     store(reinterpret_cast<void*>(row[static_cast<int64_t>(k + u) * 3 + 2]), hoff, h[u]);
                 }
                 if (f & FLAME_DYN_MEAN) {
 #pragma unroll
-                    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-                        for (int j = 0; j < EPT; ++j) mean[v][j] = X::add(mean[v][j], X::tmp(h[u][v][j], rm32, rm64));
+                    for (int j = 0; j < EPT; ++j) mean[j] = X::add(mean[j], X::tmp(h[u][j], rm32, rm64));
                 }
             }
         }
     }
-    T o[kVPT][EPT], c[kVPT][EPT];
+    T o[EPT], c[EPT];
 #pragma unroll
-    for (int v = 0; v < kVPT; ++v)
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) { o[v][j] = X::st(avg[v][j]); c[v][j] = X::st(X::add(avg[v][j], mean[v][j])); }
+    for (int j = 0; j < EPT; ++j) { o[j] = X::st(avg[j]); c[j] = X::st(X::add(avg[j], mean[j])); }
     store(sg.out, ooff, o);
     store(sg.cld, ooff, c);
 }
@@ -3036,7 +2946,6 @@ __global__ __launch_bounds__(kBlock) void feddyn_kernel(const flame_dyn_segment*
                                                         double rm64) {
     using X = Tr<DT>;
     constexpr int EPT = X::EPT;
-    constexpr int64_t VS = static_cast<int64_t>(kBlock) * EPT;
     // XCD-contiguous chunk map: 512 x 12M fp32 -0.7 % (cache order) / -1.4 % (other order)
     // (profiles/r02_feddyn_xcd_sweep.log)
     const int64_t chunk = xcd_slot(blockIdx.x, gridDim.x);
@@ -3050,7 +2959,7 @@ __global__ __launch_bounds__(kBlock) void feddyn_kernel(const flame_dyn_segment*
         ? (chunk - sg.chunk_begin) * sg.hist_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * static_cast<int64_t>(sizeof(typename X::T))
         : e0 * static_cast<int64_t>(sizeof(typename X::T));
     const uint64_t* row = steps + static_cast<int64_t>(s) * n_steps * 3;
-    const bool vec = (e0 + (kVPT - 1) * VS + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
     if (vec)
         feddyn_chunk<DT, CU, true>(sg, row, sflags, n_steps, n_phase1, ra32, rm32, ra64, rm64, e0, coff, hoff);
     else
@@ -3606,6 +3515,35 @@ int check_flags(const char* who, unsigned flags, unsigned allowed) {
     if (flags & ~allowed) return set_err(FLAME_EINVAL, "%s: unknown flags 0x%x", who, flags);
     return FLAME_OK;
 }
+// The table entry points outside the launch-branch table name themselves in every refusal
+int need_segs(const char* who, const flame_segment* segs, int32_t n_segs) {
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    return FLAME_OK;
+}
+int need_clients(const char* who, const void* clients) {
+    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    return FLAME_OK;
+}
+int no_int_dtype(const char* who, int dtype) {
+    if (dtype == FLAME_I64 || dtype == FLAME_I32)
+        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    return FLAME_OK;
+}
+int float_dtype(const char* who, int dtype) {
+    if (int rc = no_int_dtype(who, dtype)) return rc;
+    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    return FLAME_OK;
+}
+int no_seg_rates(const char* who, unsigned flags) {
+    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    return FLAME_OK;
+}
+int need_scratch(const char* who, const void* scratch, int64_t bytes, int64_t need) {
+    if (!scratch || bytes < need)
+        return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
+                       static_cast<long long>(bytes), static_cast<long long>(need));
+    return FLAME_OK;
+}
 
 int validate(const flame_segment* segs, int32_t n_segs, int64_t n_chunks, int32_t n_clients, const void* clients) {
     if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "segment table is NULL or n_segs <= 0");
@@ -3886,10 +3824,9 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment* segs
                             const double* rates64, const float* scales32, const double* scales64, void* stream) {
     const char* const who = "flame_agg_reduce_scaled";
     if (int rc = validate(segs, n_segs, n_chunks, n_clients, clients)) return rc;
-    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
     if (int rc = check_agg_flags(who, flags, n_clients)) return rc;
-    if (dtype == FLAME_I64 || dtype == FLAME_I32)
-        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
+    if (int rc = no_int_dtype(who, dtype)) return rc;
     const bool f64 = dtype == FLAME_F64;
     if (n_clients > 0 && !(f64 ? rates64 : static_cast<const void*>(rates32))) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
     if (n_clients > 0 && !(f64 ? scales64 : static_cast<const void*>(scales32))) return set_err(FLAME_EINVAL, "%s: scale array is NULL", who);
@@ -3914,14 +3851,14 @@ int flame_agg_reduce_mixed(int client_dtype, int agg_dtype, unsigned flags, cons
     if (!is16(client_dtype) || agg_dtype != FLAME_F32)
         return set_err(FLAME_ENOTSUP, "%s: client dtype %d into aggregate dtype %d is not supported (bf16 or f16 into f32 only)",
                        who, client_dtype, agg_dtype);
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
     if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
-    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (int rc = need_clients(who, clients)) return rc;
     if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
     if (flags & FLAME_AGG_INIT_FIRST)
         return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (a None-start aggregate takes the update's dtype)", who);
-    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
     if (int rc = check_flags(who, flags, FLAME_AGG_XCD_MAP)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const uint64_t* cl = reinterpret_cast<const uint64_t*>(clients);
@@ -3945,19 +3882,17 @@ int flame_agg_trimmed_max_k(void) { return kTrimMaxK; }
 int flame_agg_trimmed(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
                       const void* const* clients, int32_t n_clients, int32_t trim_k, void* stream) {
     const char* const who = "flame_agg_trimmed";
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (int rc = check_chunks(n_chunks)) return rc;
-    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (int rc = need_clients(who, clients)) return rc;
     if (trim_k < 0 || trim_k > kTrimMaxK)
         return set_err(trim_k < 0 ? FLAME_EINVAL : FLAME_ENOTSUP, "%s: trim_k %d outside [0, %d] (flame_agg_trimmed_max_k)", who,
                        trim_k, kTrimMaxK);
     if (n_clients <= 2 * trim_k)
         return set_err(FLAME_EINVAL, "%s: n_clients %d must exceed 2 * trim_k = %d", who, n_clients, 2 * trim_k);
-    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
     if (int rc = check_flags(who, flags, FLAME_AGG_INIT_FIRST | FLAME_AGG_XCD_MAP)) return rc;
-    if (dtype == FLAME_I64 || dtype == FLAME_I32)
-        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
-    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (int rc = float_dtype(who, dtype)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     constexpr int kCaps[] = {1, 2, 3, 4, 6, 8, 12, 16};      // a round pays for KT stages, not for trim_k
     static_assert(kCaps[7] == kTrimMaxK, "the capacities end at kTrimMaxK");
@@ -3981,9 +3916,9 @@ int flame_agg_select_max_clients(void) { return kSelectMaxClients; }
 int flame_agg_select(int dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
                      const void* const* clients, int32_t n_clients, int32_t trim_k, void* stream) {
     const char* const who = "flame_agg_select";
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (int rc = check_chunks(n_chunks)) return rc;
-    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
+    if (int rc = need_clients(who, clients)) return rc;
     if (trim_k < 0) return set_err(FLAME_EINVAL, "%s: trim_k %d is negative", who, trim_k);
     if (n_clients > kSelectMaxClients)
         return set_err(FLAME_ENOTSUP, "%s: n_clients %d exceeds %d (flame_agg_select_max_clients)", who, n_clients,
@@ -3991,11 +3926,9 @@ int flame_agg_select(int dtype, unsigned flags, const flame_segment* segs, int32
     if (static_cast<int64_t>(n_clients) <= 2 * static_cast<int64_t>(trim_k))
         return set_err(FLAME_EINVAL, "%s: n_clients %d must exceed 2 * trim_k = %lld", who, n_clients,
                        2 * static_cast<long long>(trim_k));
-    if (flags & FLAME_AGG_SEG_RATES) return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_SEG_RATES is not supported", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
     if (int rc = check_flags(who, flags, FLAME_AGG_INIT_FIRST | FLAME_AGG_XCD_MAP)) return rc;
-    if (dtype == FLAME_I64 || dtype == FLAME_I32)
-        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
-    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (int rc = float_dtype(who, dtype)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
         hipLaunchKernelGGL((agg_select_kernel<decltype(dt)::value>), dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0,
@@ -4014,18 +3947,13 @@ int64_t flame_update_stats_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
 static int launch_stats(const char* who, bool cen, int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
                         const void* const* clients, int32_t n_clients, double* sums, int64_t* nonfinite, void* scratch,
                         int64_t scratch_bytes, void* stream) {
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (int rc = check_chunks(n_chunks)) return rc;
     if (n_clients <= 0) return set_err(FLAME_EINVAL, "%s: n_clients <= 0", who);
-    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
-    if (dtype == FLAME_I64 || dtype == FLAME_I32)
-        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
-    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (int rc = need_clients(who, clients)) return rc;
+    if (int rc = float_dtype(who, dtype)) return rc;
     if (!sums || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
-    const int64_t need = flame_update_stats_scratch_bytes(n_chunks, n_clients);
-    if (!scratch || scratch_bytes < need)
-        return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
-                       static_cast<long long>(scratch_bytes), static_cast<long long>(need));
+    if (int rc = need_scratch(who, scratch, scratch_bytes, flame_update_stats_scratch_bytes(n_chunks, n_clients))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t n_wg = (n_chunks + kStatR - 1) / kStatR;
     dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64>(dtype, [&](auto dt) {
@@ -4076,21 +4004,16 @@ int flame_update_gram(int dtype, const flame_segment* segs, int32_t n_segs, int6
                       const void* const* clients, int32_t n_clients, double* gram, int64_t* nonfinite,
                       void* scratch, int64_t scratch_bytes, void* stream) {
     const char* const who = "flame_update_gram";
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (int rc = check_chunks(n_chunks)) return rc;
     if (n_clients <= 0) return set_err(FLAME_EINVAL, "%s: n_clients <= 0", who);
     if (n_clients > kGramMaxClients)
         return set_err(FLAME_ENOTSUP, "%s: n_clients %d exceeds %d (flame_update_gram_max_clients)", who, n_clients,
                        kGramMaxClients);
-    if (!clients) return set_err(FLAME_EINVAL, "%s: client pointer table is NULL", who);
-    if (dtype == FLAME_I64 || dtype == FLAME_I32)
-        return set_err(FLAME_ENOTSUP, "%s: integer dtype %d not supported (float dtypes only)", who, dtype);
-    if (dtype < FLAME_F32 || dtype > FLAME_F64) return set_err(FLAME_ENOTSUP, "%s: unknown dtype %d", who, dtype);
+    if (int rc = need_clients(who, clients)) return rc;
+    if (int rc = float_dtype(who, dtype)) return rc;
     if (!gram || !nonfinite) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
-    const int64_t need = flame_update_gram_scratch_bytes(n_chunks, n_clients);
-    if (!scratch || scratch_bytes < need)
-        return set_err(FLAME_EINVAL, "%s: scratch buffer is NULL or too small (%lld bytes, %lld needed)", who,
-                       static_cast<long long>(scratch_bytes), static_cast<long long>(need));
+    if (int rc = need_scratch(who, scratch, scratch_bytes, flame_update_gram_scratch_bytes(n_chunks, n_clients))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t range = gram_range(n_chunks, n_clients);
     const int64_t n_ranges = (n_chunks + range - 1) / range;
@@ -4343,7 +4266,7 @@ int flame_synth_fill(int dtype, void* out, int64_t numel, uint64_t seed, uint64_
 int flame_noise_fill(int dtype, const flame_segment* segs, int32_t n_segs, int64_t n_chunks, const uint32_t* streams,
                      const int64_t* starts, uint64_t seed, uint32_t round, double std, void* stream) {
     const char* const who = "flame_noise_fill";
-    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
     if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll)
         return set_err(FLAME_EINVAL, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
     if (dtype == FLAME_I64 || dtype == FLAME_I32)

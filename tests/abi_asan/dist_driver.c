@@ -1,6 +1,6 @@
 /* Host sanitizer run of flame_update_dist / flame_update_dist_scratch_bytes: built against a copy
  * of libflame_amd.so whose HOST code is compiled with -fsanitize=address,undefined
- * (tests/abi_asan_dist/Makefile).  Every launch call carries at least one invalid argument and
+ * (tests/abi_asan/Makefile).  Every launch call carries at least one invalid argument and
  * must be refused on the host with an error code and a message, before any HIP call, without a
  * sanitizer report.  No GPU is needed. */
 #include <stdint.h>

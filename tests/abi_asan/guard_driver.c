@@ -1,6 +1,6 @@
 /* Host sanitizer run of the update guard's two entry points (flame_update_stats,
  * flame_agg_reduce_scaled): built against a copy of libflame_amd.so whose HOST code is compiled
- * with -fsanitize=address,undefined (tests/abi_asan_guard/Makefile).  Every call carries at least
+ * with -fsanitize=address,undefined (tests/abi_asan/Makefile).  Every call carries at least
  * one invalid argument and must be refused on the host with an error code and a message, before
  * any HIP call, without a sanitizer report.  No GPU is needed. */
 #include <stdint.h>

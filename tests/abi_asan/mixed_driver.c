@@ -1,5 +1,5 @@
 /* Host sanitizer run of flame_agg_reduce_mixed: built against a copy of libflame_amd.so whose HOST
- * code is compiled with -fsanitize=address,undefined (tests/abi_asan_mixed/Makefile).  Every call
+ * code is compiled with -fsanitize=address,undefined (tests/abi_asan/Makefile).  Every call
  * carries at least one invalid argument and must be refused on the host with an error code and a
  * message naming the entry point, before any HIP call, without a sanitizer report.  No GPU is
  * needed. */

@@ -1,5 +1,5 @@
 /* Host sanitizer run of flame_noise_fill: built against a copy of libflame_amd.so whose HOST code is
- * compiled with -fsanitize=address,undefined (tests/abi_asan_noise/Makefile).  Every call carries at
+ * compiled with -fsanitize=address,undefined (tests/abi_asan/Makefile).  Every call carries at
  * least one invalid argument and must be refused on the host with an error code and a message, before
  * any HIP call, without a sanitizer report.  No GPU is needed. */
 #include <math.h>

@@ -2,14 +2,15 @@
 and the export list still agree, the launch-branch table is unchanged (the entry point stands
 outside it, as the statistics' does), every invalid call is refused with a code and a message
 before any HIP call, and there is no client cap.  Then the same validation under ASan + UBSan from
-a stand-alone C driver (tests/abi_asan_dist).  No GPU call, and no sanitizer inside Python."""
+a stand-alone C driver (tests/abi_asan/dist_driver.c).  No GPU call, and no sanitizer inside Python."""
 import ctypes
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -84,9 +85,8 @@ def test_dist_validates_without_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_dist_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_dist"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_dist_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("dist_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "dist abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -3,14 +3,15 @@ the symbols resolve, the header and the export list still agree, the launch-bran
 unchanged (the entry point stands outside it, as the update guard's do), every invalid call is
 refused with a code and a message before any HIP call, and the scratch bound is monotone and at most
 1 GiB.  Then the same validation under ASan + UBSan from a stand-alone C driver
-(tests/abi_asan_gram).  No GPU call."""
+(tests/abi_asan/gram_driver.c).  No GPU call."""
 import ctypes
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GIB = 1 << 30
@@ -94,9 +95,8 @@ def test_gram_validates_without_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_gram_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_gram"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_gram_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("gram_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "gram abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

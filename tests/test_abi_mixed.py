@@ -1,15 +1,16 @@
 """flame_agg_reduce_mixed on the host: the symbol resolves, the header and the export list agree,
 the launch-branch table and the ABI version are unchanged, every refusal comes with its code and a
 message naming the entry point before any HIP call.  Then the same validation under ASan + UBSan
-from a stand-alone C driver (tests/abi_asan_mixed).  No GPU call, and no sanitizer inside Python."""
+from a stand-alone C driver (tests/abi_asan/mixed_driver.c).  No GPU call, and no sanitizer inside Python."""
 import ctypes
 import itertools
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WHO = b"flame_agg_reduce_mixed"
@@ -75,9 +76,8 @@ def test_mixed_refuses_without_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_mixed_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_mixed"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_mixed_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("mixed_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "mixed abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -2,17 +2,18 @@
 launch-branch table and the ABI version are unchanged (the entry point stands outside the table, as
 the statistics' and the synthetic fill's do), every invalid call is refused with a code and a message
 before any HIP call -- and what lives in device memory (the starts) is refused by the planner.  Then
-the same validation under ASan + UBSan from a stand-alone C driver (tests/abi_asan_noise).  No GPU
+the same validation under ASan + UBSan from a stand-alone C driver (tests/abi_asan/noise_driver.c).  No GPU
 call, and no sanitizer inside Python."""
 import ctypes
 import math
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -102,9 +103,8 @@ def test_the_planner_refuses_what_lives_in_device_memory():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_noise_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_noise"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_noise_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("noise_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "noise abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -1,15 +1,16 @@
 """flame_agg_select / flame_agg_select_max_clients on the host: the symbols resolve, the header and
 the export list agree, the launch-branch table and the chain kernel's capacity are unchanged, every
 invalid call is refused with a code and a message before any HIP call.  Then the same validation
-under ASan + UBSan from a stand-alone C driver (tests/abi_asan_select).  No GPU call, and no
+under ASan + UBSan from a stand-alone C driver (tests/abi_asan/select_driver.c).  No GPU call, and no
 sanitizer inside Python."""
 import ctypes
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -74,9 +75,8 @@ def test_select_validates_without_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_select_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_select"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_select_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("select_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "select abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -1,13 +1,14 @@
 """flame_agg_trimmed / flame_agg_trimmed_max_k on the host: the symbols resolve, the launch-branch
 table is unchanged (the entry point stands outside it, as the update guard's two do), every
 invalid call is refused with a code and a message before any HIP call.  Then the same validation
-under ASan + UBSan from a stand-alone C driver (tests/abi_asan_trimmed).  No GPU call."""
+under ASan + UBSan from a stand-alone C driver (tests/abi_asan/trimmed_driver.c).  No GPU call."""
 import ctypes
 import os
 import shutil
-import subprocess
 
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -64,9 +65,8 @@ def test_trimmed_validates_without_gpu():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_trimmed_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_trimmed"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=900)
+def test_trimmed_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("trimmed_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "trimmed abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

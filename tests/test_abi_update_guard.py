@@ -2,14 +2,15 @@
 flame_agg_reduce_scaled) on the host: the symbols resolve, every invalid call is refused with a
 code and a message before any HIP call, the launch-branch table is unchanged (the two entry points
 stand outside it), and engine.plan carries the clip scales as it carries the rates.  Then the same
-validation under ASan + UBSan from a stand-alone C driver (tests/abi_asan_guard).  No GPU call."""
+validation under ASan + UBSan from a stand-alone C driver (tests/abi_asan/guard_driver.c).  No GPU call."""
 import ctypes
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import asan_drivers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -120,9 +121,8 @@ def test_plan_carries_scales_like_rates():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shutil.which("make") is None,
                     reason="hipcc / make not available")
-def test_guard_abi_validation_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "abi_asan_guard"), f"OUT={tmp_path}"],
-                       capture_output=True, text=True, timeout=600)
+def test_guard_abi_validation_under_asan_ubsan():
+    r = asan_drivers.run_driver("guard_driver")
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "guard abi asan OK" in r.stdout
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

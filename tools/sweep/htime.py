@@ -62,15 +62,15 @@ EDITS = [
      "            reduce_clients<DT, CU, true>(acc, !SYNC, crow + static_cast<int64_t>(m) * n_clients, n_clients,\n"
      "                                         mid_rates + static_cast<int64_t>(m) * n_clients, nullptr, e0, sg.numel,\n"
      f"                                         coff);\n            FLAME_HT({W0}, 3 + 2 * m);\n"),
-    ("                if (dp) st_v(dp + v * VS, pack<T, EPT>(d));\n            }\n            have_top = true;\n            }\n",
-     "                if (dp) st_v(dp + v * VS, pack<T, EPT>(d));\n            }\n            have_top = true;\n"
+    ("                if (dp) st_v(dp, pack<T, EPT>(d));\n            }\n            have_top = true;\n            }\n",
+     "                if (dp) st_v(dp, pack<T, EPT>(d));\n            }\n            have_top = true;\n"
      f"            FLAME_HT({W0}, 4 + 2 * m);\n            }}\n"),
-    ("                        st_v(wp + v * VS, pv);\n                    }\n                }\n            }\n        }\n",
-     "                        st_v(wp + v * VS, pv);\n                    }\n                }\n            }\n"
+    ("                    st_v(wp, pv);\n                }\n            }\n        }\n",
+     "                    st_v(wp, pv);\n                }\n            }\n"
      f"            FLAME_HT({W0}, 3 + 2 * n_mids + m0 / HB);\n        }}\n"),
-    ("                st_v(gp, pack<T, EPT>(gw));\n            }\n        }\n        return;\n    }\n"
+    ("            st_v(gp, pack<T, EPT>(gw));\n        }\n        return;\n    }\n"
      "    hier_tail<DT, SYNC>(",
-     "                st_v(gp, pack<T, EPT>(gw));\n            }\n        }\n"
+     "            st_v(gp, pack<T, EPT>(gw));\n        }\n"
      f"        FLAME_HT({W0}, 1);\n        return;\n    }}\n    hier_tail<DT, SYNC>("),
 ]
 
