@@ -72,6 +72,19 @@ def test_every_kernel_keeps_fp32_denormals(tmp_path):
     assert not flushed, f"kernels built with fp32 denormal flushing (FLOAT_DENORM_MODE_32 != 3): {flushed}"
 
 
+@pytest.mark.skipif(not os.path.exists(LIB) or not os.path.exists(f"{LLVM}/clang-offload-bundler"),
+                    reason="needs the built library and the ROCm LLVM tools")
+def test_every_kernel_keeps_fp16_fp64_denormals(tmp_path):
+    """FLOAT_DENORM_MODE_16_64, bits 19:18 of the same word (3 = no flushing): the fp16 conversions
+    (v_cvt_f16_f32, the packed fp16 ops of the eager chain) and every fp64 kernel run under it, and
+    the 16-bit sweeps' subnormal results assume it."""
+    kds = kernel_descriptors(gfx950_code_object(tmp_path))
+    assert len(kds) > 20, sorted(kds)
+    assert any("scale_add_kernel" in k for k in kds) and any("feddyn" in k for k in kds)
+    flushed = {k: (r >> 18) & 3 for k, r in kds.items() if (r >> 18) & 3 != 3}
+    assert not flushed, f"kernels built with fp16 / fp64 denormal flushing (FLOAT_DENORM_MODE_16_64 != 3): {flushed}"
+
+
 def test_fast_math_is_refused_at_compile_time():
     src = open(os.path.join(ROOT, "flame_amd", "csrc", "fedagg.hip")).read()
     assert "#error" in src and "__FAST_MATH__" in src and "__FINITE_MATH_ONLY__" in src
