@@ -776,6 +776,169 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mixed_kernel(const flame_se
         if (e0 + j < sg.numel) st1(op + j, acc[j]);
 }
 
+// ---------------------------------------------------------------- MXFP8 updates into an fp32 aggregate
+// flame_agg_reduce_mx: OCP e4m3fn / e5m2 client bytes (CD) with one E8M0 scale byte per 32 elements
+// (OCP Microscaling v1.0), summed into an fp32 base.  An element's value is f32(q) * f32(scale), ONE
+// fp32 multiply with denormals kept -- mx.dequantize's statement -- and from there the fp32
+// reduction's own ops (Tr<FLAME_F32>), so the result is flame_agg_reduce[_scaled]'s over the
+// dequantized update bit for bit.  The chunk is the clients': 4,096 elements (one 4,096-byte tile),
+// a lane owns 16 of them = one 16-byte client vector, half a scale block, 16 fp32 accumulators and
+// four 16-byte vectors of in / out.  A lane reads its block's scale byte itself, one byte load per
+// client beside the vector load (two neighbouring lanes read the same byte; a wave's 32 bytes are
+// one request).  One chunk per workgroup; 168 VGPRs (186 with SCALED) make that three workgroups per
+// CU, not the 16-bit kernel's full residency.  SCALED as in agg_reduce_scaled_kernel.
+#ifndef FLAME_T_CLIENT_UNROLL_MX
+#define FLAME_T_CLIENT_UNROLL_MX 8
+#endif
+constexpr int kClientUnrollMx = FLAME_T_CLIENT_UNROLL_MX;   // clients whose loads are in flight per lane
+// element decode: v_cvt_pk_f32_fp8 / _bf8 (1; OCP formats on gfx950 -- tests/test_gpu_mx.py runs all
+// 256 x 256 (element, scale) pairs of both formats through it) or integer ALU (0; same bits, for A/B builds)
+#ifndef FLAME_T_MX_HWCVT
+#define FLAME_T_MX_HWCVT 1
+#endif
+constexpr bool kMxHwCvt = FLAME_T_MX_HWCVT != 0;
+constexpr int kMxBlock = 32;         // elements per scale byte
+constexpr int kMxEPT = 16;           // elements per lane: one 16-byte client vector
+
+template <int CD> struct Mx;
+template <> struct Mx<FLAME_FP8_E4M3> {
+    // the four bytes of w, lowest first
+    __device__ static void dec4(uint32_t w, float (&x)[4]) {
+        if constexpr (kMxHwCvt) {
+            const f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), false);
+            const f2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), true);
+            x[0] = lo.x; x[1] = lo.y; x[2] = hi.x; x[3] = hi.y;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t b = (w >> (8 * j)) & 0xFFu, sign = (b & 0x80u) << 24, ex = (b >> 3) & 0xFu, man = b & 7u;
+                uint32_t bits;
+                if (ex == 15u && man == 7u) bits = 0x7FC00000u;                                 // the one NaN
+                else if (ex == 0u) bits = __float_as_uint(static_cast<float>(man) * 0x1p-9f);   // subnormal: man * 2^-9, exact
+                else bits = ((ex + 120u) << 23) | (man << 20);
+                x[j] = __uint_as_float(bits | sign);
+            }
+        }
+    }
+};
+template <> struct Mx<FLAME_FP8_E5M2> {
+    __device__ static void dec4(uint32_t w, float (&x)[4]) {
+        if constexpr (kMxHwCvt) {
+            const f2 lo = __builtin_amdgcn_cvt_pk_f32_bf8(static_cast<int>(w), false);
+            const f2 hi = __builtin_amdgcn_cvt_pk_f32_bf8(static_cast<int>(w), true);
+            x[0] = lo.x; x[1] = lo.y; x[2] = hi.x; x[3] = hi.y;
+        } else {
+            // e5m2 is fp16's high byte: widen exactly
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] = f16_to_f32(static_cast<uint16_t>(((w >> (8 * j)) & 0xFFu) << 8));
+        }
+    }
+};
+// E8M0: 2^(byte - 127); byte 0 is the fp32 subnormal 2^-127, byte 255 a NaN
+__device__ __forceinline__ float e8m0_to_f32(uint32_t byte) {
+    return __uint_as_float(byte == 255u ? 0x7FC00000u : byte == 0u ? 0x00400000u : byte << 23);
+}
+
+// reduce_clients' sibling: clients [0, n) of one lane's 16 elements into acc.  VEC: the client vector
+// whole and aligned; else element by element with bounds, the scale index per element.
+template <int CD, int CU, bool VEC, bool SCALED>
+__device__ __forceinline__ void reduce_clients_mx(float (&acc)[kMxEPT], const uint64_t* __restrict__ cp,
+                                                  const uint64_t* __restrict__ bsp, int n,
+                                                  const float* __restrict__ r32, const float* __restrict__ s32,
+                                                  int64_t e0, int64_t numel) {
+    using F = Tr<FLAME_F32>;
+    struct Ld { V16 q; uint32_t sb[VEC ? 1 : kMxEPT]; };
+    auto load_client = [&](int c, Ld& l) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(cp[c]) + e0;
+        const uint8_t* sp = reinterpret_cast<const uint8_t*>(bsp[c]);
+        if constexpr (VEC) {
+            l.q = ld_nt(p);
+            l.sb[0] = ld1(sp + e0 / kMxBlock);
+        } else {
+            uint8_t b[kMxEPT];
+#pragma unroll
+            for (int j = 0; j < kMxEPT; ++j) {
+                const bool in = e0 + j < numel;
+                b[j] = in ? ld1(p + j) : uint8_t(0);
+                l.sb[j] = in ? ld1(sp + (e0 + j) / kMxBlock) : 127u;
+            }
+            l.q = pack<uint8_t, kMxEPT>(b);
+        }
+    };
+    auto combine = [&](int c, const Ld& l) {
+        const float r = r32[c];
+        float x[kMxEPT];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            float d[4];
+            Mx<CD>::dec4(l.q.w[w], d);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[4 * w + j] = d[j];
+        }
+#pragma unroll
+        for (int j = 0; j < kMxEPT; ++j) {
+            float v = __fmul_rn(x[j], e8m0_to_f32(l.sb[VEC ? 0 : j]));     // the update's value: one fp32 multiply
+            if constexpr (SCALED) v = F::tmp(v, s32[c], 0.0);
+            acc[j] = F::add(acc[j], F::tmp(v, r, 0.0));
+        }
+    };
+    int i = 0;
+    for (; i + CU <= n; i += CU) {
+        Ld l[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) load_client(i + u, l[u]);
+#pragma unroll
+        for (int u = 0; u < CU; ++u) combine(i + u, l[u]);
+    }
+    for (; i < n; ++i) {
+        Ld l;
+        load_client(i, l);
+        combine(i, l);
+    }
+}
+
+template <int CD, int CU, bool SCALED>
+__global__ __launch_bounds__(kBlock) void agg_reduce_mx_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                               const uint64_t* __restrict__ clients,
+                                                               const uint64_t* __restrict__ block_scales, int n_clients,
+                                                               const float* __restrict__ r32,
+                                                               const float* __restrict__ s32, unsigned flags,
+                                                               int64_t n_chunks) {
+    static_assert(CD == FLAME_FP8_E4M3 || CD == FLAME_FP8_E5M2, "8-bit clients, one client vector per lane");
+    constexpr int EPT = kMxEPT;             // 16 client bytes = 4 fp32 vectors of 4
+    static_assert(kBlock * EPT == FLAME_TILE_BYTES && kMxBlock % EPT == 0, "a chunk is one tile; a lane stays inside one block");
+    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t e0 = (chunk - sg.chunk_begin) * (kBlock * EPT) + static_cast<int64_t>(threadIdx.x) * EPT;
+    if (e0 >= sg.numel) return;
+    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
+    const uint64_t* bsp = block_scales + static_cast<int64_t>(s) * n_clients;
+    const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
+    float* op = reinterpret_cast<float*>(sg.out) + e0;
+    float acc[EPT];
+    if (e0 + EPT <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
+        float b[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) unpack<float, 4>(ld_v(bp + 4 * q), b[q]);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) acc[j] = b[j / 4][j % 4];
+        reduce_clients_mx<CD, CU, true, SCALED>(acc, cp, bsp, n_clients, r32, s32, e0, sg.numel);
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) b[j / 4][j % 4] = acc[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) st_v(op + 4 * q, pack<float, 4>(b[q]));
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) acc[j] = (e0 + j < sg.numel) ? ld1(bp + j) : 0.f;
+    reduce_clients_mx<CD, 1, false, SCALED>(acc, cp, bsp, n_clients, r32, s32, e0, sg.numel);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, acc[j]);
+}
+
 // ---------------------------------------------------------------- trimmed mean / median
 // Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
 // the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
@@ -3773,6 +3936,7 @@ int64_t flame_chunk_elems(int dtype) {
     int64_t n = 0;
     dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64, FLAME_I64, FLAME_I32>(
         dtype, [&](auto dt) { n = chunk_elems<decltype(dt)::value>(); });
+    if (dtype == FLAME_FP8_E4M3 || dtype == FLAME_FP8_E5M2) n = static_cast<int64_t>(kBlock) * kMxEPT;   // flame_agg_reduce_mx only
     return n;
 }
 
@@ -3870,6 +4034,42 @@ int flame_agg_reduce_mixed(int client_dtype, int agg_dtype, unsigned flags, cons
                                n_clients, rates32, scales32, flags, n_chunks);
         else
             hipLaunchKernelGGL((agg_reduce_mixed_kernel<CD, kClientUnroll16, false>), grid, block, 0, st, segs, n_segs, cl,
+                               n_clients, rates32, scales32, flags, n_chunks);
+    });
+    return check_launch(who);
+}
+
+// MXFP8 updates into an fp32 aggregate: flame_agg_reduce_mixed's arguments plus the table of scale
+// byte pointers.  Outside the launch-branch table, one instantiation per element format and SCALED;
+// every refusal comes before the first HIP call.
+int flame_agg_reduce_mx(int client_dtype, int agg_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs,
+                        int64_t n_chunks, const void* const* clients, const void* const* block_scales, int32_t n_clients,
+                        const float* rates32, const float* scales32, void* stream) {
+    const char* const who = "flame_agg_reduce_mx";
+    if ((client_dtype != FLAME_FP8_E4M3 && client_dtype != FLAME_FP8_E5M2) || agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: client dtype %d into aggregate dtype %d is not supported (fp8 e4m3 or e5m2 into f32 only)",
+                       who, client_dtype, agg_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (int rc = need_clients(who, clients)) return rc;
+    if (!block_scales) return set_err(FLAME_EINVAL, "%s: block scale pointer table is NULL", who);
+    if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if (flags & FLAME_AGG_INIT_FIRST)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (an MX update has no aggregate dtype of its own)", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
+    if (int rc = check_flags(who, flags, FLAME_AGG_XCD_MAP)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t* cl = reinterpret_cast<const uint64_t*>(clients);
+    const uint64_t* bs = reinterpret_cast<const uint64_t*>(block_scales);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    dispatch<FLAME_FP8_E4M3, FLAME_FP8_E5M2>(client_dtype, [&](auto dt) {
+        constexpr int CD = decltype(dt)::value;
+        if (scales32)
+            hipLaunchKernelGGL((agg_reduce_mx_kernel<CD, kClientUnrollMx, true>), grid, block, 0, st, segs, n_segs, cl, bs,
+                               n_clients, rates32, scales32, flags, n_chunks);
+        else
+            hipLaunchKernelGGL((agg_reduce_mx_kernel<CD, kClientUnrollMx, false>), grid, block, 0, st, segs, n_segs, cl, bs,
                                n_clients, rates32, scales32, flags, n_chunks);
     });
     return check_launch(who);

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import shm_lease
+from . import mx, shm_lease
 
 DTYPE_CODE = {
     torch.float32: N.FLAME_F32, torch.bfloat16: N.FLAME_BF16, torch.float16: N.FLAME_F16,
@@ -43,17 +43,30 @@ FLOAT_CODES = (N.FLAME_F32, N.FLAME_BF16, N.FLAME_F16, N.FLAME_F64)
 # tmp is formed in fp32 by the kernel and cast, their adds are torch's (see tmp_of)
 NARROW = (torch.bool, torch.uint8, torch.int8, torch.int16)
 VEC_BYTES = 16
-ITEMSIZE = {N.FLAME_F32: 4, N.FLAME_BF16: 2, N.FLAME_F16: 2, N.FLAME_F64: 8, N.FLAME_I64: 8, N.FLAME_I32: 4}
+ITEMSIZE = {N.FLAME_F32: 4, N.FLAME_BF16: 2, N.FLAME_F16: 2, N.FLAME_F64: 8, N.FLAME_I64: 8, N.FLAME_I32: 4,
+            N.FLAME_FP8_E4M3: 1, N.FLAME_FP8_E5M2: 1}
 # update dtypes that one launch sums into an fp32 aggregate (flame_agg_reduce_mixed): a trainer's
 # 16-bit deltas into the server's fp32 model.  Every other pair of differing dtypes stays on
 # _accumulate_mixed / _accumulate_promoted.
 UPLINK16 = (torch.bfloat16, torch.float16)
+# element dtypes of an MX update (flame_amd.mx.MXWeights: float8 elements, one E8M0 scale byte per
+# MX_BLOCK elements), which one flame_agg_reduce_mx launch per format sums into an fp32 aggregate.
+# They are NOT in DTYPE_CODE: no other kernel, slab or cache takes them (:func:`mx_route`).
+MX_CODE = {torch.float8_e4m3fn: N.FLAME_FP8_E4M3, torch.float8_e5m2: N.FLAME_FP8_E5M2}
+MX_BLOCK = 32
+MX_SUPPORTED = ("MX updates are supported as flame_amd.mx.MXWeights whose every entry holds the key in ONE float8 "
+                "format (float8_e4m3fn or float8_e5m2) with a 1-D uint8 scale tensor of ceil(numel / 32) bytes, summed "
+                "into an fp32 aggregate by engine.accumulate / reduce_ (FedAvg, FedProx, FedGFT and the FedOPT family)")
 
 
 def dtype_code(dt: torch.dtype) -> int:
     try:
         return DTYPE_CODE[dt]
     except KeyError:
+        if dt in MX_CODE:
+            raise TypeError(f"flame_amd: {dt} is the element dtype of an MX update, which only the reduction into an "
+                            f"fp32 aggregate reads: the update guard, trim, krum, rfa, slabs and every other kernel "
+                            f"do not take it.  {MX_SUPPORTED}") from None
         raise TypeError(f"flame_amd: tensor dtype {dt} is not supported by the aggregation kernels "
                         f"(supported: {sorted(str(d) for d in DTYPE_CODE)})") from None
 
@@ -94,6 +107,7 @@ class Seg:
     clients: List[int] = field(default_factory=list)
     tile_stride: int = 0   # bytes between consecutive chunks of one client (0 = contiguous)
     flags: int = 0         # FLAME_SEG_* bits set by the caller (FLAME_SEG_UNALIGNED is computed)
+    bscales: Optional[List[int]] = None   # flame_agg_reduce_mx: one scale-byte pointer per client (any alignment)
 
     def pointers(self):
         return [self.out, self.inp, self.cur, self.cur_out, self.m, self.v, self.tile_stride] + list(self.clients)
@@ -111,6 +125,7 @@ class Plan:
     off_r64: int
     off_s32: int = -1     # the per-client clip scales (flame_agg_reduce_scaled), -1 without them
     off_s64: int = -1
+    off_bscales: int = -1  # the block-scale pointer table [n_segs][n_clients] (flame_agg_reduce_mx), -1 without it
 
 
 class _Block:
@@ -185,6 +200,11 @@ def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] =
         head[i] = (*fixed, s.numel, b.chunk_begin(s.numel), s.flags | b.unaligned(fixed, table[i]), s.tile_stride)
     b.add("segs", head)
     off_clients = b.add("clients", table)
+    off_bscales = -1
+    if any(s.bscales is not None for s in segs):
+        if seg_rates or compact or any(s.bscales is None or len(s.bscales) != n for s in segs):
+            raise ValueError("block scales: one pointer per client for every segment, device-table plans only")
+        off_bscales = b.add("bscales", np.asarray([s.bscales for s in segs], dtype=np.uint64))
     r64 = np.asarray(rates, dtype=np.float64).reshape(-1)
     f64 = code == N.FLAME_F64       # compact: only the rate array the dtype reads (f64 tensors the fp64 rates)
     off_r32 = b.add("r32", _f32(r64)) if not (compact and f64) else -1
@@ -197,7 +217,7 @@ def plan(code: int, segs: Sequence[Seg], rates: Sequence, chunk: Optional[int] =
         off_s32 = b.add("s32", _f32(s64))
         off_s64 = b.add("s64", s64)
     meta, n_chunks = b.finish()
-    return Plan(code, meta, n_segs, n_chunks, n, off_clients, off_r32, off_r64, off_s32, off_s64)
+    return Plan(code, meta, n_segs, n_chunks, n, off_clients, off_r32, off_r64, off_s32, off_s64, off_bscales)
 
 
 # ------------------------------------------------------------------ device staging
@@ -435,19 +455,79 @@ def uplink16_dtype(out_dtype, client_dtypes):
     return first
 
 
+def is_mx(w) -> bool:
+    """``w`` is an MX update, an :class:`flame_amd.mx.MXWeights`.  One isinstance, so the callers' hot
+    paths pay nothing for asking; a float8 tensor in any other dict is refused where its dtype is
+    looked at (:func:`dtype_code`, :func:`_check_cast`, :func:`reduce_`)."""
+    return isinstance(w, mx.MXWeights)
+
+
+def refuse_mx(ws, who: str) -> None:
+    """TypeError when one of the updates ``ws`` is an MX update: ``who`` does not take them."""
+    for w in ws:
+        if w is not None and is_mx(w):
+            raise TypeError(f"flame_amd: {who} does not take MX updates (a follow-up, not a silent slow path).  {MX_SUPPORTED}")
+
+
+def mx_route(agg_dtype, ws, k):
+    """The float8 dtype of key ``k`` when the updates ``ws`` (all carrying ``k``) take ONE
+    flame_agg_reduce_mx launch: every one an MXWeights holding ``k`` in the same float8 format with a
+    1-D uint8 scale tensor of ceil(numel / 32) bytes, under an fp32 aggregate.  None when no update
+    holds ``k`` as float8 (its present route); every case in between is a TypeError."""
+    dts = [weight_dtype(w, k) for w in ws]
+    if not any(dt in MX_CODE for dt in dts):
+        return None
+    first = next(dt for dt in dts if dt in MX_CODE)
+    if any(dt not in MX_CODE for dt in dts):
+        other = next(dt for dt in dts if dt not in MX_CODE)
+        raise TypeError(f"flame_amd: key {k!r} is {first} in some updates and {other} in others: per-key mixtures of MX "
+                        f"and plain updates are not supported.  {MX_SUPPORTED}")
+    if any(dt != first for dt in dts):
+        raise TypeError(f"flame_amd: key {k!r} comes in two MX element formats ({first} and "
+                        f"{next(dt for dt in dts if dt != first)}).  {MX_SUPPORTED}")
+    if agg_dtype != torch.float32:
+        raise TypeError(f"flame_amd: key {k!r}: MX updates into a {agg_dtype} aggregate are not supported.  {MX_SUPPORTED}")
+    for w in ws:
+        if not isinstance(w, mx.MXWeights):
+            raise TypeError(f"flame_amd: key {k!r} is a {first} tensor in a plain {type(w).__name__}: a float8 tensor "
+                            f"means nothing without its block scales.  {MX_SUPPORTED}")
+        s = w.scales.get(k)
+        want = -(-w[k].numel() // MX_BLOCK)
+        if not isinstance(s, torch.Tensor):
+            raise TypeError(f"flame_amd: key {k!r} is a {first} tensor without scales.  {MX_SUPPORTED}")
+        if s.dtype != torch.uint8 or s.dim() != 1 or s.numel() != want:
+            raise TypeError(f"flame_amd: key {k!r}: the MX scales are {s.dtype} {tuple(s.shape)}, not uint8 ({want},).  "
+                            f"{MX_SUPPORTED}")
+    return first
+
+
+def _row_pointer(c: torch.Tensor, device, keep) -> int:
+    """The device address the kernel reads a contiguous client tensor at: a device copy, or the
+    translated address of a pinned host tensor (``keep``: what must outlive the launch)."""
+    c = _as_device(c, device)
+    keep.append(c)
+    return c.data_ptr() if c.is_cuda else host_device_pointer(c.data_ptr())
+
+
 def _client_row(cs, o: torch.Tensor, device, keep, cdt=None):
     """Device pointers of one segment's clients + the segment's client_tile_stride.
 
     If every client is a tiled slab view with the same stride, the kernel reads
     them tiled; otherwise every client is read contiguous (tiled views that are
     mixed with other layouts in one call are copied out -- rare).  ``cdt``: the clients' dtype
-    where it is not the aggregate's (:func:`uplink16_dtype`); the tile-stride test is in it."""
+    where it is not the aggregate's (:func:`uplink16_dtype`); the tile-stride test is in it.  MX
+    element tensors (``cdt`` a float8 dtype) are never tiled: every row is contiguous."""
     n = o.numel()
     dt = cdt or o.dtype
     for c in cs:
         if c.dtype != dt:
             raise NotImplementedError(
                 f"flame_amd: client tensor dtype {c.dtype} differs from aggregate dtype {dt}")
+    if dt in MX_CODE:
+        for c in cs:
+            if c.numel() != n:
+                raise RuntimeError(f"flame_amd: client tensor has {c.numel()} elements, aggregate {n}")
+        return [_row_pointer(c, device, keep) for c in cs], 0
     if cs and cs[0].device == device:
         ts0 = tiled_stride(cs[0], n)
         if ts0:
@@ -464,9 +544,7 @@ def _client_row(cs, o: torch.Tensor, device, keep, cdt=None):
             c = c.reshape(-1)[:n]             # contiguous copy of a tiled view
         elif c.numel() != n:
             raise RuntimeError(f"flame_amd: client tensor has {c.numel()} elements, aggregate {n}")
-        c = _as_device(c, device)
-        keep.append(c)
-        row.append(c.data_ptr() if c.is_cuda else host_device_pointer(c.data_ptr()))
+        row.append(_row_pointer(c, device, keep))
     return row, 0
 
 
@@ -500,7 +578,8 @@ def _require_hip(device, who) -> None:
 def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients: List[List[torch.Tensor]],
             rates: Optional[Sequence[float]], *, init_first: bool = False,
             seg_rates: Optional[Sequence[Sequence[float]]] = None,
-            scales: Optional[Sequence[float]] = None) -> None:
+            scales: Optional[Sequence[float]] = None,
+            block_scales: Optional[Sequence[Optional[Sequence[torch.Tensor]]]] = None) -> None:
     """outs[s] = ins[s] (+)= Σ_i round(clients[s][i] * rates[i]) in order (kernel: flame_agg_reduce).
 
     ``outs`` are written in place (they must be contiguous device tensors);
@@ -510,27 +589,45 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
     ``scales`` (one per client; float dtypes, not with ``seg_rates``): each client's value is
     first multiplied by its clip scale, ``round(round(v * scale) * rate)`` (kernel:
     flame_agg_reduce_scaled).
+    ``block_scales[s]`` (or None per segment): segment ``s``'s clients are MX element tensors
+    (float8, :data:`MX_CODE`) and these are their uint8 E8M0 scale tensors, one per client; such
+    segments under an fp32 output take one flame_agg_reduce_mx launch per element format, the clip
+    ``scales`` inside it.
     """
     if not outs:
         return
     device = outs[0].device
     _require_hip(device, "reduce_")
     keep = []
-    # a segment of 16-bit clients under an fp32 output is grouped by both dtypes (ccode: the clients')
+    # a segment of 16-bit or MX clients under an fp32 output is grouped by both dtypes (ccode: the clients')
     cdts = [uplink16_dtype(o.dtype, (c.dtype for c in cs)) for o, cs in zip(outs, clients)]
+    for s, (o, cs) in enumerate(zip(outs, clients)):
+        mxs = block_scales[s] if block_scales is not None else None
+        if mxs is None and any(c.dtype in MX_CODE for c in cs):
+            raise TypeError(f"flame_amd.reduce_: float8 client tensors without block scales.  {MX_SUPPORTED}")
+        if mxs is not None:
+            cdts[s] = cs[0].dtype if cs else None
+            if (cdts[s] not in MX_CODE or o.dtype != torch.float32 or len(mxs) != len(cs)
+                    or any(c.dtype != cdts[s] for c in cs)
+                    or any(m.dtype != torch.uint8 or m.dim() != 1 or m.numel() != -(-o.numel() // MX_BLOCK) for m in mxs)):
+                raise TypeError(f"flame_amd.reduce_: segment {s} is not an MX segment.  {MX_SUPPORTED}")
+    ccode_of = lambda dt: MX_CODE[dt] if dt in MX_CODE else dtype_code(dt)     # noqa: E731
     for (code, ccode), idx in by_dtype(range(len(outs)), lambda s: outs[s].dtype,
-                                       also=lambda s: cdts[s] and dtype_code(cdts[s])).items():
+                                       also=lambda s: cdts[s] and ccode_of(cdts[s])).items():
         segs = []
         for s in idx:
             o = outs[s]
             assert o.is_contiguous() and o.device == device
             row, tstride = _client_row(clients[s], o, device, keep, cdts[s])
+            brow = None
+            if cdts[s] in MX_CODE:
+                brow, _ = _client_row(block_scales[s], _KeyLike(-(-o.numel() // MX_BLOCK), torch.uint8), device, keep, torch.uint8)
             inp = 0
             if not init_first:
                 i_t = ins[s]
                 assert i_t.is_contiguous() and i_t.device == device and i_t.numel() == o.numel()
                 inp = i_t.data_ptr()
-            segs.append(Seg(o.numel(), out=o.data_ptr(), inp=inp, clients=row, tile_stride=tstride))
+            segs.append(Seg(o.numel(), out=o.data_ptr(), inp=inp, clients=row, tile_stride=tstride, bscales=brow))
         _launch_reduce(code, segs, rates if seg_rates is None else [seg_rates[s] for s in idx], device, keep,
                        init_first=init_first, seg_rates=seg_rates is not None, scales=scales, ccode=ccode)
     _keepalive(keep, device)
@@ -545,9 +642,19 @@ def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rat
     L = N.lib()
     if ccode is not None and ccode != code:
         if init_first or seg_rates:
-            raise NotImplementedError("flame_amd: 16-bit updates into an fp32 aggregate take neither init_first "
+            raise NotImplementedError("flame_amd: 16-bit and MX updates into an fp32 aggregate take neither init_first "
                                       "(a None-start aggregate has the update's dtype) nor seg_rates")
         n_cl = _n_clients(rates, False)
+        if ccode in MX_CODE.values():
+            # per element: n 1-byte reads, one fp32 read, one fp32 write; per block and client one scale byte
+            nbytes = sum(s.numel * (n_cl + 2 * ITEMSIZE[code]) + n_cl * -(-s.numel // MX_BLOCK) for s in segs)
+            p = plan(ccode, segs, rates, scales=scales)
+            flags = N.FLAME_AGG_XCD_MAP if p.n_chunks >= XCD_MAP_MIN_CHUNKS else 0
+            _launch("flame_agg_reduce_mx", nbytes, device, keep, p.meta,
+                    lambda b: L.flame_agg_reduce_mx(ccode, code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients,
+                                                    b + p.off_bscales, p.n_clients, b + p.off_r32,
+                                                    b + p.off_s32 if scales is not None else None, _stream_ptr(device)))
+            return
         nbytes = sum(s.numel for s in segs) * (n_cl * ITEMSIZE[ccode] + 2 * ITEMSIZE[code])
         p = plan(ccode, segs, rates, scales=scales)
         flags = N.FLAME_AGG_XCD_MAP if p.n_chunks >= XCD_MAP_MIN_CHUNKS and all(s.tile_stride == 0 for s in segs) else 0
@@ -1194,6 +1301,7 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     if _accumulate_slab(agg, entries, device, key_groups, after_group, scales):
         return
     if key_groups is not None:
+        refuse_mx([w for w, _ in entries], "the sharded wrapper (key_groups)")
         for w, _ in entries:
             for k in w.keys():
                 if k not in agg:
@@ -1216,13 +1324,24 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     for k in keys:
         if k in per_key:
             groups.setdefault(tuple(per_key[k]), []).append(k)
+    any_mx = any(is_mx(w) for w, _ in entries)      # (a float8 tensor in a plain dict: _check_cast refuses it)
+    routed = []
     for cis, ks in groups.items():
+        # MX keys: float8 elements + block scales of MXWeights under an fp32 aggregate (reduce_ groups
+        # those into one flame_agg_reduce_mx per element format)
+        mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k) is not None}
         # same: one reduction launch per dtype pair -- the aggregate's own dtype, or bf16 / f16
         # updates under an fp32 aggregate (reduce_ groups those into flame_agg_reduce_mixed)
-        same = [k for k in ks if agg[k].dtype in DTYPE_CODE
+        same = [k for k in ks if k in mxk or (agg[k].dtype in DTYPE_CODE
                 and (all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)
-                     or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None)]
+                     or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None))]
         mixed = [k for k in ks if k not in same]
+        for k in mixed:     # (a float8 tensor in a plain dict ends here)
+            for ci in cis:
+                _check_cast(agg[k].dtype, weight_dtype(entries[ci][0], k))
+        routed.append((cis, mxk, same, mixed))
+    # every refusal of the round has been raised: the aggregate is untouched until here
+    for cis, mxk, same, mixed in routed:
         # with clip scales the float keys take the scaled kernel; integer keys are never scaled
         parts = [(same, None)] if scales is None else [
             ([k for k in same if agg[k].is_floating_point()], [scales[ci] for ci in cis]),
@@ -1233,7 +1352,8 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
             targets = [_Target(agg[k], device) for k in part]
             outs = [t.dev for t in targets]
             clients = [[entries[ci][0][k] for ci in cis] for k in part]
-            reduce_(outs, outs, clients, [entries[ci][1] for ci in cis], scales=sc)
+            bsc = [[entries[ci][0].scales[k] for ci in cis] if k in mxk else None for k in part] if mxk else None
+            reduce_(outs, outs, clients, [entries[ci][1] for ci in cis], scales=sc, **({} if bsc is None else {"block_scales": bsc}))
             for t in targets:
                 t.writeback()
         sub = [entries[ci] for ci in cis]
@@ -1386,6 +1506,7 @@ def update_stats(weights_list, device=None):
     sumsq, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int64)
     if n == 0:
         return sumsq, nonfinite
+    refuse_mx(ws, "the update guard's / rfa's measurement (engine.update_stats)")
     device = _hip_device(device, "update_stats", *ws)
     keep = []
     items = _float_items(ws, device, keep)
@@ -1419,6 +1540,7 @@ def update_dist(weights_list, center, device=None):
     dist2, nonfinite = np.zeros(n, np.float64), np.zeros(n, np.int64)
     if n == 0:
         return dist2, nonfinite
+    refuse_mx(ws, "rfa's measurement (engine.update_dist)")
     device = _hip_device(device, "update_dist", *ws)
     keep = []
 
@@ -1467,6 +1589,7 @@ def update_gram(weights_list, device=None):
         return np.zeros((0, 0), np.float64), np.zeros(0, np.int64)
     if n > gram_max_clients():
         raise NotImplementedError(f"flame_amd.update_gram: {n} updates exceed the kernel's capacity of {gram_max_clients()}")
+    refuse_mx(ws, "krum's measurement (engine.update_gram)")
     device = _hip_device(device, "update_gram", *ws)
     keep = []
     items = _float_items(ws, device, keep, uniform="update_gram")
@@ -1528,6 +1651,7 @@ def _trimmed(who, symbol, capacity, agg, weights_list, k, init_first, device) ->
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
         raise TypeError(f"{who}: k must be an int, not {type(k).__name__}")
     k = int(k)
+    refuse_mx(representatives(ws), f"trim (engine.{who})")
     if k < 0 or n <= 2 * k:
         raise ValueError(f"{who}: need 0 <= k and n > 2k, got k = {k} with {n} update(s)")
     capacity(n, k)
@@ -1789,6 +1913,9 @@ def tmp_of(v: torch.Tensor, rate: float, device, shape=None) -> torch.Tensor:
 
 
 def _check_cast(acc_dt, v_dt) -> None:
+    if v_dt in MX_CODE or acc_dt in MX_CODE:
+        raise TypeError(f"flame_amd: a {v_dt if v_dt in MX_CODE else acc_dt} tensor outside an MX update: a float8 tensor "
+                        f"means nothing without its block scales.  {MX_SUPPORTED}")
     p = torch.promote_types(acc_dt, v_dt)
     if not torch.can_cast(p, acc_dt):
         raise RuntimeError(f"result type {str(p).replace('torch.', '').capitalize()} can't be cast to the "

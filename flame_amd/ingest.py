@@ -800,6 +800,9 @@ class DeviceUpdateCache:
 
     def __setitem__(self, key, tres):
         w = getattr(tres, "weights", None)
+        if isinstance(w, dict):
+            from . import engine
+            engine.refuse_mx([w], "DeviceUpdateCache")    # no MX slots yet: a plain cache holds MX updates
         ev = None
         shm = False
         if isinstance(w, dict) and w:

@@ -102,7 +102,9 @@ class DeferredWeights(collections.abc.Mapping):
             if k not in self._base:
                 raise KeyError(k)
             acc, dt = self._base[k].dtype, engine.weight_dtype(w, k)
-            if dt != acc:
+            if dt in engine.MX_CODE:
+                engine.mx_route(acc, [w], k)        # an MX arrival: what the flush would refuse of it, now
+            elif dt != acc:
                 engine._check_cast(acc, dt)
 
     def _queue(self, entries):

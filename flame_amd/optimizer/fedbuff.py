@@ -61,6 +61,10 @@ class DeferredAggregate(collections.abc.Mapping):
         self._arrival_bytes = sum(math.prod(s) * dt.itemsize
                                   for s, dt in self._meta.values())
 
+    def queued_updates(self):
+        """The weights of the arrivals still queued, in arrival order."""
+        return [w for w, _ in self._pending]
+
     def _queue(self, entries):
         held = 0
         last_ok = None                # the slab whose slots the previous entry was checked against
@@ -206,6 +210,7 @@ class FedBuff(AbstractOptimizer):
         try:
             for k in list(cache.iterkeys()):
                 tres = cache.pop(k)
+                engine.refuse_mx([tres.weights], "FedBuff")
                 # rate determined based on the staleness of local model (fedbuff.py:94-96)
                 rate = 1 / math.sqrt(1 + version - tres.version)
                 entries.append((tres.weights, rate))
@@ -232,6 +237,7 @@ class FedBuff(AbstractOptimizer):
         if not arrivals:
             return agg_goal_weights
         n = len(arrivals)
+        engine.refuse_mx([t.weights for t in arrivals], "FedBuff")
         if any(t.count <= 0 for t in arrivals):
             raise ValueError("FedBuff.do_arrivals: an arrival with count <= 0 (the roles skip those)")
         d = 1 + version - np.fromiter((t.version for t in arrivals), dtype=np.int64, count=n)
@@ -520,6 +526,8 @@ def hierarchy_round(middles, top_agg=None, *, version: int, top_weights=None, to
     middles = list(middles)
     if not middles:
         raise ValueError("hierarchy_round: no middles")
+    for _, a, _, _ in middles:      # a middle's aggregate, or the arrivals still queued in it
+        engine.refuse_mx(a.queued_updates() if isinstance(a, DeferredAggregate) else [a], "the FedBuff hierarchy round")
     if top_weights is not None and not top_goal:
         raise ValueError("hierarchy_round: top_goal must be nonzero")
     # the top's rates, computed as FedBuff.do does (stale versions raise here, fedbuff.py:96)

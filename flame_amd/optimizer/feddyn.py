@@ -197,6 +197,7 @@ class FedDyn(FedAvg):
         for k in list(cache.iterkeys()):
             tres = cache.pop(k)
             arrivals.append((k, tres.weights))
+        engine.refuse_mx([w for _, w in arrivals], "FedDyn")
         device = engine.pick_device(base_weights, *[w for _, w in arrivals])
         had = {e for e, h in self.local_param_dict.items() if h is not None}
         for end, _ in arrivals:     # add_to_hist appends untracked ends in arrival order (:135-139)

@@ -216,6 +216,15 @@ class FedOPT(FedAvg):
         current = self.current_weights
         device = engine.pick_device(base_weights, current, *[w for w, _ in entries])
         keys = list(base_weights.keys())
+        mx_keys = set()     # the keys every update holds as MX elements of one format
+        if any(engine.is_mx(w) for w, _ in entries):
+            # an MX round's refusals (engine.mx_route) come before anything is written
+            if key_groups is not None:
+                engine.refuse_mx([w for w, _ in entries], "the sharded wrapper (key_groups)")
+            for k in keys:
+                ws = [w for w, _ in entries if k in w]
+                if ws and engine.mx_route(base_weights[k].dtype, ws, k) is not None and len(ws) == len(entries):
+                    mx_keys.add(k)
         fused, generic = [], []
         float_dts = (torch.float32, torch.bfloat16, torch.float16, torch.float64)
         for k in keys:
@@ -232,8 +241,10 @@ class FedOPT(FedAvg):
                   and all(k in w for w, _ in entries)
                   # the updates in the key's own dtype, or all bf16 / all f16 under an fp32 key
                   # (flame_agg_reduce_mixed, then the adaptive step on fp32 tensors)
+                  # ... or all MX (float8 elements + block scales: flame_agg_reduce_mx, then the same step)
                   and (all(w[k].dtype == dt for w, _ in entries)
-                       or engine.uplink16_dtype(dt, (w[k].dtype for w, _ in entries)) is not None)
+                       or engine.uplink16_dtype(dt, (w[k].dtype for w, _ in entries)) is not None
+                       or k in mx_keys)
                   and (self.m_t is None or (k in self.m_t and self.m_t[k].dtype == dt
                                             and self.v_t[k].dtype == dt)))
             (fused if ok else generic).append(k)
@@ -310,12 +321,16 @@ class FedOPT(FedAvg):
         avgs = [t.dev for t in targets]
         clients = [[w[k] for w, _ in entries] for k in ks]
         rates = [r for _, r in entries]
-        split = self.split_launch or any(
+        # MX keys (float8 elements): their scale tensors go with the reduction, which is then a launch of its own
+        bsc = [[w.scales[k] for w, _ in entries] if row and row[0].dtype in engine.MX_CODE else None
+               for k, row in zip(ks, clients)]
+        mx_kw = {"block_scales": bsc} if any(b is not None for b in bsc) else {}
+        split = self.split_launch or bool(mx_kw) or any(
             engine.uplink16_dtype(base_weights[k].dtype, (c.dtype for c in row)) is not None
             for k, row in zip(ks, clients))
         if noise is not None:
             if scales is not None or split or any(getattr(w, "slab", None) is not None for w, _ in entries):
-                engine.reduce_(avgs, avgs, clients, rates, scales=scales)
+                engine.reduce_(avgs, avgs, clients, rates, scales=scales, **mx_kw)
                 engine.reduce_(avgs, avgs, [[noise[k]] for k in ks], [1.0])
                 engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                             [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
@@ -324,11 +339,11 @@ class FedOPT(FedAvg):
                                             [row + [noise[k]] for row, k in zip(clients, ks)], rates + [1.0], hyper,
                                             state_zero, cur_is_avg=alias)
         elif scales is not None:
-            engine.reduce_(avgs, avgs, clients, rates, scales=scales)
+            engine.reduce_(avgs, avgs, clients, rates, scales=scales, **mx_kw)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
         elif split:
-            engine.reduce_(avgs, avgs, clients, rates)
+            engine.reduce_(avgs, avgs, clients, rates, **mx_kw)
             engine.fedopt_reduce_adapt_(self.variant, [None] * len(ks), avgs, curs, outs, ms, vs,
                                         [[] for _ in ks], [], hyper, state_zero, cur_is_avg=alias)
         else:

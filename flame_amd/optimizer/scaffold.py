@@ -76,12 +76,15 @@ class Scaffold(FedAvg):
         self.c_agg_weights = self.c_glob
         rate = 1 / len(self.weight_dict)
         controls = [control_cache.pop(k).weights for k in list(control_cache.iterkeys())]
+        n = len(cache)
+        updates = [cache.pop(k).weights for k in list(cache.iterkeys())]
+        engine.refuse_mx(controls + updates, "SCAFFOLD")       # before anything is written
         self._c_aggregate(controls, rate)
         self.c_glob = self.c_agg_weights
 
         self.agg_weights = base_weights
-        rate = 1 / len(cache)
-        entries = [(cache.pop(k).weights, rate) for k in list(cache.iterkeys())]
+        rate = 1 / n
+        entries = [(w, rate) for w in updates]
         engine.accumulate(self.agg_weights, entries)
         return self.agg_weights
 

@@ -35,6 +35,7 @@ def _drain(cache, total):
     entries = []
     for k in list(cache.iterkeys()):
         tres = cache.pop(k)
+        engine.refuse_mx([tres.weights], "the synchronous hierarchy round")
         entries.append((tres.weights, tres.count / total))
     return entries
 

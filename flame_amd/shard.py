@@ -151,6 +151,7 @@ class ShardPlan:
     def slice_update(self, weights):
         """This rank's slices of a full client update as plain views / host slices (what
         ``DeviceUpdateCache(shard=plan)`` copies to the device)."""
+        engine.refuse_mx([weights], "the sharded wrapper")
         for k, t in weights.items():
             if k not in self.numel:
                 raise KeyError(k)
@@ -183,6 +184,7 @@ class ShardPlan:
         """
         slab = getattr(weights, "slab", None)
         rng = getattr(weights, "ranges", None)
+        engine.refuse_mx([weights], "the sharded wrapper")      # a slice of an MX key would cut its blocks
         if slab is not None and (rng is self.full_ranges or rng is self.self_ranges):
             return weights                      # already this plan's slices (a SlabRef it made)
         if slab is not None and rng is None:

@@ -206,6 +206,7 @@ class UpdateSlab:
         registered or pageable): ``flame_slab_write_2d``, one pitched copy-engine transfer per
         key, no staging tensor.
         """
+        engine.refuse_mx([weights], "UpdateSlab.put / write")      # before anything else: no MX slots yet
         cur = engine.current_stream(self.device)
         st = stream or cur
         for k in self.keys:     # validate before the slot's reader event is consumed (a refused

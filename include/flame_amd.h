@@ -37,6 +37,9 @@
  *                               by optimizer/fedavg.py:93-104, in one pass
  *   flame_agg_reduce_mixed      optimizer/fedavg.py:93-104 with bf16 / f16 updates into an fp32 model:
  *                               `tmp = v * rate` in v's dtype, `agg += tmp` in the promoted fp32
+ *   flame_agg_reduce_mx         (no reference counterpart: MXFP8 updates -- OCP e4m3fn / e5m2 elements, one
+ *                               E8M0 scale per 32 -- into an fp32 model; the same statements over the
+ *                               dequantized update)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -84,6 +87,11 @@ extern "C" {
 #define FLAME_F64 3
 #define FLAME_I64 4
 #define FLAME_I32 5
+/* 6 .. 9 are the element types only flame_elementwise takes (FLAME_U8 .. FLAME_BOOL, below).
+ * MXFP8 client elements (OCP Microscaling v1.0), taken by flame_agg_reduce_mx alone: every other
+ * entry point refuses them as it refuses an unknown code */
+#define FLAME_FP8_E4M3 10 /* OCP e4m3fn: torch.float8_e4m3fn */
+#define FLAME_FP8_E5M2 11 /* OCP e5m2:   torch.float8_e5m2 */
 
 /* flame_agg_reduce flags */
 #define FLAME_AGG_INIT_FIRST 1u  /* no base: acc = tmp(client 0) (fedbuff.py:139-140,154-155) */
@@ -311,6 +319,43 @@ int flame_agg_reduce_scaled(int dtype, unsigned flags, const flame_segment *segs
 int flame_agg_reduce_mixed(int client_dtype, int agg_dtype, unsigned flags, const flame_segment *segs,
                            int32_t n_segs, int64_t n_chunks, const void *const *clients,
                            int32_t n_clients, const float *rates32, const float *scales32, void *stream);
+
+/*
+ * MXFP8 updates into an fp32 aggregate in one launch.  flame has no counterpart: the contract is this
+ * project's own.  An update holds, per tensor, one OCP e4m3fn or e5m2 byte per element
+ * and one E8M0 scale byte per block of 32 flat C-order elements (the last block may be partial), as
+ * flame_amd.mx.quantize writes them.  The arguments are flame_agg_reduce_mixed's plus block_scales.
+ *   client_dtype : FLAME_FP8_E4M3 or FLAME_FP8_E5M2: every client tensor of every segment.
+ *   agg_dtype    : FLAME_F32: every segment's in / out.
+ *   segs         : chunk_begin counts chunks of flame_chunk_elems(client_dtype) = 4,096 elements (one
+ *                  4,096-byte tile: a lane owns 16 elements, half a block).  client_tile_stride must
+ *                  be 0: the engine never builds a tiled MX row, and the kernel does not read the field.
+ *   clients      : device array [n_segs][n_clients] of pointers to the element bytes.
+ *   block_scales : device array [n_segs][n_clients] of pointers to the scale bytes,
+ *                  ceil(numel / 32) each, of ANY alignment (FLAME_SEG_UNALIGNED does not speak of them);
+ *                  device addresses or translated pinned-host addresses, as client rows are.
+ *   rates32      : device [n_clients]; scales32: device [n_clients] clip scales, or NULL for the plain round.
+ * Per element e, clients in order, no FMA:
+ *   acc = in[e]                                                  (fp32)
+ *   x   = f32(q_i[e]) * f32_e8m0(s_i[e / 32])                    one IEEE fp32 multiply, denormals kept;
+ *         f32_e8m0(b) = 2^(b - 127) (b = 0: the fp32 subnormal 2^-127); a NaN element or scale byte 255
+ *         gives NaN
+ *         with scales32: x = round_f32(x * scale_i)
+ *   t   = round_f32(x * rate_i)
+ *   acc = round_f32(acc + t)
+ *   out[e] = acc
+ * x is flame_amd.mx.dequantize's value of the element, so the result is bit for bit what
+ * flame_agg_reduce (with scales32: flame_agg_reduce_scaled) gives for FLAME_F32 over the
+ * dequantized update.  Refusals, each before any HIP call and named in flame_last_error: a pair other
+ * than (e4m3 | e5m2, f32) is FLAME_ENOTSUP (the message names both dtypes); FLAME_AGG_INIT_FIRST is
+ * FLAME_ENOTSUP; FLAME_AGG_SEG_RATES is FLAME_ENOTSUP; any flag beyond FLAME_AGG_XCD_MAP, a NULL
+ * table or rate array, n_segs <= 0, n_clients < 1 or n_chunks outside [1, 2^31) is FLAME_EINVAL.
+ * Device tables only (no kernel-argument variant).  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_reduce_mx(int client_dtype, int agg_dtype, unsigned flags, const flame_segment *segs,
+                        int32_t n_segs, int64_t n_chunks, const void *const *clients,
+                        const void *const *block_scales, int32_t n_clients, const float *rates32,
+                        const float *scales32, void *stream);
 
 /*
  * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,
