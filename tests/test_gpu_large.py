@@ -5,47 +5,19 @@ FedBuff's fused scale_add + delta (the hierarchy kernel with one middle) and Fed
 fused adaptive round -- checked against the oracle at the index boundaries (2^30, 2^31, the
 chunk seams, the ragged tail) and 20,000 random indices.  Inputs come from the counter
 generator on the device; only the sampled elements travel to the host."""
-import numpy as np
+from functools import partial
+
 import pytest
 import torch
 
+import large_case
 import scenarios as S
+from large_case import DEV, P32 as P, _at, _free, _need
 
 pytestmark = [pytest.mark.gpu, pytest.mark.oracle]
 
-DEV = "cuda:0"
-P = (1 << 31) + 4099           # a ragged tail after the 2^31st element
-
-
-def _need(gb):
-    free, _ = torch.cuda.mem_get_info()
-    if free < gb * 1e9:
-        pytest.skip(f"needs {gb} GB of HBM, {free / 1e9:.1f} GB free")
-
-
-def _synth(seed, stream, sigma):
-    from flame_amd import engine
-    t = torch.empty(P, device=DEV)
-    engine.synth_fill_(t, seed, stream, 0, sigma)
-    return t
-
-
-def _index():
-    edges = []
-    for b in (0, 1 << 30, (1 << 31) - 2048, 1 << 31, P - 4099, P - 2048):
-        edges += list(range(max(0, b - 3), min(P, b + 3)))
-    edges += [1023, 1024, 1025, 2047, 2048, P - 1]
-    rand = np.random.default_rng(0).integers(0, P, 20_000)
-    return torch.from_numpy(np.unique(np.concatenate([np.array(edges), rand])).astype(np.int64))
-
-
-def _at(t, idx):
-    return t.index_select(0, idx.to(t.device)).cpu()
-
-
-def _free():
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
+_synth = partial(large_case._synth, P)      # fp32, the sample set of P
+_index = partial(large_case.index, P)
 
 
 def _make(sort, **kw):
