@@ -489,22 +489,73 @@ __device__ __forceinline__ int find_segment(const SEG* __restrict__ segs, int n_
     return lo;
 }
 
-// Byte offset of this lane's first element inside every client's data for the
-// workgroup's chunk: contiguous (e0 * sizeof) or tiled (chunk * client_tile_stride + lane).
-template <int DT, typename SEG>
-__device__ __forceinline__ int64_t client_offset(const SEG& sg, int64_t chunk) {
-    using T = typename Tr<DT>::T;
-    const int64_t cl = chunk - sg.chunk_begin;
-    const int64_t lane_elem = static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
-    if (sg.client_tile_stride)
-        return cl * sg.client_tile_stride + lane_elem * static_cast<int64_t>(sizeof(T));
-    return (cl * chunk_elems<DT>() + lane_elem) * static_cast<int64_t>(sizeof(T));
+// The opening of every chunked kernel.  A workgroup owns chunk `chunk` of the launch: kBlock x EPT
+// elements of segment s (any of the three segment structs), of which a lane owns EPT, one 16-byte
+// vector (MXFP8 / mixed: one client vector), at elements e0 .. e0 + EPT - 1.  Each member is evaluated
+// where it is called and kernels copy sg out: the listings depend on both (profiles/lane_isa_diff.log).
+template <typename SEG, int EPT>
+struct LaneChunk {
+    static constexpr int64_t CE = static_cast<int64_t>(kBlock) * EPT;      // elements per chunk
+    int s;              // the segment's index (wave-uniform)
+    SEG sg;             // its table entry
+    int64_t chunk;
+    int64_t e0;         // the lane's first element
+    __device__ __forceinline__ LaneChunk(const SEG* segs, int n_segs, int64_t chunk_)
+        : s(find_segment(segs, n_segs, chunk_)), sg(segs[s]), chunk(chunk_),
+          e0((chunk - sg.chunk_begin) * CE + static_cast<int64_t>(threadIdx.x) * EPT) {}
+    // the lane has an element inside the segment
+    __device__ __forceinline__ bool live() const { return e0 < sg.numel; }
+    // the lane's vector is whole and aligned: 16-byte accesses; else element-wise with bounds
+    __device__ __forceinline__ bool vec() const { return (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED); }
+    // the segment's row of a table of n pointers per segment
+    __device__ __forceinline__ const uint64_t* row(const uint64_t* __restrict__ t, int64_t n) const { return t + s * n; }
+    // byte offset of the lane's first element (of `esize` bytes) inside a row's data: contiguous
+    // (stride 0) or tiled, the segment's chunks `stride` bytes apart (a slab)
+    __device__ __forceinline__ int64_t offset(int64_t stride, int64_t esize) const {
+        const int64_t cl = chunk - sg.chunk_begin;
+        const int64_t lane_elem = static_cast<int64_t>(threadIdx.x) * EPT;
+        if (stride) return cl * stride + lane_elem * esize;
+        return (cl * CE + lane_elem) * esize;
+    }
+};
+
+// One lane's elements between memory and registers (EPT x sizeof(T) is one 16-byte vector, or
+// several: the fp32 base of the mixed and MXFP8 kernels).  VEC: vector accesses (nt: read once);
+// else element by element inside [e0, numel), zeros loaded beyond it.
+template <bool VEC, bool NT = false, typename T, int EPT>
+__device__ __forceinline__ void lane_load(const T* p, T (&x)[EPT], int64_t e0, int64_t numel) {
+    constexpr int PER = 16 / sizeof(T);
+    static_assert(EPT % PER == 0, "whole 16-byte vectors");
+    if constexpr (VEC) {
+#pragma unroll
+        for (int q = 0; q < EPT; q += PER) {
+            const V16 v = NT ? ld_nt(p + q) : ld_v(p + q);
+            __builtin_memcpy(x + q, v.w, 16);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
+    }
+}
+template <bool VEC, typename T, int EPT>
+__device__ __forceinline__ void lane_store(T* p, const T (&x)[EPT], int64_t e0, int64_t numel) {
+    constexpr int PER = 16 / sizeof(T);
+    if constexpr (VEC) {
+#pragma unroll
+        for (int q = 0; q < EPT; q += PER) {
+            V16 v;
+            __builtin_memcpy(v.w, x + q, 16);
+            st_v(p + q, v);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < EPT; ++j)
+            if (e0 + j < numel) st1(p + j, x[j]);
+    }
 }
 
 // ---------------------------------------------------------------- reduction core
-// A lane owns one 16-byte vector of the chunk, at elements e0 .. e0 + EPT - 1.
-// Reduce clients [0, n) into acc for those slots.  VEC: the vector whole and
-// aligned; else element-wise with bounds (tails / unaligned views).  SCALED (flame_agg_reduce_scaled
+// Reduce clients [0, n) into acc for the lane's slots (LaneChunk).  VEC as in lane_load.  SCALED (flame_agg_reduce_scaled
 // only; a template parameter, so no other kernel carries the branch): client i's value is first
 // multiplied by its clip scale, tmp = round(round(v * scale_i) * rate_i).
 // AD (flame_agg_reduce_mixed only; DT everywhere else): the accumulator's dtype where it differs from
@@ -523,13 +574,7 @@ __device__ __forceinline__ void reduce_clients(typename Tr<AD>::A (&acc)[Tr<DT>:
     auto rate32 = [&](int c) -> float { if constexpr (DT == FLAME_F64) return 0.f; else return r32[c]; };
     auto rate64 = [&](int c) -> double { if constexpr (DT == FLAME_F64) return r64[c]; else return 0.0; };
     auto load_client = [&](int c, T (&x)[EPT]) {
-        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
-        if constexpr (VEC) {
-            unpack<T, EPT>(ld_nt(p), x);
-        } else {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
-        }
+        lane_load<VEC, true>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff), x, e0, numel);
     };
     // tmp of client c's element: the rate product, after the scale product when SCALED
     auto tmp_of = [&](int c, const float r, const double rd, T xv) {
@@ -584,18 +629,18 @@ __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ s
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return false;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return false;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(T));
     const bool init_first = (flags & FLAME_AGG_INIT_FIRST) != 0;
     if (flags & FLAME_AGG_SEG_RATES) {  // one rate row per segment
-        if (r32) r32 += static_cast<int64_t>(s) * n_clients;
-        if (r64) r64 += static_cast<int64_t>(s) * n_clients;
+        if (r32) r32 += static_cast<int64_t>(lc.s) * n_clients;
+        if (r64) r64 += static_cast<int64_t>(lc.s) * n_clients;
     }
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = lc.vec();
     A acc[EPT];
     const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
     op = reinterpret_cast<T*>(sg.out) + e0;
@@ -625,16 +670,15 @@ __device__ __forceinline__ bool reduce_chunk(const flame_segment* __restrict__ s
     return false;
 }
 
-template <typename T>
-__device__ __forceinline__ void store_chunk(T* op, const V16& ov) {
-    st_v(op, ov);
-}
-
 // Workgroup slot of block b when the 8 XCDs (dispatched round-robin) each take one
 // contiguous eighth of the slots (FLAME_AGG_XCD_MAP / FLAME_OPT_XCD_MAP): a bijection.
 __device__ __forceinline__ int64_t xcd_slot(int64_t b, int64_t n) {
     const int64_t q = n / 8, r = n % 8, x = b % 8;
     return x * q + (x < r ? x : r) + b / 8;
+}
+// The workgroup's slot: that map where the launch's flag bit asks for it, else launch order.
+__device__ __forceinline__ int64_t wg_slot(unsigned xcd_map) {
+    return xcd_map ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
 }
 
 // G chunks per workgroup (G = 1: chunk = workgroup slot, in launch order or the XCD-contiguous
@@ -646,12 +690,12 @@ __device__ __forceinline__ void agg_reduce_body(const flame_segment* __restrict_
                                                 const float* __restrict__ r32, const double* __restrict__ r64,
                                                 unsigned flags, int64_t n_chunks) {
     using T = typename Tr<DT>::T;
-    const int64_t slot = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t slot = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if constexpr (G == 1) {
         if (slot >= n_chunks) return;
         V16 ov;
         T* op;
-        if (reduce_chunk<DT, CU>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op)) store_chunk(op, ov);
+        if (reduce_chunk<DT, CU>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op)) st_v(op, ov);
     } else {
         static_assert(G <= 32 && G * kBlock * sizeof(V16) <= 128 * 1024, "agg_reduce_body: G chunks' outputs exceed the LDS");
         __shared__ V16 held[G][kBlock];
@@ -670,6 +714,7 @@ __device__ __forceinline__ void agg_reduce_body(const flame_segment* __restrict_
 #pragma unroll 1
         for (int g = 0; g < G; ++g) {
             if (!(pending >> g & 1u)) continue;
+            // (through LaneChunk the f16 instantiation swaps two registers: profiles/lane_isa_diff.log)
             const int64_t chunk = slot * G + g;
             const flame_segment& sg = segs[find_segment(segs, n_segs, chunk)];
             T* op = reinterpret_cast<T*>(sg.out) + (chunk - sg.chunk_begin) * chunk_elems<DT>() +
@@ -722,12 +767,12 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_scaled_kernel(const flame_s
                                                                    const double* __restrict__ s64, unsigned flags,
                                                                    int64_t n_chunks) {
     using T = typename Tr<DT>::T;
-    const int64_t slot = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t slot = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if (slot >= n_chunks) return;
     V16 ov;
     T* op;
     if (reduce_chunk<DT, CU, true>(segs, n_segs, clients, n_clients, r32, r64, flags, slot, ov, op, s32, s64))
-        store_chunk(op, ov);
+        st_v(op, ov);
 }
 
 // ---------------------------------------------------------------- 16-bit updates into an fp32 aggregate
@@ -744,18 +789,18 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mixed_kernel(const flame_se
                                                                   int64_t n_chunks) {
     static_assert(CD == FLAME_BF16 || CD == FLAME_F16, "16-bit clients, one client vector per lane");
     constexpr int EPT = Tr<CD>::EPT;        // 8 client values = 2 fp32 vectors of 4
-    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t chunk = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if (chunk >= n_chunks) return;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<CD>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<CD>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(typename Tr<CD>::T));
     const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
     float* op = reinterpret_cast<float*>(sg.out) + e0;
     float acc[EPT];
-    if (e0 + EPT <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
+    if (lc.vec()) {       // (either arm through lane_load / lane_store moves registers: profiles/lane_isa_diff.log)
         float b[2][4];
         unpack<float, 4>(ld_v(bp), b[0]);
         unpack<float, 4>(ld_v(bp + 4), b[1]);
@@ -907,28 +952,21 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mx_kernel(const flame_segme
     static_assert(CD == FLAME_FP8_E4M3 || CD == FLAME_FP8_E5M2, "8-bit clients, one client vector per lane");
     constexpr int EPT = kMxEPT;             // 16 client bytes = 4 fp32 vectors of 4
     static_assert(kBlock * EPT == FLAME_TILE_BYTES && kMxBlock % EPT == 0, "a chunk is one tile; a lane stays inside one block");
-    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t chunk = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if (chunk >= n_chunks) return;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * (kBlock * EPT) + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const uint64_t* bsp = block_scales + static_cast<int64_t>(s) * n_clients;
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const uint64_t* bsp = lc.row(block_scales, n_clients);
     const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
     float* op = reinterpret_cast<float*>(sg.out) + e0;
     float acc[EPT];
-    if (e0 + EPT <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
-        float b[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) unpack<float, 4>(ld_v(bp + 4 * q), b[q]);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) acc[j] = b[j / 4][j % 4];
+    if (lc.vec()) {       // (the element-wise arm below through lane_load / lane_store moves registers: profiles/lane_isa_diff.log)
+        lane_load<true>(bp, acc, e0, sg.numel);
         reduce_clients_mx<CD, CU, true, SCALED>(acc, cp, bsp, n_clients, r32, s32, e0, sg.numel);
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) b[j / 4][j % 4] = acc[j];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) st_v(op + 4 * q, pack<float, 4>(b[q]));
+        lane_store<true>(op, acc, e0, sg.numel);
         return;
     }
 #pragma unroll
@@ -1076,15 +1114,9 @@ __device__ __forceinline__ void trimmed_clients(double (&acc)[Tr<DT>::EPT], cons
             hi[j][r] = j < k ? K::lowest() : K::highest();
         }
     auto load_client = [&](int c) -> V16 {
-        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
-        if constexpr (VEC) {
-            return ld_nt(p);
-        } else {
-            T x[EPT];
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
-            return pack<T, EPT>(x);
-        }
+        T x[EPT];
+        lane_load<VEC, true>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff), x, e0, numel);
+        return pack<T, EPT>(x);
     };
     // PHASE 0: into lo; 1: what leaves lo into hi; 2: what leaves hi is kept
     auto arrive = [&](auto phase, const V16& v) {
@@ -1134,40 +1166,40 @@ __global__ __launch_bounds__(kBlock) void agg_trimmed_kernel(const flame_segment
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t chunk = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if (chunk >= n_chunks) return;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;
+    const flame_segment& sg = lc.sg;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(T));
     const bool init_first = (flags & FLAME_AGG_INIT_FIRST) != 0;
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = lc.vec();
     const double kept = static_cast<double>(n_clients - 2 * trim_k);
-    const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
-    T* op = reinterpret_cast<T*>(sg.out) + e0;
+    const T* bp = reinterpret_cast<const T*>(sg.in) + lc.e0;
+    T* op = reinterpret_cast<T*>(sg.out) + lc.e0;
     double acc[EPT];
 #pragma unroll
     for (int j = 0; j < EPT; ++j) acc[j] = 0.0;
-    // out = base + mean, one add in the dtype (torch-CPU's `base += mean`); INIT_FIRST: the mean
+    // out = base + mean, one add in the dtype (torch-CPU's `base += mean`); INIT_FIRST: the mean.  (As one
+    // function shared with agg_select_kernel both kernels' registers move: profiles/lane_isa_diff.log)
     auto result = [&](double a, T b) -> T {
         const A mean = trim_round<DT>(a / kept);
         return X::st(init_first ? mean : X::add(X::ld(b), mean));
     };
     if (vec) {
-        trimmed_clients<DT, KT, trim_unroll<KT>(), true>(acc, cp, n_clients, trim_k, e0, sg.numel, coff);
+        trimmed_clients<DT, KT, trim_unroll<KT>(), true>(acc, cp, n_clients, trim_k, lc.e0, sg.numel, coff);
         T b[EPT], o[EPT];
         if (!init_first) unpack<T, EPT>(ld_v(bp), b);
 #pragma unroll
         for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
-        store_chunk(op, pack<T, EPT>(o));
+        st_v(op, pack<T, EPT>(o));
         return;
     }
-    trimmed_clients<DT, KT, 1, false>(acc, cp, n_clients, trim_k, e0, sg.numel, coff);
+    trimmed_clients<DT, KT, 1, false>(acc, cp, n_clients, trim_k, lc.e0, sg.numel, coff);
 #pragma unroll
     for (int j = 0; j < EPT; ++j)
-        if (e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
+        if (lc.e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
 }
 
 // ---------------------------------------------------------------- trimmed mean / median by radix selection
@@ -1240,16 +1272,10 @@ __device__ __forceinline__ void select_clients(double (&acc)[Tr<DT>::EPT], uint3
     using U = typename S::U;
     constexpr int EPT = X::EPT, GE = S::GE, NG = EPT / GE, CU = FLAME_T_SEL_UNROLL;
     auto load_client = [&](int c, auto last) -> V16 {
-        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff);
-        if constexpr (VEC) {
-            if constexpr (decltype(last)::value) return ld_nt(p);
-            else return ld_v(p);
-        } else {
-            T x[EPT];
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < numel) ? ld1(p + j) : T(0);
-            return pack<T, EPT>(x);
-        }
+        T x[EPT];
+        lane_load<VEC, decltype(last)::value != 0>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(cp[c]) + coff), x,
+                                                   e0, numel);
+        return pack<T, EPT>(x);
     };
     auto each_client = [&](auto last, auto&& f) {
         int i = 0;
@@ -1353,19 +1379,18 @@ __global__ __launch_bounds__(kBlock) void agg_select_kernel(const flame_segment*
     constexpr int EPT = X::EPT;
     __shared__ uint32_t h0[kSelBins * kBlock], h1[kSelBins * kBlock], h2[kSelBins * kBlock], h3[kSelBins * kBlock];
     static_assert(4 * sizeof(h0) <= 64 * 1024, "agg_select_kernel: the histograms exceed 64 KiB");
-    const int64_t chunk = (flags & FLAME_AGG_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t chunk = wg_slot(flags & FLAME_AGG_XCD_MAP);
     if (chunk >= n_chunks) return;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;                      // no barrier below: the histograms are lane-private
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;                          // no barrier below: the histograms are lane-private
+    const flame_segment& sg = lc.sg;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(T));
     const bool init_first = (flags & FLAME_AGG_INIT_FIRST) != 0;
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = lc.vec();
     const double kept = static_cast<double>(n_clients - 2 * trim_k);
-    const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
-    T* op = reinterpret_cast<T*>(sg.out) + e0;
+    const T* bp = reinterpret_cast<const T*>(sg.in) + lc.e0;
+    T* op = reinterpret_cast<T*>(sg.out) + lc.e0;
     uint32_t* const h[4] = {h0 + threadIdx.x, h1 + threadIdx.x, h2 + threadIdx.x, h3 + threadIdx.x};
     double acc[EPT];
 #pragma unroll
@@ -1375,18 +1400,18 @@ __global__ __launch_bounds__(kBlock) void agg_select_kernel(const flame_segment*
         return X::st(init_first ? mean : X::add(X::ld(b), mean));
     };
     if (vec) {
-        select_clients<DT, true>(acc, h, cp, n_clients, trim_k, e0, sg.numel, coff);
+        select_clients<DT, true>(acc, h, cp, n_clients, trim_k, lc.e0, sg.numel, coff);
         T b[EPT], o[EPT];
         if (!init_first) unpack<T, EPT>(ld_v(bp), b);
 #pragma unroll
         for (int j = 0; j < EPT; ++j) o[j] = result(acc[j], init_first ? T(0) : b[j]);
-        store_chunk(op, pack<T, EPT>(o));
+        st_v(op, pack<T, EPT>(o));
         return;
     }
-    select_clients<DT, false>(acc, h, cp, n_clients, trim_k, e0, sg.numel, coff);
+    select_clients<DT, false>(acc, h, cp, n_clients, trim_k, lc.e0, sg.numel, coff);
 #pragma unroll
     for (int j = 0; j < EPT; ++j)
-        if (e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
+        if (lc.e0 + j < sg.numel) st1(op + j, result(acc[j], init_first ? T(0) : ld1(bp + j)));
 }
 
 // ---------------------------------------------------------------- update statistics (update guard)
@@ -2024,15 +2049,15 @@ __device__ __forceinline__ bool fedopt_chunk(const flame_segment* __restrict__ s
     using X = Tr<DT>;
     using T = typename X::T;
     constexpr int EPT = X::EPT;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return false;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return false;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(T));
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const bool cur_avg = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;   // cur IS the FedAvg result
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = lc.vec();
     float acc[EPT];
     const T* base = reinterpret_cast<const T*>(sg.in) + e0;
     const T* curp = reinterpret_cast<const T*>(sg.cur) + e0;
@@ -2114,7 +2139,7 @@ __device__ __forceinline__ void fedopt_body(const flame_segment* __restrict__ se
                                             const float* __restrict__ r32, unsigned flags, float b1,
                                             float omb1, float b2, float omb2, float eta, float tau,
                                             int64_t n_chunks) {
-    const int64_t wg = (flags & FLAME_OPT_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t wg = wg_slot(flags & FLAME_OPT_XCD_MAP);
     if constexpr (G == 1) {
         (void)n_chunks;
         fedopt_chunk<DT, VARIANT, CU>(segs, n_segs, wg, clients, n_clients, r32, flags, b1, omb1, b2,
@@ -2135,10 +2160,9 @@ __device__ __forceinline__ void fedopt_body(const flame_segment* __restrict__ se
 #pragma unroll 1
         for (int g = 0; g < G; ++g) {
             if (!(pending >> g & 1u)) continue;
-            const int64_t chunk = wg * G + g;
-            const flame_segment& sg = segs[find_segment(segs, n_segs, chunk)];
-            const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() +
-                               static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
+            const LaneChunk<flame_segment, Tr<DT>::EPT> lc(segs, n_segs, wg * G + g);
+            const flame_segment sg = lc.sg;
+            const int64_t e0 = lc.e0;
             T* outs[4] = {sg.out ? reinterpret_cast<T*>(sg.out) + e0 : nullptr, reinterpret_cast<T*>(sg.m) + e0,
                           reinterpret_cast<T*>(sg.v) + e0, reinterpret_cast<T*>(sg.cur_out) + e0};
 #pragma unroll
@@ -2208,7 +2232,7 @@ __device__ __forceinline__ void fedopt_chain_body(const flame_segment& sg, int64
     using X = Tr<DT>;
     using T = typename X::T;
     constexpr int EPT = X::EPT;
-    const int nv = VEC ? EPT : static_cast<int>(sg.numel - e0 < EPT ? sg.numel - e0 : EPT);
+    const int nv = VEC ? EPT : static_cast<int>(sg.numel - e0 < EPT ? sg.numel - e0 : EPT);   // (not lane_load: lane_isa_diff.log)
     bool aliased = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const T* bp = reinterpret_cast<const T*>(sg.in) + e0;
@@ -2461,15 +2485,13 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel(const flame_segmen
                                                               const uint8_t* __restrict__ step_end, unsigned flags,
                                                               float b1, float omb1, float b2, float omb2, float eta,
                                                               float tau) {
-    const int64_t chunk = blockIdx.x;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t c0 = (chunk - sg.chunk_begin) * chunk_elems<DT>();
-    const int64_t e0 = c0 + static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
-    bool full = c0 + chunk_elems<DT>() <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED);   // workgroup-uniform
+    const LaneChunk<flame_segment, Tr<DT>::EPT> lc(segs, n_segs, blockIdx.x);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(typename Tr<DT>::T));
+    bool full = (lc.chunk - sg.chunk_begin) * lc.CE + lc.CE <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED);   // workgroup-uniform (on the copy: lane_isa_diff.log)
     // the packed fp16 body's FedYogi sign is torch's only while 1 - beta_2 >= 0 (sign_h2): a beta_2
     // above 1 takes the per-element body for every chunk (a kernel argument: uniform)
     if constexpr (DT == FLAME_F16 && kF16Native && VARIANT == FLAME_FEDYOGI) full &= !(omb2 < 0.f);
@@ -2529,15 +2551,15 @@ __device__ __forceinline__ void fedopt_chunk_f64(const flame_segment* __restrict
                                                  const double* __restrict__ r64, unsigned flags, const Hyper64& h) {
     constexpr int DT = FLAME_F64;
     constexpr int EPT = Tr<DT>::EPT;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(double));
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const bool cur_avg = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;   // cur IS the FedAvg result
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
+    const bool vec = lc.vec();
     double acc[EPT];
     const double* base = reinterpret_cast<const double*>(sg.in) + e0;
     const double* curp = reinterpret_cast<const double*>(sg.cur) + e0;
@@ -2586,7 +2608,7 @@ __global__ __launch_bounds__(kBlock) void fedopt_kernel_f64(const flame_segment*
                                                             const uint64_t* __restrict__ clients, int n_clients,
                                                             const double* __restrict__ r64, unsigned flags,
                                                             const Hyper64 h, int64_t n_chunks) {
-    const int64_t chunk = (flags & FLAME_OPT_XCD_MAP) ? xcd_slot(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int64_t chunk = wg_slot(flags & FLAME_OPT_XCD_MAP);
     if (chunk >= n_chunks) return;
     fedopt_chunk_f64<VARIANT, CU>(segs, n_segs, chunk, clients, n_clients, r64, flags, h);
 }
@@ -2602,7 +2624,7 @@ __device__ __forceinline__ void fedopt_chain_body_f64(const flame_segment& sg, i
                                                       const Hyper64& h) {
     using X = Tr<FLAME_F64>;
     constexpr int EPT = X::EPT;
-    const int nv = VEC ? EPT : static_cast<int>(sg.numel - e0 < EPT ? sg.numel - e0 : EPT);
+    const int nv = VEC ? EPT : static_cast<int>(sg.numel - e0 < EPT ? sg.numel - e0 : EPT);   // (not lane_load: lane_isa_diff.log)
     bool aliased = (sg.flags & FLAME_SEG_CUR_IS_AVG) != 0;
     const bool zero_state = (flags & FLAME_OPT_STATE_ZERO) != 0;
     const double* bp = reinterpret_cast<const double*>(sg.in) + e0;
@@ -2684,19 +2706,14 @@ __global__ __launch_bounds__(kBlock) void fedopt_chain_kernel_f64(const flame_se
                                                                   int n_clients, const double* __restrict__ r64,
                                                                   const uint8_t* __restrict__ step_end,
                                                                   unsigned flags, const Hyper64 h) {
-    constexpr int DT = FLAME_F64;
-    const int64_t chunk = blockIdx.x;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t c0 = (chunk - sg.chunk_begin) * chunk_elems<DT>();
-    const int64_t e0 = c0 + static_cast<int64_t>(threadIdx.x) * Tr<DT>::EPT;
-    if (e0 >= sg.numel) return;
-    const uint64_t* cp = clients + static_cast<int64_t>(s) * n_clients;
-    const int64_t coff = client_offset<DT>(sg, chunk);
-    if (c0 + chunk_elems<DT>() <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED))   // workgroup-uniform
-        fedopt_chain_body_f64<VARIANT, CU, true>(sg, e0, cp, coff, n_clients, r64, step_end, flags, h);
+    const LaneChunk<flame_segment, Tr<FLAME_F64>::EPT> lc(segs, n_segs, blockIdx.x);
+    if (!lc.live()) return;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const int64_t coff = lc.offset(lc.sg.client_tile_stride, sizeof(double));
+    if ((lc.chunk - lc.sg.chunk_begin) * lc.CE + lc.CE <= lc.sg.numel && !(lc.sg.flags & FLAME_SEG_UNALIGNED))   // as fedopt_chain_kernel
+        fedopt_chain_body_f64<VARIANT, CU, true>(lc.sg, lc.e0, cp, coff, n_clients, r64, step_end, flags, h);
     else
-        fedopt_chain_body_f64<VARIANT, 1, false>(sg, e0, cp, coff, n_clients, r64, step_end, flags, h);
+        fedopt_chain_body_f64<VARIANT, 1, false>(lc.sg, lc.e0, cp, coff, n_clients, r64, step_end, flags, h);
 }
 
 // ---------------------------------------------------------------- FedBuff scale-add (+delta)
@@ -2744,16 +2761,15 @@ __global__ __launch_bounds__(kEwBlock) void scale_add_kernel(const flame_segment
     using S = SA<DT>;
     using T = typename S::T;
     constexpr int EPT = S::EPT;
-    const int64_t chunk = blockIdx.x;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * (kEwBlock * EPT) + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
+    static_assert(kEwBlock == kBlock, "LaneChunk's chunk is kBlock lanes");
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, blockIdx.x);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
     T* bp = reinterpret_cast<T*>(sg.out) + e0;
     const T* ap = reinterpret_cast<const T*>(sg.in) + e0;
     T* dp = sg.cur_out ? reinterpret_cast<T*>(sg.cur_out) + e0 : nullptr;
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    if (vec) {
+    if (lc.vec()) {
         T b[EPT], a[EPT], d[EPT];
         unpack<T, EPT>(ld_v(bp), b);
         unpack<T, EPT>(ld_v(ap), a);
@@ -2869,19 +2885,18 @@ __device__ __forceinline__ void hier_fedbuff_body(const flame_hier_segment* __re
     using T = typename X::T;
     using A = typename X::A;
     constexpr int EPT = X::EPT;
-    const int64_t chunk = blockIdx.x;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_hier_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const int64_t coff = client_offset<DT>(sg, chunk);
-    const uint64_t* wrow = mid_w + static_cast<int64_t>(s) * n_mids;
-    const uint64_t* drow = mid_delta ? mid_delta + static_cast<int64_t>(s) * n_mids : nullptr;
-    const uint64_t* crow = clients + static_cast<int64_t>(s) * n_mids * n_clients;
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    // byte offset of this lane's elements inside every middle's weights: contiguous or tiled
+    const LaneChunk<flame_hier_segment, EPT> lc(segs, n_segs, blockIdx.x);
+    if (!lc.live()) return;
+    const flame_hier_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const int64_t coff = lc.offset(sg.client_tile_stride, sizeof(T));
+    const uint64_t* wrow = lc.row(mid_w, n_mids);
+    const uint64_t* drow = mid_delta ? lc.row(mid_delta, n_mids) : nullptr;
+    const uint64_t* crow = clients + static_cast<int64_t>(lc.s) * n_mids * n_clients;
+    const bool vec = lc.vec();
+    // inside every middle's weights, contiguous or tiled (not lc.offset: profiles/lane_isa_diff.log)
     const int64_t woff = sg.mid_tile_stride
-        ? (chunk - sg.chunk_begin) * sg.mid_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * sizeof(T)
+        ? (lc.chunk - sg.chunk_begin) * sg.mid_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * sizeof(T)
         : e0 * static_cast<int64_t>(sizeof(T));
     auto mid_ptr = [&](int m) { return reinterpret_cast<T*>(reinterpret_cast<char*>(wrow[m]) + woff); };
     A top[EPT];
@@ -3029,23 +3044,10 @@ __device__ __forceinline__ void feddyn_chunk(const flame_dyn_segment& sg, const 
     constexpr int EPT = X::EPT;
     const int64_t ooff = e0 * static_cast<int64_t>(sizeof(T));   // base / average / cld: contiguous
     auto load = [&](uint64_t base, int64_t off, T (&x)[EPT]) {
-        const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
-        if constexpr (VEC) {
-            unpack<T, EPT>(ld_nt(p), x);
-        } else {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) x[j] = (e0 + j < sg.numel) ? ld1(p + j) : T(0);
-        }
+        lane_load<VEC, true>(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off), x, e0, sg.numel);
     };
     auto store = [&](void* base, int64_t off, const T (&x)[EPT]) {
-        T* p = reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off);
-        if constexpr (VEC) {
-            st_v(p, pack<T, EPT>(x));
-        } else {
-#pragma unroll
-            for (int j = 0; j < EPT; ++j)
-                if (e0 + j < sg.numel) st1(p + j, x[j]);
-        }
+        lane_store<VEC>(reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off), x, e0, sg.numel);
     };
     A avg[EPT], mean[EPT];
     {
@@ -3111,22 +3113,19 @@ __global__ __launch_bounds__(kBlock) void feddyn_kernel(const flame_dyn_segment*
     constexpr int EPT = X::EPT;
     // XCD-contiguous chunk map: 512 x 12M fp32 -0.7 % (cache order) / -1.4 % (other order)
     // (profiles/r02_feddyn_xcd_sweep.log)
-    const int64_t chunk = xcd_slot(blockIdx.x, gridDim.x);
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_dyn_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const int64_t coff = client_offset<DT>(sg, chunk);
-    // histories: contiguous, or tiled like the arrivals (a FedDyn history store in the slab layout)
-    const int64_t hoff = sg.hist_tile_stride
-        ? (chunk - sg.chunk_begin) * sg.hist_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * static_cast<int64_t>(sizeof(typename X::T))
-        : e0 * static_cast<int64_t>(sizeof(typename X::T));
-    const uint64_t* row = steps + static_cast<int64_t>(s) * n_steps * 3;
-    const bool vec = (e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED);
-    if (vec)
-        feddyn_chunk<DT, CU, true>(sg, row, sflags, n_steps, n_phase1, ra32, rm32, ra64, rm64, e0, coff, hoff);
+    const LaneChunk<flame_dyn_segment, EPT> lc(segs, n_segs, xcd_slot(blockIdx.x, gridDim.x));
+    if (!lc.live()) return;
+    const int64_t coff = lc.offset(lc.sg.client_tile_stride, sizeof(typename X::T));
+    // histories: contiguous, or tiled like the arrivals (a FedDyn history store in the slab layout); not
+    // lc.offset: profiles/lane_isa_diff.log
+    const int64_t hoff = lc.sg.hist_tile_stride
+        ? (lc.chunk - lc.sg.chunk_begin) * lc.sg.hist_tile_stride + static_cast<int64_t>(threadIdx.x) * EPT * static_cast<int64_t>(sizeof(typename X::T))
+        : lc.e0 * static_cast<int64_t>(sizeof(typename X::T));
+    const uint64_t* row = steps + static_cast<int64_t>(lc.s) * n_steps * 3;
+    if (lc.vec())
+        feddyn_chunk<DT, CU, true>(lc.sg, row, sflags, n_steps, n_phase1, ra32, rm32, ra64, rm64, lc.e0, coff, hoff);
     else
-        feddyn_chunk<DT, 1, false>(sg, row, sflags, n_steps, n_phase1, ra32, rm32, ra64, rm64, e0, coff, hoff);
+        feddyn_chunk<DT, 1, false>(lc.sg, row, sflags, n_steps, n_phase1, ra32, rm32, ra64, rm64, lc.e0, coff, hoff);
 }
 
 // ---------------------------------------------------------------- synthetic generator
@@ -3262,17 +3261,16 @@ __global__ __launch_bounds__(kBlock) void noise_fill_kernel(const flame_segment*
                                                           uint32_t round, float std32, double std64) {
     using T = typename Tr<DT>::T;
     constexpr int EPT = Tr<DT>::EPT;
-    const int64_t chunk = blockIdx.x;
-    const int s = find_segment(segs, n_segs, chunk);
-    const flame_segment sg = segs[s];
-    const int64_t e0 = (chunk - sg.chunk_begin) * chunk_elems<DT>() + static_cast<int64_t>(threadIdx.x) * EPT;
-    if (e0 >= sg.numel) return;
-    const uint32_t stream = streams[s];
-    const uint64_t start = static_cast<uint64_t>(starts[s]);
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, blockIdx.x);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint32_t stream = streams[lc.s];
+    const uint64_t start = static_cast<uint64_t>(starts[lc.s]);
     const uint64_t g0 = start + static_cast<uint64_t>(e0);
     T* op = reinterpret_cast<T*>(sg.out) + e0;
     float z[4];
-    if ((e0 + EPT <= sg.numel) && !(sg.flags & FLAME_SEG_UNALIGNED) && !(start & 3u)) {
+    if (lc.vec() && !(start & 3u)) {
         T x[EPT];
         if constexpr (EPT >= 4) {
 #pragma unroll

@@ -799,6 +799,44 @@ def test_feddyn_vs_oracle_partial_participation(placement, order, history):
 
 
 @pytest.mark.oracle
+def test_feddyn_full_chunk_tail_and_unaligned_view():
+    """flame_feddyn_round over one full chunk plus a 3-element tail, as allocated and viewed from an
+    offset of one element (2 keys x 3 ends, fp32), two rounds so that the second reads the
+    histories the first wrote: average, cld model and histories bitwise equal the oracle's."""
+    from flame_amd import engine
+    O = _oracle()
+    g = torch.Generator().manual_seed(29)
+    n, ends = _chunk_plus_3(torch.float32), ["e0", "e1", "e2"]
+    two = lambda t: {"a": t.clone(), "u": t.clone()}
+    w0 = torch.randn(n, generator=g)
+    amd, ora = make_amd("feddyn", alpha=0.01), O.OracleFedDyn(alpha=0.01)
+    ca_w, co_w = _aligned_and_offset(w0), two(w0)
+    launches = []
+    engine._recorders.append(launches)
+    try:
+        for r in range(2):
+            amd.save_state(S._PRE, active_ends=ends)
+            ora.save_state(S._PRE, active_ends=ends)
+            ca, co = S.SortedCache(), S.SortedCache()
+            for i, e in enumerate(ends):
+                u = torch.randn(n, generator=g) * 1e-2
+                ca[e] = S.TR(_aligned_and_offset(u), 7 + i)
+                co[e] = S.TR(two(u), 7 + i)
+            base = {"a": ca_w["a"].clone(), "u": _aligned_and_offset(ca_w["u"].cpu())["u"]}
+            a = amd.do(base, ca, total=24)
+            o = ora.do({k: v.clone() for k, v in co_w.items()}, co, total=24)
+            S.assert_bitwise(f"feddyn r{r}/avg", S.to_cpu(a), o)
+            S.assert_bitwise(f"feddyn r{r}/cld", S.to_cpu(amd.cld_model), ora.cld_model)
+            ca_w, co_w = amd.cld_model, ora.cld_model
+    finally:
+        engine._recorders.remove(launches)
+    assert [ev[0] for ev in launches if ev[0].startswith("flame_feddyn")] == ["flame_feddyn_round"] * 2, launches
+    for e, h in ora.local_param_dict.items():
+        if h is not None:
+            S.assert_bitwise(f"feddyn hist/{e}", S.to_cpu(amd.local_param_dict[e]), h)
+
+
+@pytest.mark.oracle
 @pytest.mark.parametrize("history", ["pingpong", "pingpong_rows"])
 def test_feddyn_pingpong_key_leaves_and_returns(history):
     """under history="pingpong" a key whose arrival comes in another dtype takes the
@@ -1049,6 +1087,73 @@ def test_hierarchy_round_one_pass(dtype, placement, top_start, M, path, monkeypa
     tw = {k: v.clone() for k, v in top_w0.items()}
     top_o.scale_add_agg_weights(tw, top_agg_o, 7)
     S.assert_bitwise("oracle top w", fused[3], tw)
+
+
+def _chunk_plus_3(dtype):
+    from flame_amd import engine
+    return engine.chunk_elems(engine.dtype_code(dtype)) + 3
+
+
+def _aligned_and_offset(t):
+    """A CPU tensor as two device keys holding the same data: "a" as allocated (16-byte aligned:
+    vector accesses), "u" viewed one element into a larger buffer (FLAME_SEG_UNALIGNED: every lane
+    goes element by element)."""
+    d = t.to(DEV)
+    buf = torch.empty(d.numel() + 1, dtype=d.dtype, device=DEV)
+    buf[1:].copy_(d)
+    assert d.data_ptr() % 16 == 0 and buf[1:].data_ptr() % 16 != 0
+    return {"a": d, "u": buf[1:]}
+
+
+@pytest.mark.oracle
+def test_hierarchy_round_full_chunk_tail_and_unaligned_view():
+    """flame_hier_fedbuff over one full chunk plus a 3-element tail, as allocated and viewed from an
+    offset of one element (2 keys x 2 middles x 3 arrivals, fp32, ONE launch): top aggregate, top
+    weights, middle weights and deltas bitwise equal the oracle's op sequence."""
+    from flame_amd import engine
+    from flame_amd.optimizer.fedbuff import hierarchy_round
+    O = _oracle()
+    g = torch.Generator().manual_seed(43)
+    n, M, C, rnd = _chunk_plus_3(torch.float32), 2, 3, 9
+    two = lambda t: {"a": t.clone(), "u": t.clone()}      # the oracle's copy of the same two keys
+    ups = [[torch.randn(n, generator=g) * 1e-2 for _ in range(C)] for _ in range(M)]
+    vers = [[rnd - ((m + t) % 3) for t in range(C)] for m in range(M)]
+    mid0 = [torch.randn(n, generator=g) for _ in range(M)]
+    top_w0 = torch.randn(n, generator=g)
+    goals, mid_ver = [C, C + 1], [rnd, rnd - 1]
+    mids, tw, mids_in = [_aligned_and_offset(w) for w in mid0], _aligned_and_offset(top_w0), []
+    for m in range(M):
+        opt, agg = make_amd("fedbuff"), None
+        for t in range(C):
+            cache = S.SortedCache()
+            cache["a"] = S.TR(_aligned_and_offset(ups[m][t]), 1, vers[m][t])
+            agg = opt.do(agg, cache, total=1, version=rnd)
+        mids_in.append((mids[m], agg, goals[m], mid_ver[m]))
+    engine.kernel_events = []
+    try:
+        top_agg, deltas = hierarchy_round(mids_in, None, version=rnd, top_weights=tw, top_goal=5, with_delta=True)
+        torch.cuda.synchronize()
+        assert [e[0] for e in engine.kernel_events] == ["flame_hier_fedbuff"], engine.kernel_events
+    finally:
+        engine.kernel_events = None
+    top_o, top_agg_o = O.OracleFedBuff(), None
+    for m in range(M):
+        mo, agg_o = O.OracleFedBuff(), None
+        for t in range(C):
+            cache = S.SortedCache()
+            cache["a"] = S.TR(two(ups[m][t]), 1, vers[m][t])
+            agg_o = mo.do(agg_o, cache, total=1, version=rnd)
+        w = two(mid0[m])
+        d = {k: O.scale_add_tensor(w[k], agg_o[k], goals[m], want_delta=True) for k in w}
+        S.assert_bitwise(f"mid m{m}", S.to_cpu(mids[m]), w)
+        S.assert_bitwise(f"delta m{m}", S.to_cpu(deltas[m]), d)
+        cache = S.SortedCache()
+        cache["d"] = S.TR(d, 1, mid_ver[m])
+        top_agg_o = top_o.do(top_agg_o, cache, total=1, version=rnd)
+    S.assert_bitwise("top agg", S.to_cpu(dict(top_agg)), top_agg_o)
+    wo = two(top_w0)
+    top_o.scale_add_agg_weights(wo, top_agg_o, 5)
+    S.assert_bitwise("top w", S.to_cpu(tw), wo)
 
 
 @pytest.mark.oracle
