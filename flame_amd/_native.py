@@ -16,6 +16,7 @@ FLAME_OK, FLAME_EINVAL, FLAME_EHIP, FLAME_ENOTSUP = 0, 1, 2, 3
 FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64, FLAME_I64, FLAME_I32 = range(6)
 FLAME_U8, FLAME_I8, FLAME_I16, FLAME_BOOL = range(6, 10)       # flame_elementwise only
 FLAME_FP8_E4M3, FLAME_FP8_E5M2 = 10, 11                        # flame_agg_reduce_mx only (MXFP8 client elements)
+FLAME_FP4_E2M1 = 12                                            # flame_agg_reduce_mxfp4 only (MXFP4: two elements per byte)
 FLAME_AGG_INIT_FIRST = 1
 FLAME_AGG_SEG_RATES = 2
 FLAME_AGG_XCD_MAP = 4
@@ -40,7 +41,7 @@ EXPORTS = (
     "flame_abi_version", "flame_last_error", "flame_chunk_elems", "flame_scale_add_chunk_elems",
     "flame_agg_reduce", "flame_agg_reduce_argmeta", "flame_agg_argmeta_max_bytes",
     "flame_update_stats", "flame_update_stats_scratch_bytes", "flame_agg_reduce_scaled",
-    "flame_agg_reduce_mixed", "flame_agg_reduce_mx",
+    "flame_agg_reduce_mixed", "flame_agg_reduce_mx", "flame_agg_reduce_mxfp4",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
     "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_agg_select", "flame_agg_select_max_clients", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
@@ -105,6 +106,8 @@ def lib() -> ctypes.CDLL:
     L.flame_agg_reduce_mixed.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp, i32, vp, vp, vp]
     L.flame_agg_reduce_mx.restype = ctypes.c_int
     L.flame_agg_reduce_mx.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp, vp, i32, vp, vp, vp]
+    L.flame_agg_reduce_mxfp4.restype = ctypes.c_int
+    L.flame_agg_reduce_mxfp4.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp, vp, i32, vp, vp, vp]
     L.flame_agg_trimmed.restype = ctypes.c_int
     L.flame_agg_trimmed.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, i32, i32, vp]
     L.flame_agg_trimmed_max_k.restype = ctypes.c_int

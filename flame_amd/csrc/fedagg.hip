@@ -977,6 +977,146 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mx_kernel(const flame_segme
         if (e0 + j < sg.numel) st1(op + j, acc[j]);
 }
 
+// ---------------------------------------------------------------- MXFP4 updates into an fp32 aggregate
+// flame_agg_reduce_mxfp4: OCP e2m1 client nibbles, two per byte (flat element 2i the low nibble of
+// byte i, 2i + 1 the high one), with one E8M0 scale byte per 32 elements, summed into an fp32 base.
+// An element's value is f32_e2m1(code) * f32(scale), ONE fp32 multiply with denormals kept --
+// mx.dequantize's statement -- and from there Tr<FLAME_F32>'s ops, as in the MXFP8 kernel.  The chunk
+// is 8,192 elements (one 4,096-byte tile of client bytes): a lane owns 32 of them = one 16-byte client
+// vector, exactly one scale block (no two lanes share a scale byte, and a lane's elements never
+// straddle two), 32 fp32 accumulators and eight 16-byte vectors of in / out.  A segment starts a
+// block, so e0 is a multiple of 32 on the element-wise arm as well: one scale byte per lane and
+// client on both arms.  Register figures and residency: DESIGN.md §4.
+#ifndef FLAME_T_CLIENT_UNROLL_MXFP4
+#define FLAME_T_CLIENT_UNROLL_MXFP4 4
+#endif
+constexpr int kClientUnrollMx4 = FLAME_T_CLIENT_UNROLL_MXFP4;   // clients whose loads are in flight per lane
+// element decode: v_cvt_scalef32_pk_f32_fp4, which decodes two nibbles and scales them in one instruction
+// (1; tests/test_gpu_mxfp4.py runs all 256 x 256 (packed byte, scale byte) pairs through it: subnormal
+// products, overflow, scale bytes 0 and 255, both zeros) or integer ALU and two fp32 products (0; same
+// bits, for A/B builds)
+#ifndef FLAME_T_MXFP4_HWCVT
+#define FLAME_T_MXFP4_HWCVT 1
+#endif
+constexpr bool kMx4HwCvt = FLAME_T_MXFP4_HWCVT != 0;
+constexpr int kMx4EPT = 32;          // elements per lane: one 16-byte client vector, one whole scale block
+
+// The values of the eight nibbles of w (lowest first) times the block scale sf = f32_e8m0(byte).
+// Hardware arm: byte k of w per instruction, low nibble first; the scale operand is sf itself.
+// Integer arm: the code's three magnitude bits at fp32 bits 24..22 are e2m1's value times 2^-126
+// (exponent field 0 is the fp32 subnormal 0 or 2^-127 = 0.5 * 2^-126, fields 1..3 carry 1 .. 6), so
+// one exact product by 2^126 gives the element and the second is the contract's single rounding.
+__device__ __forceinline__ void mxfp4_val8(uint32_t w, float sf, float (&x)[8]) {
+    if constexpr (kMx4HwCvt) {
+        const f2 b0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 0);
+        const f2 b1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 1);
+        const f2 b2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 2);
+        const f2 b3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, sf, 3);
+        x[0] = b0.x; x[1] = b0.y; x[2] = b1.x; x[3] = b1.y; x[4] = b2.x; x[5] = b2.y; x[6] = b3.x; x[7] = b3.y;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t c = w >> (4 * k);
+            const float q = __fmul_rn(__uint_as_float(((c & 7u) << 22) | ((c & 8u) << 28)), 0x1p126f);   // exact
+            x[k] = __fmul_rn(q, sf);                                  // the update's value: one rounding
+        }
+    }
+}
+
+// reduce_clients_mx's sibling: clients [0, n) of one lane's kMx4EPT elements into acc.  VEC: the lane's
+// client bytes whole and aligned; else byte by byte with bounds (a byte is read when its low nibble is
+// an element; an odd numel's pad nibble lands in an accumulator that is never stored).
+template <int CU, bool VEC, bool SCALED>
+__device__ __forceinline__ void reduce_clients_mxfp4(float (&acc)[kMx4EPT], const uint64_t* __restrict__ cp,
+                                                     const uint64_t* __restrict__ bsp, int n,
+                                                     const float* __restrict__ r32, const float* __restrict__ s32,
+                                                     int64_t e0, int64_t numel) {
+    using F = Tr<FLAME_F32>;
+    constexpr int NW = kMx4EPT / 8;          // 32-bit words of client nibbles per lane
+    struct Ld { uint32_t q[NW]; uint32_t sb; };
+    auto load_client = [&](int c, Ld& l) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(cp[c]) + (e0 >> 1);
+        l.sb = ld1(reinterpret_cast<const uint8_t*>(bsp[c]) + e0 / kMxBlock);
+        if constexpr (VEC) {
+            const V16 v = ld_nt(p);
+#pragma unroll
+            for (int w = 0; w < NW; ++w) l.q[w] = v.w[w];
+        } else {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                uint32_t q = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (e0 + 8 * w + 2 * j < numel) q |= static_cast<uint32_t>(ld1(p + 4 * w + j)) << (8 * j);
+                l.q[w] = q;
+            }
+        }
+    };
+    auto combine = [&](int c, const Ld& l) {
+        const float r = r32[c];
+        const float sf = e8m0_to_f32(l.sb);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            float x[8];
+            mxfp4_val8(l.q[w], sf, x);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                float v = x[k];
+                if constexpr (SCALED) v = F::tmp(v, s32[c], 0.0);
+                acc[8 * w + k] = F::add(acc[8 * w + k], F::tmp(v, r, 0.0));
+            }
+        }
+    };
+    int i = 0;
+    for (; i + CU <= n; i += CU) {
+        Ld l[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) load_client(i + u, l[u]);
+#pragma unroll
+        for (int u = 0; u < CU; ++u) combine(i + u, l[u]);
+    }
+    for (; i < n; ++i) {
+        Ld l;
+        load_client(i, l);
+        combine(i, l);
+    }
+}
+
+template <int CU, bool SCALED>
+__global__ __launch_bounds__(kBlock) void agg_reduce_mxfp4_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                  const uint64_t* __restrict__ clients,
+                                                                  const uint64_t* __restrict__ block_scales, int n_clients,
+                                                                  const float* __restrict__ r32,
+                                                                  const float* __restrict__ s32, unsigned flags,
+                                                                  int64_t n_chunks) {
+    constexpr int EPT = kMx4EPT;            // 32 nibbles = 16 client bytes = 8 fp32 vectors of 4
+    static_assert(EPT == kMxBlock && kBlock * EPT / 2 == FLAME_TILE_BYTES,
+                  "a lane owns one block; a chunk is one tile of client bytes");
+    const int64_t chunk = wg_slot(flags & FLAME_AGG_XCD_MAP);
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, EPT> lc(segs, n_segs, chunk);
+    if (!lc.live()) return;
+    const flame_segment sg = lc.sg;
+    const int64_t e0 = lc.e0;
+    const uint64_t* cp = lc.row(clients, n_clients);
+    const uint64_t* bsp = lc.row(block_scales, n_clients);
+    const float* bp = reinterpret_cast<const float*>(sg.in) + e0;
+    float* op = reinterpret_cast<float*>(sg.out) + e0;
+    float acc[EPT];
+    if (lc.vec()) {
+        lane_load<true>(bp, acc, e0, sg.numel);
+        reduce_clients_mxfp4<CU, true, SCALED>(acc, cp, bsp, n_clients, r32, s32, e0, sg.numel);
+        lane_store<true>(op, acc, e0, sg.numel);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) acc[j] = (e0 + j < sg.numel) ? ld1(bp + j) : 0.f;
+    reduce_clients_mxfp4<1, false, SCALED>(acc, cp, bsp, n_clients, r32, s32, e0, sg.numel);
+#pragma unroll
+    for (int j = 0; j < EPT; ++j)
+        if (e0 + j < sg.numel) st1(op + j, acc[j]);
+}
+
 // ---------------------------------------------------------------- trimmed mean / median
 // Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
 // the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
@@ -3935,6 +4075,7 @@ int64_t flame_chunk_elems(int dtype) {
     dispatch<FLAME_F32, FLAME_BF16, FLAME_F16, FLAME_F64, FLAME_I64, FLAME_I32>(
         dtype, [&](auto dt) { n = chunk_elems<decltype(dt)::value>(); });
     if (dtype == FLAME_FP8_E4M3 || dtype == FLAME_FP8_E5M2) n = static_cast<int64_t>(kBlock) * kMxEPT;   // flame_agg_reduce_mx only
+    if (dtype == FLAME_FP4_E2M1) n = static_cast<int64_t>(kBlock) * kMx4EPT;                              // flame_agg_reduce_mxfp4 only
     return n;
 }
 
@@ -4070,6 +4211,40 @@ int flame_agg_reduce_mx(int client_dtype, int agg_dtype, unsigned flags, const f
             hipLaunchKernelGGL((agg_reduce_mx_kernel<CD, kClientUnrollMx, false>), grid, block, 0, st, segs, n_segs, cl, bs,
                                n_clients, rates32, scales32, flags, n_chunks);
     });
+    return check_launch(who);
+}
+
+// MXFP4 updates into an fp32 aggregate: flame_agg_reduce_mx's arguments, its own entry point (that one
+// keeps refusing every code but its two).  One instantiation per SCALED; every refusal comes before
+// the first HIP call.  The segment table lives in device memory, so client_tile_stride cannot be
+// looked at here: the kernel does not read the field (engine.py never builds a tiled MX row).
+int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs,
+                           int64_t n_chunks, const void* const* clients, const void* const* block_scales,
+                           int32_t n_clients, const float* rates32, const float* scales32, void* stream) {
+    const char* const who = "flame_agg_reduce_mxfp4";
+    if (client_dtype != FLAME_FP4_E2M1 || agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: client dtype %d into aggregate dtype %d is not supported (fp4 e2m1 into f32 only)",
+                       who, client_dtype, agg_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (int rc = need_clients(who, clients)) return rc;
+    if (!block_scales) return set_err(FLAME_EINVAL, "%s: block scale pointer table is NULL", who);
+    if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if (flags & FLAME_AGG_INIT_FIRST)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (an MX update has no aggregate dtype of its own)", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
+    if (int rc = check_flags(who, flags, FLAME_AGG_XCD_MAP)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t* cl = reinterpret_cast<const uint64_t*>(clients);
+    const uint64_t* bs = reinterpret_cast<const uint64_t*>(block_scales);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    if (scales32)
+        hipLaunchKernelGGL((agg_reduce_mxfp4_kernel<kClientUnrollMx4, true>), grid, block, 0, st, segs, n_segs, cl, bs,
+                           n_clients, rates32, scales32, flags, n_chunks);
+    else
+        hipLaunchKernelGGL((agg_reduce_mxfp4_kernel<kClientUnrollMx4, false>), grid, block, 0, st, segs, n_segs, cl, bs,
+                           n_clients, rates32, scales32, flags, n_chunks);
     return check_launch(who);
 }
 

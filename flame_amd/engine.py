@@ -49,14 +49,23 @@ ITEMSIZE = {N.FLAME_F32: 4, N.FLAME_BF16: 2, N.FLAME_F16: 2, N.FLAME_F64: 8, N.F
 # 16-bit deltas into the server's fp32 model.  Every other pair of differing dtypes stays on
 # _accumulate_mixed / _accumulate_promoted.
 UPLINK16 = (torch.bfloat16, torch.float16)
-# element dtypes of an MX update (flame_amd.mx.MXWeights: float8 elements, one E8M0 scale byte per
-# MX_BLOCK elements), which one flame_agg_reduce_mx launch per format sums into an fp32 aggregate.
-# They are NOT in DTYPE_CODE: no other kernel, slab or cache takes them (:func:`mx_route`).
-MX_CODE = {torch.float8_e4m3fn: N.FLAME_FP8_E4M3, torch.float8_e5m2: N.FLAME_FP8_E5M2}
+# element dtypes of an MX update (flame_amd.mx.MXWeights: float8 elements or packed float4 ones, one
+# E8M0 scale byte per MX_BLOCK elements), which one flame_agg_reduce_mx / flame_agg_reduce_mxfp4 launch
+# per format sums into an fp32 aggregate.  They are NOT in DTYPE_CODE (nor is the packed one in
+# ITEMSIZE: half a byte): no other kernel, slab or cache takes them (:func:`mx_route`).
+MX_PACKED = torch.float4_e2m1fn_x2      # two e2m1 elements per byte: a 1-D tensor of ceil(numel / 2) bytes
+MX_CODE = {torch.float8_e4m3fn: N.FLAME_FP8_E4M3, torch.float8_e5m2: N.FLAME_FP8_E5M2, MX_PACKED: N.FLAME_FP4_E2M1}
 MX_BLOCK = 32
 MX_SUPPORTED = ("MX updates are supported as flame_amd.mx.MXWeights whose every entry holds the key in ONE float8 "
-                "format (float8_e4m3fn or float8_e5m2) with a 1-D uint8 scale tensor of ceil(numel / 32) bytes, summed "
+                "format (float8_e4m3fn or float8_e5m2), or packed as a 1-D float4_e2m1fn_x2 tensor of ceil(numel / 2) "
+                "bytes with the aggregate's shape in MXWeights.shapes, with a 1-D uint8 scale tensor of ceil(numel / 32) "
+                "bytes, summed "
                 "into an fp32 aggregate by engine.accumulate / reduce_ (FedAvg, FedProx, FedGFT and the FedOPT family)")
+
+
+def mx_row_len(dt, numel: int) -> int:
+    """Elements of dtype ``dt`` an MX client tensor holds for ``numel`` logical elements (bytes, both ways)."""
+    return -(-numel // 2) if dt == MX_PACKED else numel
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -469,11 +478,13 @@ def refuse_mx(ws, who: str) -> None:
             raise TypeError(f"flame_amd: {who} does not take MX updates (a follow-up, not a silent slow path).  {MX_SUPPORTED}")
 
 
-def mx_route(agg_dtype, ws, k):
-    """The float8 dtype of key ``k`` when the updates ``ws`` (all carrying ``k``) take ONE
-    flame_agg_reduce_mx launch: every one an MXWeights holding ``k`` in the same float8 format with a
-    1-D uint8 scale tensor of ceil(numel / 32) bytes, under an fp32 aggregate.  None when no update
-    holds ``k`` as float8 (its present route); every case in between is a TypeError."""
+def mx_route(agg_dtype, ws, k, agg_shape=None):
+    """The MX element dtype of key ``k`` when the updates ``ws`` (all carrying ``k``) take ONE
+    flame_agg_reduce_mx / flame_agg_reduce_mxfp4 launch: every one an MXWeights holding ``k`` in the
+    same element format with a 1-D uint8 scale tensor of ceil(numel / 32) bytes, under an fp32
+    aggregate; a packed e2m1 key 1-D, of ceil(numel / 2) bytes, with its logical shape (``agg_shape``
+    where the caller has it) in ``shapes``.  None when no update holds ``k`` as MX elements (its present
+    route); every case in between is a TypeError."""
     dts = [weight_dtype(w, k) for w in ws]
     if not any(dt in MX_CODE for dt in dts):
         return None
@@ -491,8 +502,23 @@ def mx_route(agg_dtype, ws, k):
         if not isinstance(w, mx.MXWeights):
             raise TypeError(f"flame_amd: key {k!r} is a {first} tensor in a plain {type(w).__name__}: a float8 tensor "
                             f"means nothing without its block scales.  {MX_SUPPORTED}")
+        numel = w[k].numel()
+        if first == MX_PACKED:
+            shape = getattr(w, "shapes", {}).get(k)
+            if shape is None:
+                raise TypeError(f"flame_amd: key {k!r} is a {first} tensor without an MXWeights.shapes entry: two elements "
+                                f"share a byte, so the packed tensor does not say how many it holds.  {MX_SUPPORTED}")
+            numel = math.prod(shape)
+            if w[k].dim() != 1:
+                raise TypeError(f"flame_amd: key {k!r} is a {first} tensor of shape {tuple(w[k].shape)}, not 1-D.  {MX_SUPPORTED}")
+            if w[k].numel() != -(-numel // 2):
+                raise TypeError(f"flame_amd: key {k!r} is a {first} tensor of {w[k].numel()} bytes, not the {-(-numel // 2)} "
+                                f"of its logical shape {tuple(shape)}.  {MX_SUPPORTED}")
+            if agg_shape is not None and tuple(shape) != tuple(agg_shape):
+                raise TypeError(f"flame_amd: key {k!r}: the MX update's logical shape {tuple(shape)} is not the aggregate's "
+                                f"{tuple(agg_shape)}.  {MX_SUPPORTED}")
         s = w.scales.get(k)
-        want = -(-w[k].numel() // MX_BLOCK)
+        want = -(-numel // MX_BLOCK)
         if not isinstance(s, torch.Tensor):
             raise TypeError(f"flame_amd: key {k!r} is a {first} tensor without scales.  {MX_SUPPORTED}")
         if s.dtype != torch.uint8 or s.dim() != 1 or s.numel() != want:
@@ -516,7 +542,8 @@ def _client_row(cs, o: torch.Tensor, device, keep, cdt=None):
     them tiled; otherwise every client is read contiguous (tiled views that are
     mixed with other layouts in one call are copied out -- rare).  ``cdt``: the clients' dtype
     where it is not the aggregate's (:func:`uplink16_dtype`); the tile-stride test is in it.  MX
-    element tensors (``cdt`` a float8 dtype) are never tiled: every row is contiguous."""
+    element tensors (``cdt`` a float8 dtype, or the packed float4 one: ceil(numel / 2) bytes) are never
+    tiled: every row is contiguous."""
     n = o.numel()
     dt = cdt or o.dtype
     for c in cs:
@@ -525,9 +552,10 @@ def _client_row(cs, o: torch.Tensor, device, keep, cdt=None):
                 f"flame_amd: client tensor dtype {c.dtype} differs from aggregate dtype {dt}")
     if dt in MX_CODE:
         for c in cs:
-            if c.numel() != n:
+            if c.numel() != mx_row_len(dt, n):
                 raise RuntimeError(f"flame_amd: client tensor has {c.numel()} elements, aggregate {n}")
-        return [_row_pointer(c, device, keep) for c in cs], 0
+        # (a packed row is staged as its bytes: torch implements few operations on the float4 shell dtype)
+        return [_row_pointer(c.view(torch.uint8) if dt == MX_PACKED else c, device, keep) for c in cs], 0
     if cs and cs[0].device == device:
         ts0 = tiled_stride(cs[0], n)
         if ts0:
@@ -590,9 +618,9 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
     first multiplied by its clip scale, ``round(round(v * scale) * rate)`` (kernel:
     flame_agg_reduce_scaled).
     ``block_scales[s]`` (or None per segment): segment ``s``'s clients are MX element tensors
-    (float8, :data:`MX_CODE`) and these are their uint8 E8M0 scale tensors, one per client; such
-    segments under an fp32 output take one flame_agg_reduce_mx launch per element format, the clip
-    ``scales`` inside it.
+    (float8 or packed float4, :data:`MX_CODE`) and these are their uint8 E8M0 scale tensors, one per
+    client; such segments under an fp32 output take one flame_agg_reduce_mx (float4:
+    flame_agg_reduce_mxfp4) launch per element format, the clip ``scales`` inside it.
     """
     if not outs:
         return
@@ -609,6 +637,7 @@ def reduce_(outs: List[torch.Tensor], ins: Optional[List[torch.Tensor]], clients
             cdts[s] = cs[0].dtype if cs else None
             if (cdts[s] not in MX_CODE or o.dtype != torch.float32 or len(mxs) != len(cs)
                     or any(c.dtype != cdts[s] for c in cs)
+                    or (cdts[s] == MX_PACKED and any(c.dim() != 1 or c.numel() != -(-o.numel() // 2) for c in cs))
                     or any(m.dtype != torch.uint8 or m.dim() != 1 or m.numel() != -(-o.numel() // MX_BLOCK) for m in mxs)):
                 raise TypeError(f"flame_amd.reduce_: segment {s} is not an MX segment.  {MX_SUPPORTED}")
     ccode_of = lambda dt: MX_CODE[dt] if dt in MX_CODE else dtype_code(dt)     # noqa: E731
@@ -646,10 +675,18 @@ def _launch_reduce(code, segs, rates, device, keep, *, init_first=False, seg_rat
                                       "(a None-start aggregate has the update's dtype) nor seg_rates")
         n_cl = _n_clients(rates, False)
         if ccode in MX_CODE.values():
-            # per element: n 1-byte reads, one fp32 read, one fp32 write; per block and client one scale byte
-            nbytes = sum(s.numel * (n_cl + 2 * ITEMSIZE[code]) + n_cl * -(-s.numel // MX_BLOCK) for s in segs)
             p = plan(ccode, segs, rates, scales=scales)
             flags = N.FLAME_AGG_XCD_MAP if p.n_chunks >= XCD_MAP_MIN_CHUNKS else 0
+            if ccode == N.FLAME_FP4_E2M1:
+                # per client ceil(numel / 2) bytes; per element one fp32 read and write; per block and client one scale byte
+                nbytes = sum(n_cl * -(-s.numel // 2) + 2 * ITEMSIZE[code] * s.numel + n_cl * -(-s.numel // MX_BLOCK) for s in segs)
+                _launch("flame_agg_reduce_mxfp4", nbytes, device, keep, p.meta,
+                        lambda b: L.flame_agg_reduce_mxfp4(ccode, code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients,
+                                                           b + p.off_bscales, p.n_clients, b + p.off_r32,
+                                                           b + p.off_s32 if scales is not None else None, _stream_ptr(device)))
+                return
+            # per element: n 1-byte reads, one fp32 read, one fp32 write; per block and client one scale byte
+            nbytes = sum(s.numel * (n_cl + 2 * ITEMSIZE[code]) + n_cl * -(-s.numel // MX_BLOCK) for s in segs)
             _launch("flame_agg_reduce_mx", nbytes, device, keep, p.meta,
                     lambda b: L.flame_agg_reduce_mx(ccode, code, flags, b, p.n_segs, p.n_chunks, b + p.off_clients,
                                                     b + p.off_bscales, p.n_clients, b + p.off_r32,
@@ -1329,7 +1366,7 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     for cis, ks in groups.items():
         # MX keys: float8 elements + block scales of MXWeights under an fp32 aggregate (reduce_ groups
         # those into one flame_agg_reduce_mx per element format)
-        mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k) is not None}
+        mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape) is not None}
         # same: one reduction launch per dtype pair -- the aggregate's own dtype, or bf16 / f16
         # updates under an fp32 aggregate (reduce_ groups those into flame_agg_reduce_mixed)
         same = [k for k in ks if k in mxk or (agg[k].dtype in DTYPE_CODE
@@ -1914,7 +1951,7 @@ def tmp_of(v: torch.Tensor, rate: float, device, shape=None) -> torch.Tensor:
 
 def _check_cast(acc_dt, v_dt) -> None:
     if v_dt in MX_CODE or acc_dt in MX_CODE:
-        raise TypeError(f"flame_amd: a {v_dt if v_dt in MX_CODE else acc_dt} tensor outside an MX update: a float8 tensor "
+        raise TypeError(f"flame_amd: a {v_dt if v_dt in MX_CODE else acc_dt} tensor outside an MX update: a float8 / float4 tensor "
                         f"means nothing without its block scales.  {MX_SUPPORTED}")
     p = torch.promote_types(acc_dt, v_dt)
     if not torch.can_cast(p, acc_dt):

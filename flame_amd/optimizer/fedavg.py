@@ -103,7 +103,7 @@ class DeferredWeights(collections.abc.Mapping):
                 raise KeyError(k)
             acc, dt = self._base[k].dtype, engine.weight_dtype(w, k)
             if dt in engine.MX_CODE:
-                engine.mx_route(acc, [w], k)        # an MX arrival: what the flush would refuse of it, now
+                engine.mx_route(acc, [w], k, self._base[k].shape)        # an MX arrival: what the flush would refuse of it, now
             elif dt != acc:
                 engine._check_cast(acc, dt)
 

@@ -223,7 +223,7 @@ class FedOPT(FedAvg):
                 engine.refuse_mx([w for w, _ in entries], "the sharded wrapper (key_groups)")
             for k in keys:
                 ws = [w for w, _ in entries if k in w]
-                if ws and engine.mx_route(base_weights[k].dtype, ws, k) is not None and len(ws) == len(entries):
+                if ws and engine.mx_route(base_weights[k].dtype, ws, k, base_weights[k].shape) is not None and len(ws) == len(entries):
                     mx_keys.add(k)
         fused, generic = [], []
         float_dts = (torch.float32, torch.bfloat16, torch.float16, torch.float64)

@@ -40,6 +40,8 @@
  *   flame_agg_reduce_mx         (no reference counterpart: MXFP8 updates -- OCP e4m3fn / e5m2 elements, one
  *                               E8M0 scale per 32 -- into an fp32 model; the same statements over the
  *                               dequantized update)
+ *   flame_agg_reduce_mxfp4      (no reference counterpart: MXFP4 updates -- OCP e2m1 elements, two per byte,
+ *                               one E8M0 scale per 32 -- into an fp32 model; the same statements again)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -92,6 +94,8 @@ extern "C" {
  * entry point refuses them as it refuses an unknown code */
 #define FLAME_FP8_E4M3 10 /* OCP e4m3fn: torch.float8_e4m3fn */
 #define FLAME_FP8_E5M2 11 /* OCP e5m2:   torch.float8_e5m2 */
+/* the MXFP4 client element, two per byte, taken by flame_agg_reduce_mxfp4 alone */
+#define FLAME_FP4_E2M1 12 /* OCP e2m1:   torch.float4_e2m1fn_x2 (one byte = two elements) */
 
 /* flame_agg_reduce flags */
 #define FLAME_AGG_INIT_FIRST 1u  /* no base: acc = tmp(client 0) (fedbuff.py:139-140,154-155) */
@@ -356,6 +360,54 @@ int flame_agg_reduce_mx(int client_dtype, int agg_dtype, unsigned flags, const f
                         int32_t n_segs, int64_t n_chunks, const void *const *clients,
                         const void *const *block_scales, int32_t n_clients, const float *rates32,
                         const float *scales32, void *stream);
+
+/*
+ * MXFP4 updates into an fp32 aggregate in one launch (OCP Microscaling v1.0; the contract is this
+ * project's own).  An update holds, per tensor, one 4-bit OCP e2m1 code per element and
+ * one E8M0 scale byte per block of 32 flat C-order elements (16 bytes; the last block may be partial),
+ * as flame_amd.mx.quantize(fmt="e2m1") writes them.
+ *   Elements: 1 sign bit, 2 exponent bits, 1 mantissa bit.  Codes 0 .. 7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6;
+ *             codes 8 .. 15 their negatives (code 8 is -0).  No inf, no NaN.
+ *   Packing : two elements per byte: flat element 2i is the LOW nibble of byte i, element 2i + 1 the
+ *             HIGH nibble (torch.float4_e2m1fn_x2's and the hardware's order).  A client pointer
+ *             addresses ceil(numel / 2) bytes; with odd numel the last high nibble is padding, which
+ *             the kernel never reads a meaning from (nothing after byte ceil(numel / 2) - 1 is read).
+ * The arguments are flame_agg_reduce_mx's.
+ *   client_dtype : FLAME_FP4_E2M1: every client tensor of every segment.
+ *   agg_dtype    : FLAME_F32: every segment's in / out.
+ *   segs         : chunk_begin counts chunks of flame_chunk_elems(FLAME_FP4_E2M1) = 8,192 elements (one
+ *                  4,096-byte tile of client bytes: a lane owns 32 elements, one whole scale block).
+ *                  client_tile_stride must be 0: a tiled MXFP4 row is refused where rows are built
+ *                  (flame_amd/engine.py; the table is device memory, this entry point cannot look), and
+ *                  the kernel does not read the field.  FLAME_SEG_UNALIGNED speaks of in, out and the
+ *                  client byte pointers.
+ *   clients      : device array [n_segs][n_clients] of pointers to the packed element bytes, of any
+ *                  alignment under FLAME_SEG_UNALIGNED.
+ *   block_scales : device array [n_segs][n_clients] of pointers to the scale bytes,
+ *                  ceil(numel / 32) each, of ANY alignment (FLAME_SEG_UNALIGNED does not speak of them).
+ *   rates32      : device [n_clients]; scales32: device [n_clients] clip scales, or NULL for the plain round.
+ * Per element e, clients in order, no FMA, denormals kept:
+ *   acc = in[e]                                                  (fp32)
+ *   b   = q_i[e >> 1];  c = (e & 1) ? b >> 4 : b & 15
+ *   x   = f32_e2m1(c) * f32_e8m0(s_i[e / 32])                    one IEEE fp32 multiply;
+ *         f32_e8m0(b) = 2^(b - 127) (b = 0: the fp32 subnormal 2^-127); scale byte 255 gives NaN
+ *         for every element of its block (the one way an MXFP4 update carries a NaN)
+ *         with scales32: x = round_f32(x * scale_i)
+ *   t   = round_f32(x * rate_i)
+ *   acc = round_f32(acc + t)
+ *   out[e] = acc
+ * x is flame_amd.mx.dequantize's value of the element, so the result is bit for bit what
+ * flame_agg_reduce (with scales32: flame_agg_reduce_scaled) gives for FLAME_F32 over the
+ * dequantized update.  Refusals, each before any HIP call and named in flame_last_error: a pair other
+ * than (e2m1, f32) is FLAME_ENOTSUP (the message names both dtypes); FLAME_AGG_INIT_FIRST is
+ * FLAME_ENOTSUP; FLAME_AGG_SEG_RATES is FLAME_ENOTSUP; any flag beyond FLAME_AGG_XCD_MAP, a NULL
+ * table or rate array, n_segs <= 0, n_clients < 1 or n_chunks outside [1, 2^31) is FLAME_EINVAL.
+ * Device tables only (no kernel-argument variant).  Not a launch branch of flame_launch_branches().
+ */
+int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, const flame_segment *segs,
+                           int32_t n_segs, int64_t n_chunks, const void *const *clients,
+                           const void *const *block_scales, int32_t n_clients, const float *rates32,
+                           const float *scales32, void *stream);
 
 /*
  * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,

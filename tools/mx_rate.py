@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
-"""What an MXFP8 uplink into an fp32 model costs, in ONE process (the shapes one after the other): after
+"""What an MXFP8 or MXFP4 uplink into an fp32 model costs, in ONE process (the shapes one after the other): after
 the bench's HBM settling, round by round and in alternating order, HIP-event times of one engine.accumulate over
 
   F32    fp32 updates                       -> flame_agg_reduce
   BF16   bf16 updates                       -> flame_agg_reduce_mixed
   E4M3   MXFP8 e4m3 updates (mx.quantize)   -> flame_agg_reduce_mx
   E5M2   MXFP8 e5m2 updates                 -> flame_agg_reduce_mx
+  E2M1   MXFP4 e2m1 updates, two per byte   -> flame_agg_reduce_mxfp4
 
 each as separate per-client tensors, once device-resident (``dev``) and once in pinned host memory
 (``host``: the kernel reads the updates over the link, zero-copy -- the whole round from host memory).
 Every arm is one kernel (engine.kernel_events).  Medians over the rounds, the bytes each arm moves
-(fp32: P (4n + 8); bf16: P (2n + 8); MX: P (n + 8) + n ceil(P / 32)), GB/s, and for every arm its time
+(fp32: P (4n + 8); bf16: P (2n + 8); MXFP8: P (n + 8) + n ceil(P / 32); MXFP4: n ceil(P / 2) + 8 P +
+n ceil(P / 32)), GB/s, and for every arm its time
 and its bytes relative to the fp32 arm of the same residency: ``x bytes`` is how far the arm is from
 its byte ratio (1.0 = exactly as many times faster as it moves fewer bytes).
 
@@ -30,7 +32,7 @@ sys.path.insert(0, ROOT)
 
 SHAPES = ("64x25000000", "1024x2000000")
 ARMS = (("F32", "flame_agg_reduce"), ("BF16", "flame_agg_reduce_mixed"), ("E4M3", "flame_agg_reduce_mx"),
-        ("E5M2", "flame_agg_reduce_mx"))
+        ("E5M2", "flame_agg_reduce_mx"), ("E2M1", "flame_agg_reduce_mxfp4"))
 
 
 def _bytes(arm, n, P):
@@ -38,6 +40,8 @@ def _bytes(arm, n, P):
         return P * (4 * n + 8)
     if arm == "BF16":
         return P * (2 * n + 8)
+    if arm == "E2M1":
+        return n * -(-P // 2) + 8 * P + n * -(-P // 32)
     return P * (n + 8) + n * -(-P // 32)
 
 
@@ -51,12 +55,16 @@ def _updates(engine, mx, n, P, dev, host):
         ups["BF16"].append({"model": fill.to(torch.bfloat16)})
         ups["E4M3"].append(mx.quantize({"model": fill}, "e4m3"))
         ups["E5M2"].append(mx.quantize({"model": fill}, "e5m2"))
+        ups["E2M1"].append(mx.quantize({"model": fill}, "e2m1"))
     torch.cuda.synchronize()
     pinned = None
     if host:
         def pin(t):
+            if t.dtype == mx.PACKED:        # (a packed key is copied as its bytes)
+                return pin(t.view(torch.uint8)).view(mx.PACKED)
             return torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t)
-        pinned = {arm: [mx.MXWeights({"model": pin(u["model"])}, {"model": pin(u.scales["model"])}) if arm[0] == "E"
+        pinned = {arm: [mx.MXWeights({"model": pin(u["model"])}, {"model": pin(u.scales["model"])}, shapes=u.shapes)
+                        if arm[0] == "E"
                         else {"model": pin(u["model"])} for u in us] for arm, us in ups.items()}
         torch.cuda.synchronize()
     return ups, pinned
