@@ -4600,7 +4600,12 @@ int flame_feddyn_round(int dtype, const flame_dyn_segment* segs, int32_t n_segs,
 int flame_host_register(void* host, uint64_t nbytes) {
     if (!host || nbytes == 0) return set_err(FLAME_EINVAL, "flame_host_register: empty range");
     hipError_t e = hipHostRegister(host, static_cast<size_t>(nbytes), hipHostRegisterMapped | hipHostRegisterPortable);
-    if (e != hipSuccess) return set_err(FLAME_EHIP, "hipHostRegister: %s", hipGetErrorString(e));
+    if (e != hipSuccess) {
+        // the runtime also keeps the failure as its last error, where the next launch's check (ours or
+        // torch's) would find it and blame that launch: it is reported here, so take it back
+        (void)hipGetLastError();
+        return set_err(FLAME_EHIP, "hipHostRegister: %s", hipGetErrorString(e));
+    }
     return FLAME_OK;
 }
 

@@ -244,7 +244,7 @@ class ShardedEgress:
 
     Each rank D2Hs only ITS ranges of the model -- the plan's owned pieces of every key; rank 0 also
     the replicated key tails and the pickle's own bytes -- over its own PCIe link, straight into a
-    POSIX shared-memory segment that every rank has mapped and page-locked; after a barrier rank 0
+    POSIX shared-memory segment that every rank has mapped and (where the machine can) page-locked; after a barrier rank 0
     holds the complete payload (``encode`` returns it there, ``None`` elsewhere), byte-for-byte what
     :class:`MessageEncoder` builds.  With ``ShardedOptimizer(gather=False)`` the model never crosses
     xGMI: at N GPUs the egress is N links' D2H of 1/N of the model each instead of one link's D2H of
@@ -279,7 +279,7 @@ class ShardedEgress:
             return
         self.close()
         from multiprocessing import shared_memory
-        from .ingest import RegisteredBuffer
+        from .ingest import RegisteredBuffer, host_register_supported
         size = -(-max(total, 1) // (1 << 20)) * (1 << 20)
         nm = f"{self.name}-{size}"
         seg = None
@@ -299,7 +299,9 @@ class ShardedEgress:
                 resource_tracker.unregister(seg._name, "shared_memory")  # noqa: SLF001
             except Exception:  # noqa: BLE001
                 pass
-        self._reg = RegisteredBuffer(seg.buf) if torch.cuda.is_available() else None
+        # (where the machine cannot page-lock the segment, the D2H copies into it are pageable ones:
+        # encode() waits for each source's stream before its barrier either way)
+        self._reg = RegisteredBuffer(seg.buf) if torch.cuda.is_available() and host_register_supported() else None
         self._seg, self._size = seg, size
 
     def encode(self, message: Any):

@@ -607,10 +607,33 @@ def loads(payload):
 
 
 # ------------------------------------------------------------------ registered receive buffers
+_host_register = None
+
+
+def host_register_supported() -> bool:
+    """Can this machine page-lock host memory the program already has (``flame_host_register``)?
+    Some virtual machines page-lock only what the runtime allocates itself (``pin_memory=True``).
+    Asked of the runtime once, with one page."""
+    global _host_register
+    if _host_register is None:
+        import mmap
+        import numpy as np
+        from . import _native as N
+        page = mmap.mmap(-1, mmap.PAGESIZE)
+        arr = np.frombuffer(page, dtype=np.uint8)
+        _host_register = N.lib().flame_host_register(arr.ctypes.data, arr.nbytes) == N.FLAME_OK
+        if _host_register:
+            N.check(N.lib().flame_host_unregister(arr.ctypes.data))
+        del arr
+        page.close()
+    return _host_register
+
+
 class RegisteredBuffer:
     """Page-lock + map a host buffer (bytearray, mmap, numpy array, shm segment) so the
     reduction kernel can read tensors decoded from it zero-copy over PCIe
-    (``flame_host_register``).  Use as a context manager or call ``close()``."""
+    (``flame_host_register``).  Use as a context manager or call ``close()``.  Raises where
+    :func:`host_register_supported` is False."""
 
     def __init__(self, buf):
         import numpy as np
@@ -653,6 +676,13 @@ class ShmReceiver:
     views into the shared segment that the reduction kernel streams over PCIe, or that
     :class:`DeviceUpdateCache` copies to HBM, without any host copy.
 
+    On a machine that cannot page-lock another process's pages
+    (:func:`host_register_supported` is False) ``register=True`` keeps one pinned buffer
+    per sender instead: :meth:`get_data` copies the message into it (the reference's one
+    host copy, ``bytes(read_buf.buf[:msg_size])``) and returns a memoryview of that, so
+    the decoded tensors are pinned all the same and every consumer goes on as above; the
+    sender's next message overwrites the buffer as it would the segment.
+
     Lifetime (``flame_amd.shm_lease``): the sender rewrites its segment for its next
     message (``backend/shm.py:393-403``), and nothing tells the receiver when.  So no
     consumer keeps a view past the call it was handed to: a kernel streaming the views
@@ -667,7 +697,7 @@ class ShmReceiver:
         self.self_id = self_id
         self.register = register
         self.untrack = untrack     # the writer owns (and unlinks) its segment
-        self._segs = {}   # name -> (SharedMemory, RegisteredBuffer | None)
+        self._segs = {}   # name -> (SharedMemory, RegisteredBuffer | None, pinned copy of the message | None)
 
     def _segment(self, other: str, msg_size: int):
         from multiprocessing import shared_memory
@@ -684,21 +714,29 @@ class ShmReceiver:
                     resource_tracker.unregister(shm._name, "shared_memory")  # noqa: SLF001
                 except Exception:  # noqa: BLE001
                     pass
-            reg = RegisteredBuffer(shm.buf) if self.register else None
-            seg = (shm, reg)
-            self._segs[name] = seg
             import numpy as np
             from . import shm_lease
-            shm_lease.add(name, np.frombuffer(shm.buf, dtype=np.uint8).ctypes.data, shm.size)
+            reg = pinned = None
+            if self.register and host_register_supported():
+                reg = RegisteredBuffer(shm.buf)
+            elif self.register:
+                pinned = torch.empty(shm.size, dtype=torch.uint8, pin_memory=True).numpy()
+            seg = (shm, reg, pinned)
+            self._segs[name] = seg
+            held = pinned if pinned is not None else np.frombuffer(shm.buf, dtype=np.uint8)
+            shm_lease.add(name, held.ctypes.data, shm.size)     # the range the decoded views lie in
         return seg
 
     def get_data(self, other: str, msg_size: int) -> memoryview:
         """The message bytes in place (the reference returns a copy).  Views of the sender's
         previous message become stale (``shm_lease.check_live`` raises on them)."""
         from . import shm_lease
-        shm, _ = self._segment(other, msg_size)
+        shm, _, pinned = self._segment(other, msg_size)
         shm_lease.next_generation(other + "-" + self.self_id)
-        return shm.buf[:msg_size]
+        if pinned is None:
+            return shm.buf[:msg_size]
+        pinned[:msg_size] = shm.buf[:msg_size]
+        return memoryview(pinned)[:msg_size]
 
     def loads(self, other: str, msg_size: int):
         """get_data + zero-copy decode (falls back to cloudpickle for non-update messages);
@@ -711,7 +749,7 @@ class ShmReceiver:
     def _close_one(self, name):
         from . import shm_lease
         shm_lease.remove(name)
-        shm, reg = self._segs.pop(name)
+        shm, reg, _ = self._segs.pop(name)
         if reg is not None:
             reg.close()
         del reg

@@ -756,6 +756,9 @@ int flame_hier_resident_per_cu(int dtype, unsigned flags, int32_t n_mids);
  *   flame_host_register:   page-lock + map an existing host range (e.g. a received
  *                          channel payload or the LIFL shared-memory segment,
  *                          lib/python/flame/backend/shm.py:386-403) for device access.
+ *                          FLAME_EHIP where the machine cannot (some virtual machines
+ *                          page-lock only memory the runtime allocates); the failure
+ *                          is not left behind for a later launch to report.
  *   flame_host_unregister: undo it.
  *   flame_host_device_pointer: device address of a pinned / registered host address
  *                          (hipHostMalloc'd memory maps to itself).

@@ -363,6 +363,7 @@ def test_optimizers_over_a_device_update_cache(case):
     for i, u in enumerate(ups):
         cache[f"e{i:02d}"] = S.TR({key: v.clone() for key, v in u.items()}, 3 + i)
     assert cache.slab is not None
+    torch.cuda.synchronize()       # the inserts run on the cache's side stream: snapshot what they wrote
     slab_before = {dt: st.clone() for dt, st in cache.slab.storage.items()}
     dev = S.to_dev(base, DEV)
     out = opt.do(dev, cache, total=sum(3 + i for i in range(n)))

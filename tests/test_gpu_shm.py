@@ -153,6 +153,39 @@ def test_stale_view_raises_instead_of_reading_torn_data():
         snd.close()
 
 
+def test_receiver_without_host_registration_hands_out_pinned_copies(monkeypatch):
+    """Where the machine cannot page-lock a sender's segment, a message is copied once into the
+    receiver's pinned buffer for that sender: the decoded tensors are pinned, hold the message's
+    bits, lie outside the segment, are leased like in-place views and go stale the same way."""
+    import numpy as np
+    from flame_amd import ingest, shm_lease
+    monkeypatch.setattr(ingest, "_host_register", False)
+    g = torch.Generator().manual_seed(73)
+    m1, m2 = ({"weights": {"w": torch.randn(4099, generator=g), "b": torch.randn(37, generator=g).bfloat16()},
+               "dataset_size": 10 + i} for i in range(2))
+    tag = f"flamecopy{os.getpid()}"
+    snd = _Sender(tag, len(cloudpickle.dumps(m1)) + 4096)
+    rx = ingest.ShmReceiver("agg", untrack=False)
+    try:
+        old = rx.loads(tag, snd.send(m1))
+        seg = np.frombuffer(snd.seg.buf, dtype=np.uint8)
+        lo = seg.ctypes.data
+        del seg
+        for k, v in m1["weights"].items():
+            t = old["weights"][k]
+            assert t.is_pinned() and shm_lease.aliases(t) and not lo <= t.data_ptr() < lo + snd.seg.size
+            assert torch.equal(t.view(torch.uint8), v.view(torch.uint8))
+            shm_lease.check_live(t)
+        new = rx.loads(tag, snd.send(m2))
+        with pytest.raises(RuntimeError, match="stale shared-memory view"):
+            shm_lease.check_live(old["weights"]["w"])
+        assert torch.equal(new["weights"]["w"], m2["weights"]["w"])
+        del old, new, t
+    finally:
+        rx.close()
+        snd.close()
+
+
 def _one(msg, version):
     c = S.SortedCache()
     c["t0"] = S.TR({k: v.clone() for k, v in msg["weights"].items()}, msg["dataset_size"], version)
