@@ -1117,6 +1117,247 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mxfp4_kernel(const flame_se
         if (e0 + j < sg.numel) st1(op + j, acc[j]);
 }
 
+// ---------------------------------------------------------------- MX downlink: the quantiser
+// flame_mx_quantize: fp32 / bf16 / f16 keys into OCP e4m3 / e5m2 bytes or packed e2m1 nibbles plus one
+// E8M0 scale byte per 32 elements, by flame_amd.mx.quantize's rule ("the MX quantiser"):
+//     amax = the block's largest finite |x|;  e = amax > 0 ? max(floor(log2 amax) - emax, -127) : 0
+//     y = x * 2^-e (ONE fp32 multiply, denormals kept), clamped to +-fmax, rounded to nearest even
+// A lane owns 8 consecutive elements (two 16-byte loads of fp32, one of a 16-bit source), so a block is
+// one quad and a workgroup covers 2,048 elements per pass; a chunk is kMxqPasses passes whose loads are
+// all issued before the first use.  The block maximum is taken on integer magnitudes (a non-finite one
+// counts as 0), lane-local and then by two quad_perm DPP steps: no LDS, no wave-wide shuffle.
+// floor(log2 amax) is the maximum's exponent field - 127; a subnormal maximum (field 0) clamps to -127
+// as the frexp route does, since emax >= 2.  e never exceeds 127 - emax, so 2^-e is a normal fp32.
+// e2m1 has no NaN: its block's scale byte is 255 when any element is one, an OR that takes two DPP steps
+// of its own (folded into the maximum's key it would displace the maximum, which the nibbles still need).
+// A lane's 8 fp8 bytes leave as one 8-byte store, its 8 nibbles as one dword; the quad leaders put the
+// chunk's 256 scale bytes into LDS and 16 lanes write them as 16-byte stores.  A chunk that is not whole
+// or whose segment is FLAME_SEG_UNALIGNED goes element by element with bounds, pass by pass, scale bytes
+// one by one (elements past numel count as zeros: the pad nibble of an odd e2m1 key is 0).
+// The products of a lane by one scale are what the backend pairs into packed fp32 multiplies; this code
+// is compared bit for bit and keeps to the scalar v_mul_f32 (FLAME_MXQ_FN on every function of it).
+#define FLAME_MXQ_FN __attribute__((target("no-packed-fp32-ops")))
+// element conversion per format, a bit mask (1: e4m3, 2: e5m2, 4: e2m1): the integer / comparison arm
+// that is correct by reading (bit clear), or v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 /
+// v_cvt_scalef32_pk_fp4_f32 after the explicit scale and clamp (bit set).  All three ship the hardware arm:
+// it passed tests/test_gpu_mx_quantize.py's rounding-boundary and shape tests on the MI355X in every format,
+// as the other arm did (0; the same bytes, for A/B builds), and was 0.03 ms faster at 25M parameters.
+#ifndef FLAME_T_MXQ_HWCVT
+#define FLAME_T_MXQ_HWCVT 7
+#endif
+// (the HIP header's __float_as_uint and its kin are plain inline functions, which do not inline into a
+// function of other target features and would stay calls: bit casts by the builtin)
+FLAME_MXQ_FN __device__ __forceinline__ uint32_t mxq_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+FLAME_MXQ_FN __device__ __forceinline__ float mxq_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
+constexpr int kMxqEPT = 8;           // source elements per lane and pass: a quad is one block
+constexpr int kMxqPasses = 4;        // passes per chunk
+constexpr int64_t kMxqChunk = static_cast<int64_t>(kBlock) * kMxqEPT * kMxqPasses;      // 8,192 source elements
+static_assert(4 * kMxqEPT == kMxBlock && kMxqChunk / kMxBlock == 16 * 16, "a quad is a block; 16 lanes store the scales");
+
+template <int FD> struct Mxq;
+template <> struct Mxq<FLAME_FP8_E4M3> {
+    static constexpr int EMAX = 8, MB = 3, BIAS = 7;
+    static constexpr uint32_t FMAX = 0x43E00000u;       // 448
+    static constexpr bool HW = (FLAME_T_MXQ_HWCVT & 1) != 0;
+};
+template <> struct Mxq<FLAME_FP8_E5M2> {
+    static constexpr int EMAX = 15, MB = 2, BIAS = 15;
+    static constexpr uint32_t FMAX = 0x47600000u;       // 57344
+    static constexpr bool HW = (FLAME_T_MXQ_HWCVT & 2) != 0;
+};
+template <> struct Mxq<FLAME_FP4_E2M1> {
+    static constexpr int EMAX = 2;
+    static constexpr bool HW = (FLAME_T_MXQ_HWCVT & 4) != 0;
+};
+
+// |y| saturated at fmax with y's sign, a NaN as it is (never a floating-point min: minNum drops a NaN)
+template <int FD> FLAME_MXQ_FN __device__ __forceinline__ float mxq_clamp(float y) {
+    const uint32_t u = mxq_bits(y), a = u & 0x7FFFFFFFu;
+    return (a > Mxq<FD>::FMAX && a <= 0x7F800000u) ? mxq_f32((u & 0x80000000u) | Mxq<FD>::FMAX) : y;
+}
+// One fp8 byte of the clamped y, round to nearest even in integer arithmetic.  A normal result: the
+// fp32 bits plus half an fp8 ulp less one plus the kept mantissa's lowest bit, rebased and shifted (a
+// carry runs into the exponent by itself).  Below the smallest normal 2^(1 - BIAS) the fp8 values are the
+// multiples of 2^(1 - BIAS - MB): adding 2^(24 - BIAS - MB), whose fp32 ulp is that step, rounds |y| to
+// one of them (one IEEE add), and the sum's low bits are the byte.
+template <int FD> FLAME_MXQ_FN __device__ __forceinline__ uint32_t mxq_fp8(float y) {
+    using F = Mxq<FD>;
+    constexpr int SH = 23 - F::MB;
+    constexpr uint32_t MIN_NORMAL = static_cast<uint32_t>(128 - F::BIAS) << 23;
+    constexpr uint32_t MAGIC = static_cast<uint32_t>(127 + 24 - F::BIAS - F::MB) << 23;
+    const uint32_t u = mxq_bits(y), sign = (u >> 24) & 0x80u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return sign | 0x7Fu;                       // a NaN in both formats
+    if (a >= MIN_NORMAL)
+        return sign | ((a + ((1u << (SH - 1)) - 1u) + ((a >> SH) & 1u) - (static_cast<uint32_t>(127 - F::BIAS) << 23)) >> SH);
+    return sign | (mxq_bits(mxq_f32(a) + mxq_f32(MAGIC)) - MAGIC);
+}
+// The eight elements of a lane, scaled, as fp8 bytes: q[0] holds elements 0..3 (lowest byte first)
+template <int FD> FLAME_MXQ_FN __device__ __forceinline__ void mxq_cvt8(const float (&y)[kMxqEPT], uint32_t (&q)[2]) {
+    if constexpr (FD == FLAME_FP4_E2M1) {
+        uint32_t w = 0;
+        if constexpr (Mxq<FD>::HW) {
+            float z[kMxqEPT];
+#pragma unroll
+            for (int j = 0; j < kMxqEPT; ++j) z[j] = (y[j] != y[j]) ? 0.f : y[j];       // a NaN is code 0
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, z[0], z[1], 1.0f, 0);
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, z[2], z[3], 1.0f, 1);
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, z[4], z[5], 1.0f, 2);
+            w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, z[6], z[7], 1.0f, 3);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kMxqEPT; ++j) {
+                // the seven midpoints, ties to the even mantissa bit; every comparison is false for a NaN
+                // (code 0, no sign) and anything past 5, inf included, is 6: the saturation
+                const float a = __builtin_fabsf(y[j]);
+                uint32_t c = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.0f);
+                if ((mxq_bits(y[j]) >> 31) && !(y[j] != y[j])) c |= 8u;          // the sign is kept, -0 included
+                w |= c << (4 * j);
+            }
+        }
+        q[0] = w;
+        q[1] = 0;
+    } else if constexpr (Mxq<FD>::HW) {
+        float z[kMxqEPT];
+#pragma unroll
+        for (int j = 0; j < kMxqEPT; ++j) z[j] = mxq_clamp<FD>(y[j]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int w = 0;
+            if constexpr (FD == FLAME_FP8_E4M3) {
+                w = __builtin_amdgcn_cvt_pk_fp8_f32(z[4 * h], z[4 * h + 1], w, false);
+                w = __builtin_amdgcn_cvt_pk_fp8_f32(z[4 * h + 2], z[4 * h + 3], w, true);
+            } else {
+                w = __builtin_amdgcn_cvt_pk_bf8_f32(z[4 * h], z[4 * h + 1], w, false);
+                w = __builtin_amdgcn_cvt_pk_bf8_f32(z[4 * h + 2], z[4 * h + 3], w, true);
+            }
+            q[h] = static_cast<uint32_t>(w);
+        }
+    } else {
+        q[0] = q[1] = 0;
+#pragma unroll
+        for (int j = 0; j < kMxqEPT; ++j) q[j >> 2] |= mxq_fp8<FD>(mxq_clamp<FD>(y[j])) << (8 * (j & 3));
+    }
+}
+// v of the quad's lane quad_perm CTRL names
+template <int CTRL> FLAME_MXQ_FN __device__ __forceinline__ uint32_t mxq_quad(uint32_t v) {
+    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
+}
+// A lane's eight source values to its block's scale byte (the same in the four lanes of the quad; every
+// lane of the wave must be here) and its own element bytes
+template <int FD> FLAME_MXQ_FN __device__ __forceinline__ uint32_t mxq_lane(const float (&x)[kMxqEPT], uint32_t (&q)[2]) {
+    uint32_t m = 0, nan = 0;
+#pragma unroll
+    for (int j = 0; j < kMxqEPT; ++j) {
+        const uint32_t a = mxq_bits(x[j]) & 0x7FFFFFFFu;
+        const uint32_t fin = a < 0x7F800000u ? a : 0u;
+        m = m > fin ? m : fin;
+        nan |= a > 0x7F800000u ? 1u : 0u;
+    }
+    // quad_perm [1,0,3,2] then [2,3,0,1]: every lane of the quad ends with the block's maximum
+    constexpr int SWAP1 = 0xB1, SWAP2 = 0x4E;
+    uint32_t o = mxq_quad<SWAP1>(m);
+    m = m > o ? m : o;
+    o = mxq_quad<SWAP2>(m);
+    m = m > o ? m : o;
+    if constexpr (FD == FLAME_FP4_E2M1) {
+        nan |= mxq_quad<SWAP1>(nan);
+        nan |= mxq_quad<SWAP2>(nan);
+    }
+    int e = static_cast<int>(m >> 23) - 127 - Mxq<FD>::EMAX;
+    e = m == 0u ? 0 : (e < -127 ? -127 : e);
+    const float inv = mxq_f32(static_cast<uint32_t>(127 - e) << 23);       // 2^-e: field 2 .. 254
+    float y[kMxqEPT];
+#pragma unroll
+    for (int j = 0; j < kMxqEPT; ++j) y[j] = x[j] * inv;        // one IEEE multiply (the build never contracts)
+    mxq_cvt8<FD>(y, q);
+    return (FD == FLAME_FP4_E2M1 && nan) ? 255u : static_cast<uint32_t>(e + 127);
+}
+template <int SD> FLAME_MXQ_FN __device__ __forceinline__ float mxq_widen(typename Tr<SD>::T v) {
+    if constexpr (SD == FLAME_F32) return v;
+    else if constexpr (SD == FLAME_BF16) return mxq_f32(static_cast<uint32_t>(v) << 16);
+    else {
+        _Float16 h;
+        __builtin_memcpy(&h, &v, 2);
+        return static_cast<float>(h);
+    }
+}
+
+// __syncthreads() by its builtins: the header's function does not inline into a function of other target features
+FLAME_MXQ_FN __device__ __forceinline__ void mxq_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int SD, int FD>
+__global__ __launch_bounds__(kBlock) FLAME_MXQ_FN void mx_quantize_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                        int64_t n_chunks) {
+    using T = typename Tr<SD>::T;
+    constexpr int EPT = kMxqEPT, P = kMxqPasses;
+    constexpr bool FP4 = FD == FLAME_FP4_E2M1;
+    constexpr int64_t PASS = static_cast<int64_t>(kBlock) * EPT;
+    __shared__ __attribute__((aligned(16))) uint8_t sbl[kMxqChunk / kMxBlock];
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, EPT * P> lc(segs, n_segs, chunk);       // its CE is the chunk; the lane layout is ours
+    const flame_segment sg = lc.sg;
+    const int t = static_cast<int>(threadIdx.x);
+    const int64_t cb = (chunk - sg.chunk_begin) * kMxqChunk;                // the chunk's first element
+    const T* src = reinterpret_cast<const T*>(sg.in);
+    uint8_t* out = reinterpret_cast<uint8_t*>(sg.out);
+    uint8_t* scales = reinterpret_cast<uint8_t*>(sg.cur_out);
+    if (cb + kMxqChunk <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
+        T x[P][EPT];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int64_t e = cb + p * PASS + static_cast<int64_t>(t) * EPT;
+            lane_load<true>(src + e, x[p], e, sg.numel);
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int64_t e = cb + p * PASS + static_cast<int64_t>(t) * EPT;
+            float f[EPT];
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) f[j] = mxq_widen<SD>(x[p][j]);
+            uint32_t q[2];
+            const uint32_t sb = mxq_lane<FD>(f, q);
+            if constexpr (FP4) {
+                *G(reinterpret_cast<uint32_t*>(out + (e >> 1))) = q[0];
+            } else {
+                using u2 = __attribute__((ext_vector_type(2))) uint32_t;
+                *G(reinterpret_cast<u2*>(out + e)) = u2{q[0], q[1]};
+            }
+            if ((t & 3) == 0) sbl[p * (kBlock / 4) + (t >> 2)] = static_cast<uint8_t>(sb);
+        }
+        mxq_barrier();
+        if (t < 16) {
+            V16 v;
+            __builtin_memcpy(v.w, sbl + 16 * t, 16);
+            st_plain(scales + cb / kMxBlock + 16 * t, v);
+        }
+        return;
+    }
+    for (int p = 0; p < P; ++p) {
+        if (cb + p * PASS >= sg.numel) break;                                // wave-uniform: every lane stays for the DPP steps
+        const int64_t e = cb + p * PASS + static_cast<int64_t>(t) * EPT;
+        float f[EPT];
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) f[j] = (e + j < sg.numel) ? mxq_widen<SD>(ld1(src + e + j)) : 0.f;
+        uint32_t q[2];
+        const uint32_t sb = mxq_lane<FD>(f, q);
+        if constexpr (FP4) {
+#pragma unroll
+            for (int j = 0; j < EPT / 2; ++j)
+                if (e + 2 * j < sg.numel) st1(out + (e >> 1) + j, static_cast<uint8_t>(q[0] >> (8 * j)));
+        } else {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                if (e + j < sg.numel) st1(out + e + j, static_cast<uint8_t>(q[j >> 2] >> (8 * (j & 3))));
+        }
+        if ((t & 3) == 0 && e < sg.numel) st1(scales + e / kMxBlock, static_cast<uint8_t>(sb));
+    }
+}
+
 // ---------------------------------------------------------------- trimmed mean / median
 // Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
 // the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
@@ -4245,6 +4486,31 @@ int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, cons
     else
         hipLaunchKernelGGL((agg_reduce_mxfp4_kernel<kClientUnrollMx4, false>), grid, block, 0, st, segs, n_segs, cl, bs,
                            n_clients, rates32, scales32, flags, n_chunks);
+    return check_launch(who);
+}
+
+// The MX quantiser (the downlink): outside the launch-branch table as the MX reductions are, one
+// instantiation per (source dtype, element format).  Every refusal comes before the first HIP call.
+int64_t flame_mx_quantize_chunk_elems(void) { return kMxqChunk; }
+
+int flame_mx_quantize(int src_dtype, int fmt, unsigned flags, const flame_segment* segs, int32_t n_segs,
+                      int64_t n_chunks, void* stream) {
+    const char* const who = "flame_mx_quantize";
+    if (!is_f32_or_16(src_dtype))
+        return set_err(FLAME_ENOTSUP, "%s: source dtype %d is not supported (f32, bf16 or f16 only)", who, src_dtype);
+    if (fmt != FLAME_FP8_E4M3 && fmt != FLAME_FP8_E5M2 && fmt != FLAME_FP4_E2M1)
+        return set_err(FLAME_ENOTSUP, "%s: element format %d is not supported (fp8 e4m3, fp8 e5m2 or fp4 e2m1 only)", who, fmt);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (int rc = check_flags(who, flags, 0)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(src_dtype, [&](auto sd) {
+        dispatch<FLAME_FP8_E4M3, FLAME_FP8_E5M2, FLAME_FP4_E2M1>(fmt, [&](auto fd) {
+            hipLaunchKernelGGL((mx_quantize_kernel<decltype(sd)::value, decltype(fd)::value>), grid, block, 0, st, segs, n_segs,
+                               n_chunks);
+        });
+    });
     return check_launch(who);
 }
 

@@ -182,9 +182,20 @@ class MessageEncoder:
     """Encodes flame messages whose tensors (device or host) go straight into one pinned payload
     buffer.  ``encode`` returns a read-only ``memoryview`` of that buffer, valid until the next
     ``encode`` on this encoder reuses it (``ring`` buffers are cycled; each is reused only once
-    the copies into it have completed); ``encode_bytes`` returns an independent ``bytes``."""
+    the copies into it have completed); ``encode_bytes`` returns an independent ``bytes``.
 
-    def __init__(self, ring: int = 2, pin: bool = True):
+    ``mx`` ("e4m3", "e5m2" or "e2m1"; default None: nothing changes) is the MX downlink: a dict under
+    ``message["weights"]`` leaves as ``engine.mx_quantize(weights, mx, mx_min_numel)`` of it, an
+    :class:`flame_amd.mx.MXWeights` of 0.258 (fp8) or 0.133 (e2m1) of the fp32 bytes, quantised on the
+    device by one flame_mx_quantize launch per source dtype.  The trainer reads
+    ``mx.dequantize(msg["weights"])``.  The caller's message and tensors are untouched."""
+
+    def __init__(self, ring: int = 2, pin: bool = True, mx=None, mx_min_numel: int = 0):
+        if mx is not None:
+            from . import mx as _mx
+            if mx not in _mx.FORMATS:
+                raise ValueError(f"flame_amd.mx.quantize: fmt {mx!r} is not one of {sorted(_mx.FORMATS)}")
+        self.mx, self.mx_min_numel = mx, mx_min_numel
         self.ring = max(1, int(ring))
         self.pin = pin and torch.cuda.is_available()
         self._bufs = [None] * self.ring
@@ -200,6 +211,10 @@ class MessageEncoder:
         return buf
 
     def encode(self, message: Any) -> memoryview:
+        if self.mx is not None and isinstance(message, dict) and isinstance(message.get("weights"), dict):
+            from . import engine
+            message = dict(message)     # shallow: the caller's message keeps its own weights
+            message["weights"] = engine.mx_quantize(message["weights"], self.mx, self.mx_min_numel)
         # a fresh random mark per message: no bytes of the message itself can pass for a placeholder
         pieces, total = _layout(message, os.urandom(_MARK_LEN))
         buf = self._buffer(total)

@@ -4,7 +4,7 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``synth_fill_``) need the native
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``synth_fill_``) need the native
 library and a HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
@@ -1267,6 +1267,101 @@ def noise_fill(like: dict, seed: int, rnd: int, std: float, *, device=None) -> d
             streams.append(pos)
     noise_fill_(outs, streams, [0] * len(outs), seed, rnd, std)
     return collections.OrderedDict(zip(keys, outs))
+
+
+# ------------------------------------------------------------------ the MX downlink: quantise on the device
+MX_FORMAT_CODE = {fmt: MX_CODE[dt] for fmt, (dt, _, _) in mx.FORMATS.items()}
+
+
+def plan_mx_quantize(segs: Sequence[Seg], chunk: Optional[int] = None):
+    """[segments (10 words)] -> (meta, n_chunks): the metadata block of one flame_mx_quantize launch (no
+    GPU needed).  A segment's ``inp`` is the source, ``out`` the element bytes, ``cur_out`` the scale
+    bytes; every segment starts a chunk, so a block of 32 never straddles two keys."""
+    if not segs:
+        raise ValueError("empty segment list")
+    b = _Block(chunk or int(N.lib().flame_mx_quantize_chunk_elems()))
+    head = np.zeros((len(segs), SEG_WORDS), dtype=np.uint64)
+    for i, s in enumerate(segs):
+        fixed = (s.out, s.inp, 0, s.cur_out)
+        head[i] = (*fixed, 0, 0, s.numel, b.chunk_begin(s.numel), b.unaligned(fixed), 0)
+    b.add("segs", head)
+    return b.finish()
+
+
+def mx_out_bytes(fmt: str, numel: int) -> int:
+    """Element bytes of ``numel`` elements quantised to ``fmt``."""
+    return mx_row_len(mx.FORMATS[fmt][0], numel)
+
+
+def mx_quantize_(srcs: List[torch.Tensor], qs: List[torch.Tensor], scales: List[torch.Tensor], fmt: str) -> None:
+    """qs[s], scales[s] = the element and E8M0 scale bytes of ``mx.quantize`` for srcs[s], written in
+    place (kernel: flame_mx_quantize; DESIGN.md §2 "the MX quantiser").  ``srcs`` are contiguous device
+    tensors of f32 / bf16 / f16; ``qs`` contiguous device tensors of ``numel`` bytes (``ceil(numel / 2)`` for
+    "e2m1"), ``scales`` of ``ceil(numel / 32)`` bytes, any 1-byte dtype.  A tensor off 16-byte alignment
+    sends its key element by element.  One launch per source dtype on torch's current stream."""
+    if fmt not in mx.FORMATS:
+        raise ValueError(f"flame_amd.mx.quantize: fmt {fmt!r} is not one of {sorted(mx.FORMATS)}")
+    if not (len(srcs) == len(qs) == len(scales)):
+        raise ValueError("flame_amd.mx_quantize_: one element tensor and one scale tensor per source")
+    if not srcs:
+        return
+    device = srcs[0].device
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.mx_quantize_: tensors must live on the GPU (no CPU fallback)")
+    fcode = MX_FORMAT_CODE[fmt]
+    L = N.lib()
+    keep = []
+    for code, idx in by_dtype(range(len(srcs)), lambda s: srcs[s].dtype).items():
+        if srcs[idx[0]].dtype not in mx.QUANTIZED_FROM:
+            raise TypeError(f"flame_amd.mx_quantize_: {srcs[idx[0]].dtype} keys are not quantised (f32, bf16, f16 only)")
+        segs = []
+        for s in idx:
+            n = srcs[s].numel()
+            for t, want in ((srcs[s], n), (qs[s], mx_out_bytes(fmt, n)), (scales[s], mx.n_blocks(n))):
+                if not (t.is_contiguous() and t.device == device):
+                    raise ValueError("flame_amd.mx_quantize_: contiguous tensors on one device")
+                if t is not srcs[s] and (t.element_size() != 1 or t.numel() != want):
+                    raise ValueError(f"flame_amd.mx_quantize_: a key of {n} elements needs {want} bytes here, "
+                                     f"got {t.numel()} of {t.dtype}")
+            if n:
+                segs.append(Seg(n, out=qs[s].data_ptr(), inp=srcs[s].data_ptr(), cur_out=scales[s].data_ptr()))
+        if not segs:
+            continue
+        meta, n_chunks = plan_mx_quantize(segs)
+        nbytes = sum(sg.numel * ITEMSIZE[code] + mx_out_bytes(fmt, sg.numel) + mx.n_blocks(sg.numel) for sg in segs)
+        _launch("flame_mx_quantize", nbytes, device, keep, meta,
+                lambda b: L.flame_mx_quantize(code, fcode, 0, b, len(segs), n_chunks, _stream_ptr(device)))
+    _keepalive(keep + list(srcs) + list(qs) + list(scales), device)
+
+
+def mx_quantize(weights, fmt: str = "e4m3", min_numel: int = 0, *, device=None) -> "mx.MXWeights":
+    """``mx.quantize(weights, fmt, min_numel)`` computed on the device: the same keys are quantised (fp32 /
+    bf16 / f16 of at least ``max(min_numel, 1)`` elements), to the same scale bytes and element bytes
+    (where the element is a NaN, to some NaN); every other key passes through as the object it is.  The
+    outputs are new device tensors: a float8 tensor of the key's shape, or a 1-D ``float4_e2m1fn_x2``
+    tensor with the key's shape in ``MXWeights.shapes``.  A host-resident or strided source is staged to
+    the device first.  One flame_mx_quantize launch per source dtype on torch's current stream; nothing is
+    read back."""
+    if fmt not in mx.FORMATS:
+        raise ValueError(f"flame_amd.mx.quantize: fmt {fmt!r} is not one of {sorted(mx.FORMATS)}")
+    device = _hip_device(device, "mx_quantize", prefer=weights)
+    edt = mx.FORMATS[fmt][0]
+    out, scales, shapes = collections.OrderedDict(), {}, {}
+    srcs, qs = [], []
+    for k, v in weights.items():
+        out[k] = v
+        if isinstance(v, torch.Tensor) and v.dtype in mx.QUANTIZED_FROM and v.numel() >= max(min_numel, 1):
+            n = v.numel()
+            srcs.append(_staged(v.detach(), device))
+            q = torch.empty(mx_out_bytes(fmt, n), dtype=torch.uint8, device=device)
+            qs.append(q)
+            scales[k] = torch.empty(mx.n_blocks(n), dtype=torch.uint8, device=device)
+            if edt == MX_PACKED:
+                out[k], shapes[k] = q.view(edt), tuple(v.shape)
+            else:
+                out[k] = q.view(edt).view(v.shape)
+    mx_quantize_(srcs, qs, [scales[k] for k in scales], fmt)
+    return mx.MXWeights(out, scales, shapes=shapes)
 
 
 # ------------------------------------------------------------------ dict-level helpers used by the optimizers

@@ -42,6 +42,8 @@
  *                               dequantized update)
  *   flame_agg_reduce_mxfp4      (no reference counterpart: MXFP4 updates -- OCP e2m1 elements, two per byte,
  *                               one E8M0 scale per 32 -- into an fp32 model; the same statements again)
+ *   flame_mx_quantize           (no reference counterpart: the model as MXFP8 / MXFP4 bytes for the
+ *                               downlink, by flame_amd.mx.quantize's rule)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -408,6 +410,40 @@ int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, cons
                            int32_t n_segs, int64_t n_chunks, const void *const *clients,
                            const void *const *block_scales, int32_t n_clients, const float *rates32,
                            const float *scales32, void *stream);
+
+/*
+ * The MX quantiser: fp32 / bf16 / f16 keys into MX element bytes and E8M0 scale bytes in one launch per
+ * (source dtype, element format) -- the model message's downlink (flame_amd.egress.MessageEncoder(mx=)).
+ * flame_amd.mx.quantize is the definition ("the MX quantiser"); flame_agg_reduce_mx's and
+ * flame_agg_reduce_mxfp4's comments state the formats and the e2m1 packing.
+ *   src_dtype : FLAME_F32, FLAME_BF16 or FLAME_F16: every segment's in (a 16-bit source is widened to
+ *               fp32 exactly).
+ *   fmt       : FLAME_FP8_E4M3, FLAME_FP8_E5M2 or FLAME_FP4_E2M1: every segment's out.
+ *   flags     : 0.
+ *   segs      : in = the source, numel elements; out = the element bytes, numel of them (fp8) or
+ *               ceil(numel / 2) (e2m1, an odd numel's last high nibble written as 0); cur_out = the
+ *               scale bytes, ceil(numel / 32) of them; chunk_begin counts chunks of
+ *               flame_mx_quantize_chunk_elems() = 8,192 source elements, so a block of 32 never
+ *               straddles two segments.  FLAME_SEG_UNALIGNED speaks of in, out and cur_out.  No other
+ *               field is read and nothing is written past the three extents.
+ * Per block b of 32 flat elements (a partial last block's missing elements count as +0), denormals kept:
+ *   amax = max |x| over the block's FINITE elements (0 without one)
+ *   e    = amax > 0 ? clamp(floor(log2 amax) - emax, -127, 127) : 0      emax = 8, 15, 2 (e4m3, e5m2, e2m1)
+ *   scale byte = e + 127; for e2m1 255 when any element of the block is a NaN
+ *   y    = round_f32(x * 2^-e)                                           one IEEE fp32 multiply
+ *   fp8  : y saturated to +-fmax (448, 57344; +-inf included), rounded to nearest even; a NaN stays a NaN
+ *          (sign and payload not stated)
+ *   e2m1 : |y| rounded to nearest of 0, 0.5, 1, 1.5, 2, 3, 4, 6, ties to the even mantissa bit, anything
+ *          above 5 is 6 (+-inf included); the sign is kept (-0 is code 8); a NaN is code 0
+ * Scale bytes equal flame_amd.mx.quantize's byte for byte, element bytes wherever its element is not a NaN.
+ * Refusals, each before any HIP call and named in flame_last_error: a source dtype or an element format
+ * other than those above is FLAME_ENOTSUP (the message names what is accepted); a NULL table,
+ * n_segs <= 0, n_chunks outside [1, 2^31) or any flag is FLAME_EINVAL.  Device tables only.  Not a launch
+ * branch of flame_launch_branches().
+ */
+int flame_mx_quantize(int src_dtype, int fmt, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                      int64_t n_chunks, void *stream);
+int64_t flame_mx_quantize_chunk_elems(void);
 
 /*
  * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,
