@@ -43,6 +43,7 @@ EXPORTS = (
     "flame_update_stats", "flame_update_stats_scratch_bytes", "flame_agg_reduce_scaled",
     "flame_agg_reduce_mixed", "flame_agg_reduce_mx", "flame_agg_reduce_mxfp4",
     "flame_mx_quantize", "flame_mx_quantize_chunk_elems",
+    "flame_sparse_chunk_elems", "flame_sparse_index_scratch_bytes", "flame_sparse_index", "flame_agg_reduce_sparse",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
     "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_agg_select", "flame_agg_select_max_clients", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
@@ -113,6 +114,14 @@ def lib() -> ctypes.CDLL:
     L.flame_mx_quantize.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp]
     L.flame_mx_quantize_chunk_elems.restype = i64
     L.flame_mx_quantize_chunk_elems.argtypes = []
+    L.flame_sparse_chunk_elems.restype = i64
+    L.flame_sparse_chunk_elems.argtypes = []
+    L.flame_sparse_index_scratch_bytes.restype = i64
+    L.flame_sparse_index_scratch_bytes.argtypes = [i64, i32]
+    L.flame_sparse_index.restype = ctypes.c_int
+    L.flame_sparse_index.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, i64, vp]
+    L.flame_agg_reduce_sparse.restype = ctypes.c_int
+    L.flame_agg_reduce_sparse.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp]
     L.flame_agg_trimmed.restype = ctypes.c_int
     L.flame_agg_trimmed.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, i32, i32, vp]
     L.flame_agg_trimmed_max_k.restype = ctypes.c_int

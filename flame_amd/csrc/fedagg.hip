@@ -1117,6 +1117,205 @@ __global__ __launch_bounds__(kBlock) void agg_reduce_mxfp4_kernel(const flame_se
         if (e0 + j < sg.numel) st1(op + j, acc[j]);
 }
 
+// ---------------------------------------------------------------- top-k sparse updates
+// flame_sparse_index + flame_agg_reduce_sparse: (int32 index, fp32 value) updates into an fp32 aggregate
+// ("the sparse contract"; flame_amd/sparse.py is the format).  Indices are flat C-order
+// element indices of the segment, strictly ascending per client.  A chunk is 4,096 output elements, one
+// workgroup; a wave owns one 1,024-element sub-range of it, so no two waves share an accumulator and
+// neither kernel has a barrier.
+//   * sparse_index_kernel validates and buckets.  Validation is split by POSITION (a chunk's workgroup
+//     streams the cl-th of seg_chunks equal slices of every client's index array, coalesced and
+//     non-temporal), never by value: slices cut by a search over unsorted indices could leave entries
+//     unread.  An entry is bad when it is negative, >= numel or not greater than its predecessor; bad
+//     entries are counted per client with integer atomics (an error path: one per lane that saw one).
+//     Bucketing: one lower_bound per (client, sub-range boundary), 5 boundaries per chunk; the position
+//     is the `hi` of the sub-range that ends there and the `lo` of the one that starts there.  A search
+//     reads idx[mid] for 0 <= mid < nnz only, whatever the indices hold.
+//   * agg_reduce_sparse_kernel is an output-stationary gather: the wave loads its 1,024 accumulators
+//     into LDS (four 1 KiB wave loads), walks the clients in order and stores them.  For client i lane j
+//     loads idx[lo + j], val[lo + j] (coalesced, non-temporal; CU clients' first 64 entries are in flight
+//     before the first LDS update, entries past 64 loop), forms t = v * rate (the clip scale first) and
+//     does read-add-write on acc[idx - sub_base].  A client's indices are unique, so one wave
+//     instruction never touches an address twice; a wave's LDS operations retire in program order, so
+//     the client order holds; hence no atomic.  lo / hi are clamped to 0 <= lo <= hi <= nnz and an entry
+//     is applied only if (uint32)(idx - sub_base) < sub_len: bad indices give wrong sums, never an
+//     access outside the tables.  Products and sums are the scalar v_mul_f32 / v_add_f32
+//     (FLAME_SPARSE_FN), one IEEE rounding each.  Register figures and residency: DESIGN.md §4.
+#define FLAME_SPARSE_FN __attribute__((target("no-packed-fp32-ops")))
+#ifndef FLAME_T_SPARSE_UNROLL
+#define FLAME_T_SPARSE_UNROLL 8
+#endif
+constexpr int kSparseUnroll = FLAME_T_SPARSE_UNROLL;    // clients whose first 64 entries are in flight per wave
+constexpr int kWaveLanes = 64;
+constexpr int kSparseSubs = kBlock / kWaveLanes;        // sub-ranges per chunk: one per wave
+constexpr int kSparseSub = 1024;                        // elements per sub-range
+constexpr int64_t kSparseChunk = static_cast<int64_t>(kSparseSubs) * kSparseSub;
+static_assert(kSparseSub == kWaveLanes * 16, "a lane loads and stores four 16-byte vectors of its wave's sub-range");
+using f4 = __attribute__((ext_vector_type(4))) float;
+struct SparseBound { int32_t lo, hi; };                 // one client's entry range of one sub-range
+
+// first position p of [0, nnz) with idx[p] >= key (nnz without one); reads inside [0, nnz) only
+FLAME_SPARSE_FN __device__ __forceinline__ int64_t sparse_lower_bound(const int32_t* idx, int64_t nnz, int64_t key) {
+    int64_t lo = 0, hi = nnz;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (static_cast<int64_t>(ld1(idx + mid)) < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) FLAME_SPARSE_FN void sparse_index_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                              const uint64_t* __restrict__ indices,
+                                                                              const int64_t* __restrict__ nnz, int n_clients,
+                                                                              int64_t n_chunks, unsigned long long* bad,
+                                                                              SparseBound* __restrict__ bounds) {
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int64_t cl = chunk - sg.chunk_begin;
+    const int64_t seg_chunks = (sg.numel + kSparseChunk - 1) / kSparseChunk;
+    if (cl >= seg_chunks) return;                        // the idle chunk of a launch of empty segments
+    const uint64_t* ip = indices + static_cast<int64_t>(s) * n_clients;
+    const int64_t* np = nnz + static_cast<int64_t>(s) * n_clients;
+    const int t = static_cast<int>(threadIdx.x), lane = t % kWaveLanes;
+    // validation: this chunk's slice of every client's positions, a wave per client
+    for (int i = t / kWaveLanes; i < n_clients; i += kSparseSubs) {
+        const int32_t* idx = reinterpret_cast<const int32_t*>(ip[i]);
+        const int64_t n = np[i];
+        const int64_t per = (n + seg_chunks - 1) / seg_chunks;
+        const int64_t p0 = cl * per, p1 = p0 + per < n ? p0 + per : n;
+        unsigned long long cnt = 0;
+        for (int64_t p = p0 + lane; p < p1; p += kWaveLanes) {
+            const int32_t v = __builtin_nontemporal_load(G(idx + p));
+            bool b = v < 0 || static_cast<int64_t>(v) >= sg.numel;
+            if (p > 0) b = b || v <= ld1(idx + p - 1);
+            cnt += b ? 1 : 0;
+        }
+        if (cnt) __hip_atomic_fetch_add(bad + i, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // bucketing: boundary b of the chunk is element cl * 4,096 + b * 1,024 (cut at numel)
+    SparseBound* row = bounds + chunk * kSparseSubs * n_clients;
+    for (int u = t; u < n_clients * (kSparseSubs + 1); u += kBlock) {
+        const int b = u / n_clients, i = u - b * n_clients;
+        int64_t key = cl * kSparseChunk + static_cast<int64_t>(b) * kSparseSub;
+        if (key > sg.numel) key = sg.numel;
+        const int64_t p = sparse_lower_bound(reinterpret_cast<const int32_t*>(ip[i]), np[i], key);
+        const int32_t pos = p > 0x7FFFFFFF ? 0x7FFFFFFF : static_cast<int32_t>(p);
+        if (b < kSparseSubs) row[b * n_clients + i].lo = pos;
+        if (b > 0) row[(b - 1) * n_clients + i].hi = pos;
+    }
+}
+
+// a bound as the reduction reads it: 0 <= lo <= hi <= nnz whatever the scratch holds
+FLAME_SPARSE_FN __device__ __forceinline__ SparseBound sparse_clamp(SparseBound b, int64_t nnz) {
+    const int32_t n = nnz < 0 ? 0 : nnz > 0x7FFFFFFF ? 0x7FFFFFFF : static_cast<int32_t>(nnz);
+    b.lo = b.lo < 0 ? 0 : b.lo > n ? n : b.lo;
+    b.hi = b.hi < b.lo ? b.lo : b.hi > n ? n : b.hi;
+    return b;
+}
+
+template <int CU, bool SCALED>
+__global__ __launch_bounds__(kBlock) FLAME_SPARSE_FN void agg_reduce_sparse_kernel(
+        const flame_segment* __restrict__ segs, int n_segs, const uint64_t* __restrict__ indices,
+        const uint64_t* __restrict__ values, const int64_t* __restrict__ nnz, int n_clients, const float* __restrict__ r32,
+        const float* __restrict__ s32, const SparseBound* __restrict__ bounds, int64_t n_chunks) {
+    __shared__ __attribute__((aligned(16))) float lds[kSparseChunk];
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const int s = find_segment(segs, n_segs, chunk);
+    const flame_segment sg = segs[s];
+    const int t = static_cast<int>(threadIdx.x), lane = t % kWaveLanes;
+    const int q = __builtin_amdgcn_readfirstlane(t / kWaveLanes);                  // the wave's sub-range
+    const int64_t sub_base = (chunk - sg.chunk_begin) * kSparseChunk + static_cast<int64_t>(q) * kSparseSub;
+    if (sub_base >= sg.numel) return;                    // the whole wave (there is no barrier to miss)
+    const uint32_t sub_len = sg.numel - sub_base < kSparseSub ? static_cast<uint32_t>(sg.numel - sub_base) : kSparseSub;
+    const uint64_t* ip = indices + static_cast<int64_t>(s) * n_clients;
+    const uint64_t* vp = values + static_cast<int64_t>(s) * n_clients;
+    const int64_t* np = nnz + static_cast<int64_t>(s) * n_clients;
+    const SparseBound* bp = bounds + (chunk * kSparseSubs + q) * n_clients;
+    const float* in = reinterpret_cast<const float*>(sg.in) + sub_base;
+    float* out = reinterpret_cast<float*>(sg.out) + sub_base;
+    if (sg.in == sg.out) {          // in place and no client has an entry here: nothing to load or store
+        bool any = false;
+        for (int i = lane; i < n_clients; i += kWaveLanes) {
+            const SparseBound b = sparse_clamp(bp[i], np[i]);
+            any = any || b.hi > b.lo;
+        }
+        if (!__builtin_amdgcn_ballot_w64(any)) return;
+    }
+    float* acc = lds + q * kSparseSub;
+    const bool aligned = !(sg.flags & FLAME_SEG_UNALIGNED);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const uint32_t o = static_cast<uint32_t>(v * 4 * kWaveLanes + 4 * lane);
+        if (aligned && o + 4 <= sub_len) {
+            const V16 x = ld_v(in + o);
+            f4 f;
+            __builtin_memcpy(&f, x.w, 16);
+            *reinterpret_cast<f4*>(acc + o) = f;
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (o + j < sub_len) acc[o + j] = ld1(in + o + j);
+        }
+    }
+    // one entry of client c: acc[idx - sub_base] = acc + t, in this order per element
+    auto apply = [&](int c, int32_t ix, float v) FLAME_SPARSE_FN {
+        float tv;
+        if constexpr (SCALED) tv = (v * s32[c]) * r32[c];
+        else tv = v * r32[c];
+        const uint32_t off = static_cast<uint32_t>(ix) - static_cast<uint32_t>(sub_base);
+        if (off < sub_len) acc[off] = acc[off] + tv;
+    };
+    // a client's entries from the d0-th on, 64 per step (the trip count is wave-uniform)
+    auto rest = [&](int c, SparseBound b, int64_t d0) FLAME_SPARSE_FN {
+        const int32_t* idx = reinterpret_cast<const int32_t*>(ip[c]) + b.lo;
+        const float* val = reinterpret_cast<const float*>(vp[c]) + b.lo;
+        const int64_t n = b.hi - b.lo;
+        for (int64_t d = d0; d < n; d += kWaveLanes)
+            if (d + lane < n)
+                apply(c, __builtin_nontemporal_load(G(idx + d + lane)), __builtin_nontemporal_load(G(val + d + lane)));
+    };
+    int i = 0;
+    for (; i + CU <= n_clients; i += CU) {
+        SparseBound b[CU];
+        int32_t ix[CU];
+        float vl[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) b[u] = sparse_clamp(bp[i + u], np[i + u]);
+#pragma unroll
+        for (int u = 0; u < CU; ++u) {
+            ix[u] = -1;
+            vl[u] = 0.f;
+            if (lane < b[u].hi - b[u].lo) {
+                ix[u] = __builtin_nontemporal_load(G(reinterpret_cast<const int32_t*>(ip[i + u]) + b[u].lo + lane));
+                vl[u] = __builtin_nontemporal_load(G(reinterpret_cast<const float*>(vp[i + u]) + b[u].lo + lane));
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CU; ++u) {
+            if (lane < b[u].hi - b[u].lo) apply(i + u, ix[u], vl[u]);
+            rest(i + u, b[u], kWaveLanes);
+        }
+    }
+    for (; i < n_clients; ++i) rest(i, sparse_clamp(bp[i], np[i]), 0);
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+        const uint32_t o = static_cast<uint32_t>(v * 4 * kWaveLanes + 4 * lane);
+        if (aligned && o + 4 <= sub_len) {
+            const f4 f = *reinterpret_cast<const f4*>(acc + o);
+            V16 x;
+            __builtin_memcpy(x.w, &f, 16);
+            st_v(out + o, x);
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                if (o + j < sub_len) st1(out + o + j, acc[o + j]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- MX downlink: the quantiser
 // flame_mx_quantize: fp32 / bf16 / f16 keys into OCP e4m3 / e5m2 bytes or packed e2m1 nibbles plus one
 // E8M0 scale byte per 32 elements, by flame_amd.mx.quantize's rule ("the MX quantiser"):
@@ -4486,6 +4685,66 @@ int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, cons
     else
         hipLaunchKernelGGL((agg_reduce_mxfp4_kernel<kClientUnrollMx4, false>), grid, block, 0, st, segs, n_segs, cl, bs,
                            n_clients, rates32, scales32, flags, n_chunks);
+    return check_launch(who);
+}
+
+// Top-k sparse updates into an fp32 aggregate: two launches over the same tables, flame_sparse_index
+// (validate, bucket) and flame_agg_reduce_sparse (the gather).  Outside the launch-branch table, one
+// instantiation per SCALED; every refusal comes before the first HIP call.
+int64_t flame_sparse_chunk_elems(void) { return kSparseChunk; }
+
+int64_t flame_sparse_index_scratch_bytes(int64_t n_chunks, int32_t n_clients) {
+    if (n_chunks <= 0 || n_chunks > 0x7FFFFFFFll || n_clients <= 0) return 0;
+    return n_chunks * kSparseSubs * static_cast<int64_t>(n_clients) * static_cast<int64_t>(sizeof(SparseBound));
+}
+
+int flame_sparse_index(const flame_segment* segs, int32_t n_segs, int64_t n_chunks, const void* const* indices,
+                       const int64_t* nnz, int32_t n_clients, int64_t* bad, void* scratch, int64_t scratch_bytes,
+                       void* stream) {
+    const char* const who = "flame_sparse_index";
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (!indices) return set_err(FLAME_EINVAL, "%s: index pointer table is NULL", who);
+    if (!nnz) return set_err(FLAME_EINVAL, "%s: nnz table is NULL", who);
+    if (!bad) return set_err(FLAME_EINVAL, "%s: output array is NULL", who);
+    if (int rc = need_scratch(who, scratch, scratch_bytes, flame_sparse_index_scratch_bytes(n_chunks, n_clients))) return rc;
+    hipLaunchKernelGGL(sparse_index_kernel, dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), segs, n_segs, reinterpret_cast<const uint64_t*>(indices), nnz,
+                       n_clients, n_chunks, reinterpret_cast<unsigned long long*>(bad), static_cast<SparseBound*>(scratch));
+    return check_launch(who);
+}
+
+int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                            const void* const* indices, const void* const* values, const int64_t* nnz, int32_t n_clients,
+                            const float* rates32, const float* scales32, const void* bounds, int64_t bounds_bytes,
+                            void* stream) {
+    const char* const who = "flame_agg_reduce_sparse";
+    if (agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: aggregate dtype %d is not supported (sparse updates into f32 only)", who, agg_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (!indices) return set_err(FLAME_EINVAL, "%s: index pointer table is NULL", who);
+    if (!values) return set_err(FLAME_EINVAL, "%s: value pointer table is NULL", who);
+    if (!nnz) return set_err(FLAME_EINVAL, "%s: nnz table is NULL", who);
+    if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if (flags & FLAME_AGG_INIT_FIRST)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (an absent element has no first client)", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
+    if (int rc = check_flags(who, flags, 0)) return rc;
+    if (int rc = need_scratch(who, bounds, bounds_bytes, flame_sparse_index_scratch_bytes(n_chunks, n_clients))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint64_t* ix = reinterpret_cast<const uint64_t*>(indices);
+    const uint64_t* vl = reinterpret_cast<const uint64_t*>(values);
+    const SparseBound* bd = static_cast<const SparseBound*>(bounds);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    if (scales32)
+        hipLaunchKernelGGL((agg_reduce_sparse_kernel<kSparseUnroll, true>), grid, block, 0, st, segs, n_segs, ix, vl, nnz,
+                           n_clients, rates32, scales32, bd, n_chunks);
+    else
+        hipLaunchKernelGGL((agg_reduce_sparse_kernel<kSparseUnroll, false>), grid, block, 0, st, segs, n_segs, ix, vl, nnz,
+                           n_clients, rates32, scales32, bd, n_chunks);
     return check_launch(who);
 }
 

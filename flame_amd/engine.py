@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import mx, shm_lease
+from . import mx, shm_lease, sparse
 
 DTYPE_CODE = {
     torch.float32: N.FLAME_F32, torch.bfloat16: N.FLAME_BF16, torch.float16: N.FLAME_F16,
@@ -472,10 +472,68 @@ def is_mx(w) -> bool:
 
 
 def refuse_mx(ws, who: str) -> None:
-    """TypeError when one of the updates ``ws`` is an MX update: ``who`` does not take them."""
+    """TypeError when one of the updates ``ws`` is an MX update or a sparse one: ``who`` takes neither."""
     for w in ws:
         if w is not None and is_mx(w):
             raise TypeError(f"flame_amd: {who} does not take MX updates (a follow-up, not a silent slow path).  {MX_SUPPORTED}")
+    refuse_sparse(ws, who)
+
+
+# top-k sparse updates (flame_amd.sparse.SparseWeights: fp32 values + int32 indices per sparsified key),
+# which one flame_sparse_index and one flame_agg_reduce_sparse launch sum into an fp32 aggregate
+SPARSE_SUPPORTED = ("Sparse updates are supported as flame_amd.sparse.SparseWeights whose every entry holds the key as a "
+                    "1-D fp32 value tensor with a 1-D int32 index tensor of the same length (strictly ascending) in "
+                    "SparseWeights.indices and the aggregate's shape in SparseWeights.shapes, summed into an fp32 "
+                    "aggregate by engine.accumulate (FedAvg, FedProx and FedGFT with defer=False)")
+
+
+def is_sparse(w) -> bool:
+    """``w`` is a sparse update, a :class:`flame_amd.sparse.SparseWeights` (one isinstance, as :func:`is_mx`)."""
+    return isinstance(w, sparse.SparseWeights)
+
+
+def refuse_sparse(ws, who: str) -> None:
+    """TypeError when one of the updates ``ws`` is a sparse update: ``who`` does not take them (a values
+    tensor would otherwise pass for a dense fp32 key)."""
+    for w in ws:
+        if w is not None and is_sparse(w):
+            raise TypeError(f"flame_amd: {who} does not take sparse updates (a follow-up, not a silent slow path).  "
+                            f"{SPARSE_SUPPORTED}")
+
+
+def sparse_route(agg_dtype, ws, k, agg_shape) -> bool:
+    """True when the updates ``ws`` (all carrying ``k``) hold key ``k`` as sparse values + indices that ONE
+    flame_sparse_index / flame_agg_reduce_sparse pair takes; False when none holds it sparse (its present
+    route); every case in between is a TypeError.  What only the device can see -- unsorted, duplicate or
+    out-of-range indices -- is flame_sparse_index's to count."""
+    held = [is_sparse(w) and k in w.indices for w in ws]
+    if not any(held):
+        return False
+    if not all(held):
+        raise TypeError(f"flame_amd: key {k!r} is sparse in update {held.index(True)} and dense in update "
+                        f"{held.index(False)}: per-key mixtures of sparse and dense updates are not supported.  {SPARSE_SUPPORTED}")
+    if agg_dtype != torch.float32:
+        raise TypeError(f"flame_amd: key {k!r}: sparse updates into a {agg_dtype} aggregate are not supported.  {SPARSE_SUPPORTED}")
+    numel = math.prod(agg_shape)
+    for w in ws:
+        v, i = w[k], w.indices[k]
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 1:
+            raise TypeError(f"flame_amd: key {k!r}: the sparse values are {getattr(v, 'dtype', type(v).__name__)} "
+                            f"{tuple(getattr(v, 'shape', ()))}, not 1-D torch.float32.  {SPARSE_SUPPORTED}")
+        if not isinstance(i, torch.Tensor) or i.dtype != torch.int32 or i.dim() != 1 or i.numel() != v.numel():
+            raise TypeError(f"flame_amd: key {k!r}: the sparse indices are {getattr(i, 'dtype', type(i).__name__)} "
+                            f"{tuple(getattr(i, 'shape', ()))}, not torch.int32 ({v.numel()},).  {SPARSE_SUPPORTED}")
+        shape = w.shapes.get(k)
+        if shape is None:
+            raise TypeError(f"flame_amd: key {k!r} has sparse values without a SparseWeights.shapes entry: the values do "
+                            f"not say which tensor they index.  {SPARSE_SUPPORTED}")
+        if tuple(shape) != tuple(agg_shape):
+            raise TypeError(f"flame_amd: key {k!r}: the sparse update's logical shape {tuple(shape)} is not the aggregate's "
+                            f"{tuple(agg_shape)}.  {SPARSE_SUPPORTED}")
+        if v.numel() > numel or numel >= sparse.INDEX_LIMIT:
+            raise TypeError(f"flame_amd: key {k!r}: {v.numel()} sparse entries into {numel} elements (strictly ascending int32 "
+                            f"indices address at most min(numel, 2^31) of them).  {SPARSE_SUPPORTED}")
+    return True
 
 
 def mx_route(agg_dtype, ws, k, agg_shape=None):
@@ -1457,23 +1515,35 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         if k in per_key:
             groups.setdefault(tuple(per_key[k]), []).append(k)
     any_mx = any(is_mx(w) for w, _ in entries)      # (a float8 tensor in a plain dict: _check_cast refuses it)
+    any_sparse = any(is_sparse(w) for w, _ in entries)
     routed = []
     for cis, ks in groups.items():
         # MX keys: float8 elements + block scales of MXWeights under an fp32 aggregate (reduce_ groups
         # those into one flame_agg_reduce_mx per element format)
         mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape) is not None}
+        # sparse keys: fp32 values + int32 indices of SparseWeights under an fp32 aggregate (_SparseRound)
+        spk = [k for k in ks if any_sparse and sparse_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape)]
         # same: one reduction launch per dtype pair -- the aggregate's own dtype, or bf16 / f16
         # updates under an fp32 aggregate (reduce_ groups those into flame_agg_reduce_mixed)
-        same = [k for k in ks if k in mxk or (agg[k].dtype in DTYPE_CODE
+        sps = set(spk)
+        same = [k for k in ks if k not in sps and (k in mxk or (agg[k].dtype in DTYPE_CODE
                 and (all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)
-                     or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None))]
-        mixed = [k for k in ks if k not in same]
+                     or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None)))]
+        mixed = [k for k in ks if k not in same and k not in sps]
         for k in mixed:     # (a float8 tensor in a plain dict ends here)
             for ci in cis:
                 _check_cast(agg[k].dtype, weight_dtype(entries[ci][0], k))
-        routed.append((cis, mxk, same, mixed))
-    # every refusal of the round has been raised: the aggregate is untouched until here
-    for cis, mxk, same, mixed in routed:
+        routed.append((cis, mxk, same, mixed, spk))
+    # every refusal of the round has been raised: the aggregate is untouched until here.  The sparse keys'
+    # indices are validated on the device first (flame_sparse_index; its counters come back in one small
+    # copy, a synchronisation point): a bad index raises ValueError before any reduction is launched
+    sparse_rounds = [_SparseRound(agg, spk, cis, entries, scales, device) if spk else None for cis, _, _, _, spk in routed]
+    for sr in sparse_rounds:
+        if sr is not None:
+            sr.check()
+    for (cis, mxk, same, mixed, _), sr in zip(routed, sparse_rounds):
+        if sr is not None:
+            sr.reduce()
         # with clip scales the float keys take the scaled kernel; integer keys are never scaled
         parts = [(same, None)] if scales is None else [
             ([k for k in same if agg[k].is_floating_point()], [scales[ci] for ci in cis]),
@@ -1492,6 +1562,92 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         if scales is not None and mixed:
             sub = _prescaled(sub, [scales[ci] for ci in cis], mixed, device)
         _accumulate_mixed(agg, mixed, sub, device)
+
+
+def sparse_chunk_elems() -> int:
+    """Output elements per chunk of the two sparse launches, as compiled into the library."""
+    return int(N.lib().flame_sparse_chunk_elems())
+
+
+def sparse_scratch_bytes(n_chunks: int, n_clients: int) -> int:
+    """Bytes of bounds scratch flame_sparse_index writes and flame_agg_reduce_sparse reads."""
+    return int(N.lib().flame_sparse_index_scratch_bytes(n_chunks, n_clients))
+
+
+def plan_sparse(segs: Sequence[Seg], indices, values, nnz, rates, scales=None, chunk: Optional[int] = None):
+    """The metadata block both sparse launches read (no GPU needed): ``[segments] [index pointers] [value
+    pointers] [nnz] [rates32] [scales32]``, the three tables ``[n_segs][n_clients]``.  Returns ``(meta,
+    n_chunks, byte offsets by name)``; chunks of flame_sparse_chunk_elems() output elements."""
+    b = _Block(chunk or sparse_chunk_elems())
+    head = np.zeros((len(segs), SEG_WORDS), dtype=np.uint64)
+    for i, s in enumerate(segs):
+        head[i, :2] = (s.out, s.inp)
+        head[i, 6:9] = (s.numel, b.chunk_begin(s.numel), s.flags | b.unaligned((s.out, s.inp)))
+    b.add("segs", head)
+    b.add("indices", np.asarray(indices, dtype=np.uint64))
+    b.add("values", np.asarray(values, dtype=np.uint64))
+    b.add("nnz", np.asarray(nnz, dtype=np.int64))
+    b.add("r32", _f32(rates))
+    if scales is not None:
+        b.add("s32", _f32(scales))
+    meta, n_chunks = b.finish()
+    return meta, n_chunks, b.offs
+
+
+class _SparseRound:
+    """The sparse keys ``keys`` of one client group of :func:`accumulate`: everything is staged and
+    flame_sparse_index is launched here; :meth:`check` reads its counters back (one small D2H copy, which
+    waits for the stream) and raises ValueError on a bad index; :meth:`reduce` launches
+    flame_agg_reduce_sparse over the same tables.  Host-resident values and indices are copied to the
+    device once each (never read in place: the indices are read by both launches)."""
+
+    def __init__(self, agg, keys, cis, entries, scales, device):
+        L = N.lib()
+        self.device, self.cis, self.keep = device, cis, []
+        ws = [entries[ci][0] for ci in cis]
+        self.targets = [_Target(agg[k], device) for k in keys]
+        idx = [[_staged(w.indices[k], device) for w in ws] for k in keys]
+        val = [[_staged(w[k], device) for w in ws] for k in keys]
+        self.keep += [t.dev for t in self.targets] + [t for row in idx + val for t in row]
+        segs = [Seg(t.dev.numel(), out=t.dev.data_ptr(), inp=t.dev.data_ptr()) for t in self.targets]
+        nnz = [[t.numel() for t in row] for row in idx]
+        self.scaled = scales is not None
+        meta, self.n_chunks, self.offs = plan_sparse(
+            segs, [[t.data_ptr() for t in row] for row in idx], [[t.data_ptr() for t in row] for row in val], nnz,
+            [entries[ci][1] for ci in cis], [scales[ci] for ci in cis] if self.scaled else None)
+        self.n_segs, self.n = len(segs), len(cis)
+        self.entries = sum(map(sum, nnz))
+        self.elems = sum(s.numel for s in segs)
+        self.sbytes = sparse_scratch_bytes(self.n_chunks, self.n)
+        self.bounds = torch.empty(self.sbytes, dtype=torch.uint8, device=device)
+        self.bad = torch.zeros(self.n, dtype=torch.int64, device=device)
+        self.keep += [self.bounds, self.bad]
+        self.meta = _stage(meta, device, self.keep)
+        o = self.offs
+        # every index is read once; the bounds are written
+        _launch("flame_sparse_index", 4 * self.entries + self.sbytes, device, self.keep, self.meta,
+                lambda b: L.flame_sparse_index(b, self.n_segs, self.n_chunks, b + o["indices"], b + o["nnz"], self.n,
+                                               self.bad.data_ptr(), self.bounds.data_ptr(), self.sbytes, _stream_ptr(device)))
+
+    def check(self):
+        bad = self.bad.cpu().numpy()
+        if bad.any():
+            _keepalive(self.keep, self.device)
+            raise ValueError("flame_amd: sparse indices must be strictly ascending int32 in [0, numel): update(s) at position(s) "
+                             + ", ".join(f"{self.cis[i]} ({int(bad[i])} bad entries)" for i in np.flatnonzero(bad))
+                             + " hold negative, out-of-range, unsorted or duplicate indices; nothing was aggregated")
+
+    def reduce(self):
+        L, o, device = N.lib(), self.offs, self.device
+        # per client and key 8 * nnz (index + value), the bounds, one fp32 read and one fp32 write per element
+        _launch("flame_agg_reduce_sparse", 8 * self.entries + self.sbytes + 2 * ITEMSIZE[N.FLAME_F32] * self.elems, device,
+                self.keep, self.meta,
+                lambda b: L.flame_agg_reduce_sparse(N.FLAME_F32, 0, b, self.n_segs, self.n_chunks, b + o["indices"], b + o["values"],
+                                                    b + o["nnz"], self.n, b + o["r32"], b + o["s32"] if self.scaled else None,
+                                                    self.bounds.data_ptr(), self.sbytes, _stream_ptr(device)))
+        _keepalive(self.keep, device)
+        for t in self.targets:
+            t.writeback()
 
 
 def _prescaled(entries, scales, keys, device):

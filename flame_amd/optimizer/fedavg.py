@@ -108,6 +108,7 @@ class DeferredWeights(collections.abc.Mapping):
                 engine._check_cast(acc, dt)
 
     def _queue(self, entries):
+        engine.refuse_sparse([w for w, _ in entries], "a deferred queue (defer=True)")
         for w, _ in entries:
             self._check(w)
         # a view into a sender's shared-memory segment is copied to HBM before do() returns

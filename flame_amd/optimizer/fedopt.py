@@ -165,6 +165,12 @@ class FedOPT(FedAvg):
     def d_t(self, value):
         self._d_t = value
 
+    def _select(self, cache, total, kwargs=()):
+        entries, scales = super()._select(cache, total, kwargs)
+        # a sparse update's values tensor would pass for a dense fp32 key in the adaptive step
+        engine.refuse_sparse([w for w, _ in entries], "FedOPT")
+        return entries, scales
+
     def do(self, base_weights, cache, *, total: int = 0, version: int = 0, **kwargs):
         logger.debug("calling fedopt (flame_amd)")
         self._check_poisoned()
@@ -370,6 +376,7 @@ class FedOPT(FedAvg):
             self._flush_chain()
             ch = None
         popped = [(k, cache.pop(k)) for k in list(cache.iterkeys())]
+        engine.refuse_sparse([tres.weights for _, tres in popped], "FedOPT")
         keys = list(base_weights.keys())
         shapes = {k: base_weights[k].shape for k in keys}
         device = base_weights[keys[0]].device

@@ -42,6 +42,8 @@
  *                               dequantized update)
  *   flame_agg_reduce_mxfp4      (no reference counterpart: MXFP4 updates -- OCP e2m1 elements, two per byte,
  *                               one E8M0 scale per 32 -- into an fp32 model; the same statements again)
+ *   flame_sparse_index,         (no reference counterpart: top-k sparse updates -- int32 indices, fp32
+ *   flame_agg_reduce_sparse     values -- into an fp32 model; an absent element contributes nothing)
  *   flame_mx_quantize           (no reference counterpart: the model as MXFP8 / MXFP4 bytes for the
  *                               downlink, by flame_amd.mx.quantize's rule)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
@@ -410,6 +412,60 @@ int flame_agg_reduce_mxfp4(int client_dtype, int agg_dtype, unsigned flags, cons
                            int32_t n_segs, int64_t n_chunks, const void *const *clients,
                            const void *const *block_scales, int32_t n_clients, const float *rates32,
                            const float *scales32, void *stream);
+
+/*
+ * Top-k sparse updates into an fp32 aggregate (the contract is this project's own, DESIGN.md §2;
+ * flame_amd.sparse is the format).  An update holds, per tensor, nnz fp32 values and nnz int32 flat
+ * C-order element indices, strictly ascending, as flame_amd.sparse.topk writes them.  A round is two
+ * launches over the same tables: flame_sparse_index, then -- once its counters have come back all zero --
+ * flame_agg_reduce_sparse.
+ *   segs     : out / in = the fp32 aggregate (in may == out), numel < 2^31; chunk_begin counts chunks of
+ *              flame_sparse_chunk_elems() = 4,096 output elements (a wave owns a 1,024-element sub-range).
+ *              FLAME_SEG_UNALIGNED speaks of in and out; no other field is read.  The table lives in device
+ *              memory, so neither entry point can refuse a larger numel (flame_amd/engine.py does): int32
+ *              indices cannot address its elements past 2^31, and a direct caller gets wrong sums there,
+ *              not a refusal and not an access outside the tables.
+ *   indices  : device array [n_segs][n_clients] of device pointers to int32 [nnz], 4-byte aligned.
+ *   values   : device array [n_segs][n_clients] of device pointers to fp32 [nnz], 4-byte aligned.
+ *   nnz      : device int64 [n_segs][n_clients], entries per segment and client (0 is fine).
+ *   scratch / bounds : device buffer of >= flame_sparse_index_scratch_bytes(n_chunks, n_clients) bytes
+ *              (scratch_bytes / bounds_bytes: its size): per chunk, sub-range and client one int32 pair
+ *              [lo, hi), the client's entries whose index falls into the sub-range.  flame_sparse_index
+ *              writes it, flame_agg_reduce_sparse reads it.
+ * flame_sparse_index
+ *   bad      : device int64 [n_clients], ZEROED by the caller: per client, the entries (of all segments)
+ *              that are negative, >= numel, or not greater than their predecessor are added to it.  It
+ *              streams every index once and one lower_bound per (client, sub-range boundary); it reads
+ *              nothing outside [0, nnz) of any array, whatever the indices hold.
+ * flame_agg_reduce_sparse
+ *   agg_dtype: FLAME_F32.  flags: 0.
+ *   rates32  : device [n_clients]; scales32: device [n_clients] clip scales, or NULL for the plain round.
+ * Per element e, over the clients that hold e, in order, no FMA, denormals kept:
+ *   acc = in[e]                                                  (fp32)
+ *   t   = round_f32(v_i * rate_i)          with scales32: round_f32(round_f32(v_i * scale_i) * rate_i)
+ *   acc = round_f32(acc + t)
+ *   out[e] = acc
+ * An absent element contributes nothing, not a zero: the result is bit for bit what flame_agg_reduce (with
+ * scales32: flame_agg_reduce_scaled) gives for FLAME_F32 over the densified update, except that an
+ * untouched -0.0 stays -0.0.  Equal launches give equal bits (no floating-point atomic).  Memory safety
+ * does not rest on the indices: lo / hi are clamped to 0 <= lo <= hi <= nnz and an entry is applied only
+ * if (uint32)(idx - sub_base) < sub_len, so indices that flame_sparse_index would have counted give
+ * wrong sums, never an access outside the tables.
+ * Refusals, each before any HIP call and named in flame_last_error: an aggregate dtype other than
+ * FLAME_F32 is FLAME_ENOTSUP; FLAME_AGG_INIT_FIRST is FLAME_ENOTSUP; FLAME_AGG_SEG_RATES is
+ * FLAME_ENOTSUP; any other flag, a NULL table, rate or output array, a NULL or too small scratch / bounds
+ * buffer, n_segs <= 0, n_clients < 1 or n_chunks outside [1, 2^31) is FLAME_EINVAL.
+ * Device tables only (no kernel-argument variant).  Not launch branches of flame_launch_branches().
+ */
+int64_t flame_sparse_chunk_elems(void);
+int64_t flame_sparse_index_scratch_bytes(int64_t n_chunks, int32_t n_clients);
+int flame_sparse_index(const flame_segment *segs, int32_t n_segs, int64_t n_chunks, const void *const *indices,
+                       const int64_t *nnz, int32_t n_clients, int64_t *bad, void *scratch,
+                       int64_t scratch_bytes, void *stream);
+int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                            int64_t n_chunks, const void *const *indices, const void *const *values,
+                            const int64_t *nnz, int32_t n_clients, const float *rates32,
+                            const float *scales32, const void *bounds, int64_t bounds_bytes, void *stream);
 
 /*
  * The MX quantiser: fp32 / bf16 / f16 keys into MX element bytes and E8M0 scale bytes in one launch per
