@@ -23,6 +23,7 @@ FLAME_AGG_XCD_MAP = 4
 FLAME_FEDADAM, FLAME_FEDYOGI, FLAME_FEDADAGRAD = 0, 1, 2
 FLAME_OPT_STATE_ZERO = 1
 FLAME_OPT_XCD_MAP = 2
+FLAME_TOPK_BASE = 1                                            # flame_topk_select: every segment's m is its base
 FLAME_SEG_UNALIGNED = 1
 FLAME_SEG_CUR_IS_AVG = 2
 FLAME_HIER_TOP_ACCUM = 1
@@ -43,6 +44,7 @@ EXPORTS = (
     "flame_update_stats", "flame_update_stats_scratch_bytes", "flame_agg_reduce_scaled",
     "flame_agg_reduce_mixed", "flame_agg_reduce_mx", "flame_agg_reduce_mxfp4",
     "flame_mx_quantize", "flame_mx_quantize_chunk_elems",
+    "flame_topk_chunk_elems", "flame_topk_scratch_bytes", "flame_topk_select",
     "flame_sparse_chunk_elems", "flame_sparse_index_scratch_bytes", "flame_sparse_index", "flame_agg_reduce_sparse",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
@@ -114,6 +116,12 @@ def lib() -> ctypes.CDLL:
     L.flame_mx_quantize.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp]
     L.flame_mx_quantize_chunk_elems.restype = i64
     L.flame_mx_quantize_chunk_elems.argtypes = []
+    L.flame_topk_chunk_elems.restype = i64
+    L.flame_topk_chunk_elems.argtypes = []
+    L.flame_topk_scratch_bytes.restype = i64
+    L.flame_topk_scratch_bytes.argtypes = [i32, i64]
+    L.flame_topk_select.restype = ctypes.c_int
+    L.flame_topk_select.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, vp, i64, vp]
     L.flame_sparse_chunk_elems.restype = i64
     L.flame_sparse_chunk_elems.argtypes = []
     L.flame_sparse_index_scratch_bytes.restype = i64

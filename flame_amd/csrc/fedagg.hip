@@ -1557,6 +1557,382 @@ __global__ __launch_bounds__(kBlock) FLAME_MXQ_FN void mx_quantize_kernel(const 
     }
 }
 
+// ---------------------------------------------------------------- top-k selection
+// flame_topk_select: the k elements of largest magnitude of one long key, as ascending (int32 index, fp32
+// value) pairs ("the top-k selection"; flame_amd/sparse.py is the format).  The order is taken
+// on key(e) = bits(f32(x[e])) & 0x7FFFFFFF as an unsigned integer, so +-0 tie and a NaN ranks above inf.
+// With a base (fp32 only) x is d = x - base, one IEEE subtract, and a selected element's base becomes
+// base + d.  Phases, ordered by kernel boundaries alone (no workgroup ever waits for another):
+//   * three digit passes (topk_hist_kernel) over the key's 11 / 11 / 9 bits from the top.  A workgroup
+//     streams kTopkGroup chunks, bins the elements whose higher digits equal the prefix found so far into
+//     one LDS histogram per wave (integer ds_add) and flushes the non-zero bins to the segment's global
+//     histogram with integer atomics.
+//   * after each, topk_resolve_kernel (one workgroup per segment): a suffix scan of the 2,048 counters
+//     finds the bin of the k-th largest key and how many are still wanted inside it.  After the third the
+//     prefix is T, the k-th largest key, and `want` = k - #{key > T}, the ties to take.
+//   * topk_count_kernel writes each chunk's (#key > T, #key == T); topk_scan_kernel (one workgroup per
+//     segment, kBlock chunks per step, a carry between steps) turns them into exclusive prefixes.
+//   * topk_write_kernel re-reads the chunk and ranks its elements in index order: ballots and mbcnt inside
+//     a wave, wave offsets through LDS.  key > T is selected; key == T while its global tie rank < want.
+//     A selected element lands at gt_before + min(eq_before, want) + its rank inside the chunk.
+// Lane layout: a chunk is 4,096 elements, a wave owns 1,024 consecutive ones, and vector q of lane l holds
+// elements (q * 64 + l) * PER .. + PER - 1 of them (PER = 4 for fp32, 8 for bf16 / f16), so every wave load
+// is 1 KiB contiguous and index order is (wave, q, lane, j).  A ragged chunk or a FLAME_SEG_UNALIGNED
+// segment goes element by element with bounds; an element past numel is in no count.
+// Memory safety does not rest on the counts: a store goes to position < k and element < numel only.
+#define FLAME_TOPK_FN __attribute__((target("no-packed-fp32-ops")))
+constexpr int kTopkEPT = 16;                                   // elements per lane and chunk
+constexpr int64_t kTopkChunk = static_cast<int64_t>(kBlock) * kTopkEPT;
+constexpr int kTopkWaves = kBlock / kWaveLanes;
+constexpr int kTopkWaveElems = kWaveLanes * kTopkEPT;          // 1,024 consecutive elements per wave
+constexpr int kTopkBins = 2048;                                // counters per digit (the third uses 512)
+constexpr int kTopkDigits = 3;
+constexpr int64_t kTopkMaxSegChunks = (1ll << 31) / kTopkChunk; // a key of more chunks has 2^31 elements or more
+#ifndef FLAME_T_TOPK_GROUP
+#define FLAME_T_TOPK_GROUP 4
+#endif
+constexpr int kTopkGroup = FLAME_T_TOPK_GROUP;                 // chunks per workgroup of a digit pass
+struct TopkState { uint32_t prefix, want, k, pad; };           // per segment: digits found, count still wanted, k
+struct TopkCount { uint32_t gt, eq; };                         // per chunk: counts, then exclusive prefixes
+struct TopkScratch { uint32_t* hist; TopkState* state; TopkCount* counts; };
+static_assert(kTopkWaves == 4 && kTopkChunk == 4096, "four waves of 1,024 elements");
+
+inline __host__ __device__ TopkScratch topk_carve(void* scratch, int n_segs) {
+    TopkScratch c;
+    c.hist = static_cast<uint32_t*>(scratch);
+    c.state = reinterpret_cast<TopkState*>(c.hist + static_cast<int64_t>(n_segs) * kTopkDigits * kTopkBins);
+    c.counts = reinterpret_cast<TopkCount*>(c.state + n_segs);
+    return c;
+}
+
+FLAME_TOPK_FN __device__ __forceinline__ uint32_t topk_mbcnt(uint64_t m) {      // set bits of m below this lane
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+}
+FLAME_TOPK_FN __device__ __forceinline__ uint32_t topk_key(float v) { return mxq_bits(v) & 0x7FFFFFFFu; }
+
+// The lane's 16 values of the chunk that starts at element cb: v (the difference to the base when BASE),
+// b (the base's values), live (bit i: element i is inside the segment); returns the element of v[0].
+// Element i = q * PER + j of the lane is element  ret + q * 64 * PER + j  of the segment.
+template <int SD, bool BASE>
+FLAME_TOPK_FN __device__ __forceinline__ int64_t topk_load(const flame_segment& sg, int64_t cb, float (&v)[kTopkEPT],
+                                                           float (&b)[kTopkEPT], uint32_t& live) {
+    using T = typename Tr<SD>::T;
+    constexpr int PER = 16 / sizeof(T), NV = kTopkEPT / PER;
+    const int t = static_cast<int>(threadIdx.x);
+    const int64_t e0 = cb + static_cast<int64_t>(t / kWaveLanes) * kTopkWaveElems + static_cast<int64_t>(t % kWaveLanes) * PER;
+    const T* src = reinterpret_cast<const T*>(sg.in);
+    const float* base = reinterpret_cast<const float*>(sg.m);
+    const bool based = BASE && base != nullptr;
+    T x[NV][PER];
+    float y[NV][PER];
+    if (cb + kTopkChunk <= sg.numel && !(sg.flags & FLAME_SEG_UNALIGNED)) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) lane_load<true, true>(src + e0 + q * kWaveLanes * PER, x[q], e0, sg.numel);
+        if constexpr (BASE) {
+            if (based) {
+#pragma unroll
+                for (int q = 0; q < NV; ++q) lane_load<true>(base + e0 + q * kWaveLanes * PER, y[q], e0, sg.numel);
+            }
+        }
+        live = 0xFFFFu;
+    } else {
+        live = 0;
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            const int64_t e = e0 + q * kWaveLanes * PER;
+            lane_load<false>(src + e, x[q], e, sg.numel);
+            if constexpr (BASE) {
+                if (based) lane_load<false>(base + e, y[q], e, sg.numel);
+            }
+#pragma unroll
+            for (int j = 0; j < PER; ++j) live |= (e + j < sg.numel ? 1u : 0u) << (q * PER + j);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            float f = mxq_widen<SD>(x[q][j]);
+            b[q * PER + j] = 0.f;
+            if constexpr (BASE) {
+                if (based) {
+                    b[q * PER + j] = y[q][j];
+                    f = f - y[q][j];                              // one IEEE subtract (the build never contracts)
+                }
+            }
+            v[q * PER + j] = f;
+        }
+    }
+    return e0;
+}
+
+__global__ __launch_bounds__(kBlock) void topk_zero_kernel(uint32_t* __restrict__ p, int64_t n) {
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock)
+        p[i] = 0;
+}
+
+// One digit pass.  digit 0 / 1 / 2: key bits [30:20] / [19:9] / [8:0]; an element is binned when the bits
+// above the digit equal the segment's prefix (digit 0: every element).
+template <int SD, bool BASE>
+__global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_hist_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                       int64_t n_chunks, int digit, TopkScratch sc) {
+    __shared__ uint32_t lh[kTopkWaves][kTopkBins];
+    const int t = static_cast<int>(threadIdx.x), w = t / kWaveLanes;
+    const int above = digit == 0 ? 31 : digit == 1 ? 20 : 9, shift = digit == 0 ? 20 : digit == 1 ? 9 : 0;
+    const int bins = digit == 2 ? 512 : kTopkBins;
+    for (int i = t; i < kTopkWaves * kTopkBins; i += kBlock) (&lh[0][0])[i] = 0;
+    mxq_barrier();
+    // the bins of segment s leave for its global histogram, and the LDS copies are zero again
+    auto flush = [&](int s) FLAME_TOPK_FN {
+        mxq_barrier();
+        uint32_t* gh = sc.hist + (static_cast<int64_t>(s) * kTopkDigits + digit) * kTopkBins;
+        for (int i = t; i < bins; i += kBlock) {
+            uint32_t sum = 0;
+#pragma unroll
+            for (int u = 0; u < kTopkWaves; ++u) {
+                sum += lh[u][i];
+                lh[u][i] = 0;
+            }
+            if (sum) __hip_atomic_fetch_add(gh + i, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        mxq_barrier();
+    };
+    int cur = -1;
+    uint32_t prefix = 0;
+    for (int g = 0; g < kTopkGroup; ++g) {
+        const int64_t chunk = static_cast<int64_t>(blockIdx.x) * kTopkGroup + g;
+        if (chunk >= n_chunks) break;
+        const LaneChunk<flame_segment, kTopkEPT> lc(segs, n_segs, chunk);
+        const flame_segment sg = lc.sg;
+        const int64_t cb = (chunk - sg.chunk_begin) * kTopkChunk;
+        if (cb >= sg.numel) continue;                        // the idle chunk of a launch of empty segments
+        if (lc.s != cur) {
+            if (cur >= 0) flush(cur);
+            cur = lc.s;
+            prefix = digit ? sc.state[cur].prefix : 0u;
+        }
+        float v[kTopkEPT], b[kTopkEPT];
+        uint32_t live;
+        topk_load<SD, BASE>(sg, cb, v, b, live);
+#pragma unroll
+        for (int i = 0; i < kTopkEPT; ++i) {
+            const uint32_t key = topk_key(v[i]);
+            if (((live >> i) & 1u) && (key >> above) == prefix)
+                __hip_atomic_fetch_add(&lh[w][(key >> shift) & (bins - 1)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    if (cur >= 0) flush(cur);
+}
+
+// The digit's bin that holds the want-th largest of the elements counted, by a suffix scan: a lane sums
+// its 8 counters, the lane sums are scanned through LDS, and the one lane whose range holds the rank walks
+// its counters from the top.  digit 0 starts from k[s], clamped to [1, numel].
+__global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_resolve_kernel(const flame_segment* __restrict__ segs, int digit,
+                                                                          const int64_t* __restrict__ k, TopkScratch sc) {
+    constexpr int PERL = kTopkBins / kBlock;
+    __shared__ uint32_t sums[kBlock];
+    __shared__ uint32_t found[2];
+    const int s = blockIdx.x, t = static_cast<int>(threadIdx.x);
+    const int64_t numel = segs[s].numel;
+    const int bits = digit == 2 ? 9 : 11, bins = 1 << bits;
+    TopkState st = {0, 0, 0, 0};
+    if (digit == 0) {
+        const int64_t kk = k[s];
+        if (numel > 0 && numel < (1ll << 31)) st.k = static_cast<uint32_t>(kk < 1 ? 1 : kk > numel ? numel : kk);
+        st.want = st.k;
+    } else {
+        st = sc.state[s];
+    }
+    const uint32_t* gh = sc.hist + (static_cast<int64_t>(s) * kTopkDigits + digit) * kTopkBins;
+    uint32_t c[PERL], mine = 0;
+#pragma unroll
+    for (int j = 0; j < PERL; ++j) {
+        c[j] = t * PERL + j < bins ? gh[t * PERL + j] : 0u;
+        mine += c[j];
+    }
+    sums[t] = mine;
+    if (t < 2) found[t] = 0;
+    mxq_barrier();
+    for (int off = 1; off < kBlock; off <<= 1) {             // inclusive suffix sums of the lane sums
+        const uint32_t a = t + off < kBlock ? sums[t + off] : 0u;
+        mxq_barrier();
+        sums[t] += a;
+        mxq_barrier();
+    }
+    uint32_t higher = sums[t] - mine;                        // elements in the bins above this lane's
+    if (st.want > higher && st.want <= higher + mine) {
+#pragma unroll
+        for (int j = PERL - 1; j >= 0; --j) {
+            if (st.want > higher && st.want <= higher + c[j]) {
+                found[0] = static_cast<uint32_t>(t * PERL + j);
+                found[1] = st.want - higher;
+            }
+            higher += c[j];
+        }
+    }
+    mxq_barrier();
+    if (t == 0) {
+        st.prefix = (st.prefix << bits) | found[0];
+        st.want = found[1];                                  // 0 only where the counts do not hold k elements (k = 0)
+        sc.state[s] = st;
+    }
+}
+
+template <int SD, bool BASE>
+__global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_count_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                        int64_t n_chunks, TopkScratch sc) {
+    __shared__ uint32_t ws[kTopkWaves][2];
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, kTopkEPT> lc(segs, n_segs, chunk);
+    const flame_segment sg = lc.sg;
+    const int t = static_cast<int>(threadIdx.x);
+    const int64_t cb = (chunk - sg.chunk_begin) * kTopkChunk;
+    uint32_t gt = 0, eq = 0;                                 // wave-uniform
+    if (cb < sg.numel) {
+        const uint32_t T = sc.state[lc.s].prefix;
+        float v[kTopkEPT], b[kTopkEPT];
+        uint32_t live;
+        topk_load<SD, BASE>(sg, cb, v, b, live);
+#pragma unroll
+        for (int i = 0; i < kTopkEPT; ++i) {
+            const uint32_t key = topk_key(v[i]);
+            const bool on = (live >> i) & 1u;
+            gt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(on && key > T));
+            eq += __builtin_popcountll(__builtin_amdgcn_ballot_w64(on && key == T));
+        }
+    }
+    if (t % kWaveLanes == 0) {
+        ws[t / kWaveLanes][0] = gt;
+        ws[t / kWaveLanes][1] = eq;
+    }
+    mxq_barrier();
+    if (t == 0) {
+        TopkCount c = {0, 0};
+#pragma unroll
+        for (int u = 0; u < kTopkWaves; ++u) {
+            c.gt += ws[u][0];
+            c.eq += ws[u][1];
+        }
+        sc.counts[chunk] = c;
+    }
+}
+
+// A segment's chunk counts into exclusive prefixes, in place: kBlock chunks per step, a carry between steps.
+__global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_scan_kernel(const flame_segment* __restrict__ segs, int64_t n_chunks,
+                                                                       TopkScratch sc) {
+    __shared__ uint32_t sg_[kBlock], se_[kBlock];
+    const int s = blockIdx.x, t = static_cast<int>(threadIdx.x);
+    const int64_t numel = segs[s].numel, first = segs[s].chunk_begin;
+    int64_t nc = numel > 0 ? (numel + kTopkChunk - 1) / kTopkChunk : 0;
+    if (first < 0 || first >= n_chunks) nc = 0;
+    else if (nc > n_chunks - first) nc = n_chunks - first;   // whatever the table says, inside the counts
+    uint32_t carry_g = 0, carry_e = 0;
+    for (int64_t i0 = 0; i0 < nc; i0 += kBlock) {
+        const int64_t i = i0 + t;
+        TopkCount c = {0, 0};
+        if (i < nc) c = sc.counts[first + i];
+        sg_[t] = c.gt;
+        se_[t] = c.eq;
+        mxq_barrier();
+        for (int off = 1; off < kBlock; off <<= 1) {
+            const uint32_t a = t >= off ? sg_[t - off] : 0u, e = t >= off ? se_[t - off] : 0u;
+            mxq_barrier();
+            sg_[t] += a;
+            se_[t] += e;
+            mxq_barrier();
+        }
+        if (i < nc) sc.counts[first + i] = TopkCount{carry_g + sg_[t] - c.gt, carry_e + se_[t] - c.eq};
+        carry_g += sg_[kBlock - 1];
+        carry_e += se_[kBlock - 1];
+        mxq_barrier();
+    }
+}
+
+template <int SD, bool BASE>
+__global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_write_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                        int64_t n_chunks, TopkScratch sc) {
+    using T = typename Tr<SD>::T;
+    constexpr int PER = 16 / sizeof(T), NV = kTopkEPT / PER;
+    __shared__ uint32_t ws[kTopkWaves][2];
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, kTopkEPT> lc(segs, n_segs, chunk);
+    const flame_segment sg = lc.sg;
+    const int t = static_cast<int>(threadIdx.x), w = t / kWaveLanes;
+    const int64_t cb = (chunk - sg.chunk_begin) * kTopkChunk;
+    if (cb >= sg.numel) return;                              // the whole workgroup
+    const TopkState st = sc.state[lc.s];
+    const TopkCount before = sc.counts[chunk];
+    float v[kTopkEPT], b[kTopkEPT];
+    uint32_t live;
+    const int64_t e0 = topk_load<SD, BASE>(sg, cb, v, b, live);
+    uint32_t mg = 0, me = 0;                                 // bit i: element i has key > T / key == T
+    uint32_t pg[NV], pe[NV];                                 // such elements of the wave before the lane's vector q
+    uint32_t wg = 0, we = 0;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        uint32_t lg = 0, le = 0, tg = 0, te = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = q * PER + j;
+            const uint32_t key = topk_key(v[i]);
+            const bool on = (live >> i) & 1u, g = on && key > st.prefix, e = on && key == st.prefix;
+            mg |= (g ? 1u : 0u) << i;
+            me |= (e ? 1u : 0u) << i;
+            const uint64_t bg = __builtin_amdgcn_ballot_w64(g), be = __builtin_amdgcn_ballot_w64(e);
+            lg += topk_mbcnt(bg);
+            le += topk_mbcnt(be);
+            tg += __builtin_popcountll(bg);
+            te += __builtin_popcountll(be);
+        }
+        pg[q] = wg + lg;
+        pe[q] = we + le;
+        wg += tg;
+        we += te;
+    }
+    if (t % kWaveLanes == 0) {
+        ws[w][0] = wg;
+        ws[w][1] = we;
+    }
+    mxq_barrier();
+    uint32_t og = 0, oe = 0;                                 // such elements of the chunk's earlier waves
+#pragma unroll
+    for (int u = 0; u < kTopkWaves; ++u) {
+        if (u < w) {
+            og += ws[u][0];
+            oe += ws[u][1];
+        }
+    }
+    const uint32_t room = st.want > before.eq ? st.want - before.eq : 0u;       // ties this chunk may still take
+    const uint32_t first = before.gt + (before.eq < st.want ? before.eq : st.want);
+    float* val = reinterpret_cast<float*>(sg.out);
+    int32_t* idx = reinterpret_cast<int32_t*>(sg.cur_out);
+    float* base = reinterpret_cast<float*>(sg.m);
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        uint32_t cg = og + pg[q], ce = oe + pe[q];
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int i = q * PER + j;
+            const bool g = (mg >> i) & 1u, e = (me >> i) & 1u;
+            if (g || (e && ce < room)) {
+                const uint32_t pos = first + cg + (ce < room ? ce : room);
+                const int64_t el = e0 + q * kWaveLanes * PER + j;
+                if (pos < st.k) {
+                    st1(idx + pos, static_cast<int32_t>(el));
+                    st1(val + pos, v[i]);
+                    if constexpr (BASE) {
+                        if (base) st1(base + el, b[i] + v[i]);
+                    }
+                }
+            }
+            cg += g ? 1u : 0u;
+            ce += e ? 1u : 0u;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- trimmed mean / median
 // Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
 // the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
@@ -4770,6 +5146,56 @@ int flame_mx_quantize(int src_dtype, int fmt, unsigned flags, const flame_segmen
                                n_chunks);
         });
     });
+    return check_launch(who);
+}
+
+// The top-k selection: outside the launch-branch table, one instantiation of the three streaming kernels
+// per (source dtype, base).  One call enqueues the whole sequence on the caller's stream -- the histograms
+// cleared, three times (digit pass, resolve), count, scan, write -- and every refusal comes before the
+// first HIP call.  Nothing is assumed of the scratch's contents.
+int64_t flame_topk_chunk_elems(void) { return kTopkChunk; }
+
+int64_t flame_topk_scratch_bytes(int32_t n_segs, int64_t n_chunks) {
+    if (n_segs <= 0 || n_chunks <= 0 || n_chunks > 0x7FFFFFFFll) return 0;
+    return static_cast<int64_t>(n_segs) * (kTopkDigits * kTopkBins * static_cast<int64_t>(sizeof(uint32_t)) + static_cast<int64_t>(sizeof(TopkState)))
+           + n_chunks * static_cast<int64_t>(sizeof(TopkCount));
+}
+
+int flame_topk_select(int src_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                      const int64_t* k, void* scratch, int64_t scratch_bytes, void* stream) {
+    const char* const who = "flame_topk_select";
+    if (!is_f32_or_16(src_dtype))
+        return set_err(FLAME_ENOTSUP, "%s: source dtype %d is not supported (f32, bf16 or f16 only)", who, src_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (int rc = check_flags(who, flags, FLAME_TOPK_BASE)) return rc;
+    if ((flags & FLAME_TOPK_BASE) && src_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_TOPK_BASE with source dtype %d is not supported (an f32 source only)", who, src_dtype);
+    if (n_chunks > static_cast<int64_t>(n_segs) * kTopkMaxSegChunks)
+        return set_err(FLAME_ENOTSUP, "%s: %lld chunks in %d segments: a key of 2^31 elements or more (int32 indices address fewer)",
+                       who, (long long)n_chunks, n_segs);
+    if (!k) return set_err(FLAME_EINVAL, "%s: k array is NULL", who);
+    if (int rc = need_scratch(who, scratch, scratch_bytes, flame_topk_scratch_bytes(n_segs, n_chunks))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const TopkScratch sc = topk_carve(scratch, n_segs);
+    const dim3 block(kBlock), per_chunk(static_cast<unsigned>(n_chunks)), per_seg(static_cast<unsigned>(n_segs));
+    const dim3 grouped(static_cast<unsigned>((n_chunks + kTopkGroup - 1) / kTopkGroup));
+    const int64_t words = static_cast<int64_t>(n_segs) * kTopkDigits * kTopkBins;
+    hipLaunchKernelGGL(topk_zero_kernel, dim3(static_cast<unsigned>(words / kBlock < 1024 ? words / kBlock : 1024)), block, 0, st,
+                       sc.hist, words);
+    auto run = [&](auto sd, auto based) {
+        constexpr int SD = decltype(sd)::value;
+        constexpr bool BASE = decltype(based)::value != 0;
+        for (int digit = 0; digit < kTopkDigits; ++digit) {
+            hipLaunchKernelGGL((topk_hist_kernel<SD, BASE>), grouped, block, 0, st, segs, n_segs, n_chunks, digit, sc);
+            hipLaunchKernelGGL(topk_resolve_kernel, per_seg, block, 0, st, segs, digit, k, sc);
+        }
+        hipLaunchKernelGGL((topk_count_kernel<SD, BASE>), per_chunk, block, 0, st, segs, n_segs, n_chunks, sc);
+        hipLaunchKernelGGL(topk_scan_kernel, per_seg, block, 0, st, segs, n_chunks, sc);
+        hipLaunchKernelGGL((topk_write_kernel<SD, BASE>), per_chunk, block, 0, st, segs, n_segs, n_chunks, sc);
+    };
+    if (flags & FLAME_TOPK_BASE) run(ic<FLAME_F32>{}, ic<1>{});
+    else dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(src_dtype, [&](auto sd) { run(sd, ic<0>{}); });
     return check_launch(who);
 }
 

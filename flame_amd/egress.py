@@ -188,13 +188,33 @@ class MessageEncoder:
     ``message["weights"]`` leaves as ``engine.mx_quantize(weights, mx, mx_min_numel)`` of it, an
     :class:`flame_amd.mx.MXWeights` of 0.258 (fp8) or 0.133 (e2m1) of the fp32 bytes, quantised on the
     device by one flame_mx_quantize launch per source dtype.  The trainer reads
-    ``mx.dequantize(msg["weights"])``.  The caller's message and tensors are untouched."""
+    ``mx.dequantize(msg["weights"])``.  The caller's message and tensors are untouched.
 
-    def __init__(self, ring: int = 2, pin: bool = True, mx=None, mx_min_numel: int = 0):
+    ``sparse`` (a ratio in (0, 1]; default None: nothing changes; not together with ``mx``) is the sparse
+    downlink.  The first message, the first after :meth:`reset`, and any message whose weight keys, shapes or
+    dtypes differ from the held state send the weights as they are, and the encoder takes an fp32 device
+    clone of every fp32 key of at least ``sparse_min_numel`` elements as its base (the cost: one more fp32
+    copy of the model on the device).  Every later message sends ``engine.topk(weights, sparse,
+    sparse_min_numel, base=...)``: a :class:`flame_amd.sparse.SparseWeights` of the largest changes since the
+    base, which advances by exactly what was sent.  A trainer that applies every message with
+    ``sparse.apply_(model, msg["weights"])`` holds, in every sparsified key, bit for bit the encoder's base;
+    what has not been sent stays in ``weights - base`` and competes again in the next message.  Keys that are
+    not fp32, and keys under ``sparse_min_numel``, travel dense in every message.  A trainer that joins later
+    needs a ``reset()``."""
+
+    def __init__(self, ring: int = 2, pin: bool = True, mx=None, mx_min_numel: int = 0, sparse=None,
+                 sparse_min_numel: int = 0):
         if mx is not None:
             from . import mx as _mx
             if mx not in _mx.FORMATS:
                 raise ValueError(f"flame_amd.mx.quantize: fmt {mx!r} is not one of {sorted(_mx.FORMATS)}")
+        if sparse is not None:
+            if mx is not None:
+                raise ValueError("flame_amd.egress: mx and sparse are two downlinks; choose one")
+            if not 0.0 < sparse <= 1.0:
+                raise ValueError(f"flame_amd.sparse.topk: ratio {sparse!r} is not in (0, 1]")
+        self.sparse, self.sparse_min_numel = sparse, sparse_min_numel
+        self._base, self._held = None, None
         self.mx, self.mx_min_numel = mx, mx_min_numel
         self.ring = max(1, int(ring))
         self.pin = pin and torch.cuda.is_available()
@@ -215,6 +235,9 @@ class MessageEncoder:
             from . import engine
             message = dict(message)     # shallow: the caller's message keeps its own weights
             message["weights"] = engine.mx_quantize(message["weights"], self.mx, self.mx_min_numel)
+        if self.sparse is not None and isinstance(message, dict) and isinstance(message.get("weights"), dict):
+            message = dict(message)
+            message["weights"] = self._sparsified(message["weights"])
         # a fresh random mark per message: no bytes of the message itself can pass for a placeholder
         pieces, total = _layout(message, os.urandom(_MARK_LEN))
         buf = self._buffer(total)
@@ -240,6 +263,23 @@ class MessageEncoder:
     def encode_bytes(self, message: Any) -> bytes:
         return bytes(self.encode(message))
 
+    def reset(self) -> None:
+        """Forget the sparse downlink's base: the next message sends the weights as they are."""
+        self._base, self._held = None, None
+
+    def _sparsified(self, weights):
+        """The sparse downlink's weights: the dict itself while there is no base for its structure (the base is
+        taken), else the top-k of the change against the base (the base advances by it)."""
+        from . import engine
+        held = [(k, tuple(v.shape), v.dtype) if isinstance(v, torch.Tensor) else (k, None, None) for k, v in weights.items()]
+        if self._base is None or held != self._held:
+            device = engine._hip_device(None, "MessageEncoder(sparse=)", prefer=weights)
+            self._base = {k: v.detach().to(device, copy=True).contiguous() for k, v in weights.items()
+                          if isinstance(v, torch.Tensor) and v.dtype == torch.float32
+                          and v.numel() >= max(self.sparse_min_numel, 1)}
+            self._held = held
+            return weights
+        return engine.topk(weights, self.sparse, self.sparse_min_numel, base=self._base)
 
 _default = None
 

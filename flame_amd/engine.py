@@ -4,7 +4,7 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``synth_fill_``) need the native
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``topk``, ``synth_fill_``) need the native
 library and a HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
@@ -1420,6 +1420,131 @@ def mx_quantize(weights, fmt: str = "e4m3", min_numel: int = 0, *, device=None) 
                 out[k] = q.view(edt).view(v.shape)
     mx_quantize_(srcs, qs, [scales[k] for k in scales], fmt)
     return mx.MXWeights(out, scales, shapes=shapes)
+
+
+# ------------------------------------------------------------------ the top-k selection: sparsify on the device
+def topk_scratch_bytes(n_segs: int, n_chunks: int) -> int:
+    """Bytes of scratch one flame_topk_select call needs (histograms, per-segment state, chunk counts)."""
+    return int(N.lib().flame_topk_scratch_bytes(n_segs, n_chunks))
+
+
+def plan_topk(segs: Sequence[Seg], ks: Sequence[int], chunk: Optional[int] = None):
+    """[segments (10 words)] [k (int64 each)] -> (meta, n_chunks): the metadata block of one flame_topk_select
+    call (no GPU needed).  A segment's ``inp`` is the source, ``out`` the values, ``cur_out`` the indices,
+    ``m`` the base or 0; every segment starts a chunk.  FLAME_SEG_UNALIGNED speaks of the source and the base."""
+    if not segs or len(ks) != len(segs):
+        raise ValueError("flame_amd.plan_topk: one k per segment of a non-empty list")
+    b = _Block(chunk or int(N.lib().flame_topk_chunk_elems()))
+    head = np.zeros((len(segs), SEG_WORDS), dtype=np.uint64)
+    for i, (s, k) in enumerate(zip(segs, ks)):
+        if not 1 <= k <= s.numel:
+            raise ValueError(f"flame_amd.plan_topk: k = {k} is outside [1, {s.numel}]")
+        head[i] = (s.out, s.inp, 0, s.cur_out, s.m, 0, s.numel, b.chunk_begin(s.numel), b.unaligned((s.inp, s.m)), 0)
+    b.add("segs", head)
+    b.add("k", np.asarray(ks, dtype=np.int64))
+    return b.finish()
+
+
+def topk_(srcs: List[torch.Tensor], values: List[torch.Tensor], indices: List[torch.Tensor], ks: Sequence[int],
+          bases: Optional[List[torch.Tensor]] = None) -> None:
+    """values[s], indices[s] = the ``ks[s]`` elements of largest magnitude of srcs[s] as fp32 values and
+    ascending int32 flat indices, written in place (kernels: flame_topk_select; DESIGN.md §2 "the top-k
+    selection").  ``srcs`` are contiguous device tensors of f32 / bf16 / f16 on one device, ``values[s]`` /
+    ``indices[s]`` contiguous fp32 / int32 device tensors of ``ks[s]`` elements.  With ``bases`` (fp32 sources
+    only; contiguous fp32 device tensors of the sources' numels) the selection is taken on ``src - base``
+    and a selected element's base becomes ``base + (src - base)``.  One flame_topk_select call per source
+    dtype on torch's current stream; nothing is read back."""
+    if not (len(srcs) == len(values) == len(indices) == len(ks)) or (bases is not None and len(bases) != len(srcs)):
+        raise ValueError("flame_amd.topk_: one values tensor, one indices tensor and one k per source (and one base, if any)")
+    if not srcs:
+        return
+    device = srcs[0].device
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.topk_: tensors must live on the GPU (no CPU fallback)")
+    L = N.lib()
+    keep = []
+    for code, idx in by_dtype(range(len(srcs)), lambda s: srcs[s].dtype).items():
+        dt = srcs[idx[0]].dtype
+        if dt not in sparse.SPARSIFIED_FROM:
+            raise TypeError(f"flame_amd.topk_: {dt} keys are not sparsified (f32, bf16, f16 only)")
+        if bases is not None and dt != torch.float32:
+            raise TypeError(f"flame_amd.topk_: a base goes with an fp32 source, not {dt}")
+        segs = []
+        for s in idx:
+            n, k = srcs[s].numel(), int(ks[s])
+            if n >= sparse.INDEX_LIMIT:
+                raise ValueError(f"flame_amd.topk_: a key of {n} elements; int32 indices address fewer than 2^31")
+            if not 1 <= k <= n:
+                raise ValueError(f"flame_amd.topk_: k = {k} is outside [1, {n}]")
+            want = [(srcs[s], dt, n), (values[s], torch.float32, k), (indices[s], torch.int32, k)]
+            if bases is not None:
+                want.append((bases[s], torch.float32, n))
+            for t, tdt, tn in want:
+                if not (t.is_contiguous() and t.device == device):
+                    raise ValueError("flame_amd.topk_: contiguous tensors on one device")
+                if t.dtype != tdt or t.numel() != tn:
+                    raise ValueError(f"flame_amd.topk_: a key of {n} elements at k = {k} needs {tn} of {tdt} here, "
+                                     f"got {t.numel()} of {t.dtype}")
+            segs.append(Seg(n, out=values[s].data_ptr(), inp=srcs[s].data_ptr(), cur_out=indices[s].data_ptr(),
+                            m=bases[s].data_ptr() if bases is not None else 0))
+        kk = [int(ks[s]) for s in idx]
+        meta, n_chunks = plan_topk(segs, kk)
+        sbytes = topk_scratch_bytes(len(segs), n_chunks)
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
+        keep.append(scratch)
+        flags, off_k = (N.FLAME_TOPK_BASE if bases is not None else 0), len(segs) * SEG_WORDS * 8
+        # five reads of the source (and of the base), the pairs written, a selected element's base written
+        nbytes = sum(5 * sg.numel * (ITEMSIZE[code] + (4 if bases is not None else 0)) for sg in segs) \
+            + sum(kk) * (8 + (4 if bases is not None else 0))
+        _launch("flame_topk_select", nbytes, device, keep, meta,
+                lambda b: L.flame_topk_select(code, flags, b, len(segs), n_chunks, b + off_k, scratch.data_ptr(), sbytes,
+                                              _stream_ptr(device)))
+    _keepalive(keep + list(srcs) + list(values) + list(indices) + list(bases or ()), device)
+
+
+def topk(weights, ratio: float = 0.01, min_numel: int = 0, *, base=None, device=None) -> "sparse.SparseWeights":
+    """``sparse.topk(weights, ratio, min_numel)`` computed on the device: the same keys are sparsified (fp32 /
+    bf16 / f16 of at least ``max(min_numel, 1)`` elements) to ``k = min(n, max(1, ceil(ratio * n)))`` pairs,
+    among equal magnitudes at the threshold the lowest indices (DESIGN.md §2 "the top-k selection"); every
+    other key passes through as the object it is.  The outputs are new device tensors.  A host-resident or
+    strided source is staged to the device first.
+
+    With ``base`` (``{key: contiguous fp32 device tensor of the key's numel}``, one per selected key) only
+    fp32 keys are selected, the pairs are those of ``weights[key] - base[key]``, and the bases are updated in
+    place: ``base += sent`` where something was sent, not a bit elsewhere.  A 16-bit key with a base raises
+    TypeError."""
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError(f"flame_amd.sparse.topk: ratio {ratio!r} is not in (0, 1]")
+    device = _hip_device(device, "topk", prefer=weights)
+    out, indices, shapes = collections.OrderedDict(), {}, {}
+    srcs, vals, idxs, ks, bases = [], [], [], [], []
+    for key, v in weights.items():
+        out[key] = v
+        if not (isinstance(v, torch.Tensor) and v.dtype in sparse.SPARSIFIED_FROM and v.numel() >= max(min_numel, 1)):
+            continue
+        if base is not None:
+            if key in base and v.dtype != torch.float32:
+                raise TypeError(f"flame_amd.topk: key {key!r} is {v.dtype}; a base goes with an fp32 key")
+            if v.dtype != torch.float32:
+                continue
+            if key not in base:
+                raise KeyError(f"flame_amd.topk: no base for key {key!r}")
+            if not (base[key].is_contiguous() and base[key].dtype == torch.float32 and base[key].numel() == v.numel()):
+                raise ValueError(f"flame_amd.topk: the base of key {key!r} must be a contiguous fp32 tensor of {v.numel()} elements")
+            bases.append(base[key])
+        n = v.numel()
+        if n >= sparse.INDEX_LIMIT:
+            raise ValueError(f"flame_amd.sparse.topk: key {key!r} has {n} elements; int32 indices address fewer than 2^31")
+        k = min(n, max(1, math.ceil(ratio * n)))
+        srcs.append(_staged(v.detach(), device).view(-1))
+        out[key] = torch.empty(k, dtype=torch.float32, device=device)
+        indices[key] = torch.empty(k, dtype=torch.int32, device=device)
+        shapes[key] = tuple(v.shape)
+        vals.append(out[key])
+        idxs.append(indices[key])
+        ks.append(k)
+    topk_(srcs, vals, idxs, ks, [b.view(-1) for b in bases] if base is not None else None)
+    return sparse.SparseWeights(out, indices, shapes)
 
 
 # ------------------------------------------------------------------ dict-level helpers used by the optimizers

@@ -72,6 +72,25 @@ def topk(weights, ratio: float = 0.01, min_numel: int = 0) -> SparseWeights:
     return SparseWeights(out, indices, shapes)
 
 
+def apply_(model: dict, msg) -> dict:
+    """The trainer's side of the sparse downlink (``egress.MessageEncoder(sparse=)``): ``msg`` applied to
+    ``model`` in place.  A sparsified key of a :class:`SparseWeights` is the change since the last message:
+    ``flat[idx] = flat[idx] + v``, one fp32 add per sent element (the indices are unique).  Every other key,
+    and every key of a plain dict, is copied over.  Applied to every message in order, a sparsified key holds
+    bit for bit the encoder's base.  Returns ``model``."""
+    sent = msg.indices if isinstance(msg, SparseWeights) else {}
+    for k, v in msg.items():
+        if k in sent:
+            flat, idx = model[k].view(-1), sent[k].to(model[k].device).long()
+            flat[idx] = flat[idx] + v.to(flat.device)
+        elif isinstance(v, torch.Tensor) and isinstance(model.get(k), torch.Tensor) and model[k].shape == v.shape \
+                and model[k].dtype == v.dtype:
+            model[k].copy_(v)
+        else:
+            model[k] = v.clone() if isinstance(v, torch.Tensor) else v
+    return model
+
+
 def densify(w: SparseWeights) -> dict:
     """``{key: fp32 tensor}`` for the sparsified keys of ``w``, zeros where nothing was sent; every other
     key as it is."""

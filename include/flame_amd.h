@@ -46,6 +46,8 @@
  *   flame_agg_reduce_sparse     values -- into an fp32 model; an absent element contributes nothing)
  *   flame_mx_quantize           (no reference counterpart: the model as MXFP8 / MXFP4 bytes for the
  *                               downlink, by flame_amd.mx.quantize's rule)
+ *   flame_topk_select           (no reference counterpart: exact top-k by magnitude of each key as ascending
+ *                               index / value pairs, optionally of the change against a base it advances)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -500,6 +502,39 @@ int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment *
 int flame_mx_quantize(int src_dtype, int fmt, unsigned flags, const flame_segment *segs, int32_t n_segs,
                       int64_t n_chunks, void *stream);
 int64_t flame_mx_quantize_chunk_elems(void);
+
+/*
+ * The top-k selection: the k elements of largest magnitude of each key, as ascending (int32 index, fp32
+ * value) pairs -- the device-side producer of flame_amd.sparse's format and, with a base, the sparse
+ * downlink (flame_amd.egress.MessageEncoder(sparse=)).  DESIGN.md §2, "the top-k selection", is the contract.
+ *   src_dtype : FLAME_F32, FLAME_BF16 or FLAME_F16: every segment's in (a 16-bit source is widened exactly).
+ *   flags     : 0 or FLAME_TOPK_BASE (FLAME_F32 only): every segment's m is its base.
+ *   segs      : in = the source x, numel elements (numel < 2^31); out = the values, fp32 [k[s]]; cur_out =
+ *               the indices, int32 [k[s]]; m = the base, fp32 [numel] (read and written only under
+ *               FLAME_TOPK_BASE); chunk_begin counts chunks of flame_topk_chunk_elems() = 4,096 source
+ *               elements and every segment starts a chunk.  FLAME_SEG_UNALIGNED speaks of in and m (out and
+ *               cur_out are written element by element).  No other field is read.
+ *   k         : device int64 [n_segs], 1 <= k[s] <= numel (clamped into that range on the device).
+ *   scratch   : device buffer of >= flame_topk_scratch_bytes(n_segs, n_chunks) bytes, 8-byte aligned; its
+ *               contents on entry do not matter.
+ * Per segment, with d[e] = f32(x[e]) (under FLAME_TOPK_BASE f32(x[e] - m[e]), one IEEE subtract) and
+ * key(e) = bits(d[e]) & 0x7FFFFFFF compared as an unsigned integer (+-0 tie, a NaN ranks above inf):
+ *   T = the k-th largest key; selected = every e with key(e) > T and, of those with key(e) == T, the ones of
+ *   lowest index, k elements in all;  cur_out = the selected e ascending, out[j] = d[cur_out[j]];  under
+ *   FLAME_TOPK_BASE m[e] = f32(m[e] + d[e]) for the selected e, every other element of m untouched.
+ * One call enqueues ten launches, small and streaming, on `stream` (five reads of the source) and reads
+ * nothing back; no launch waits for another workgroup.  Equal calls give equal bits.
+ * Refusals, each before any HIP call and named in flame_last_error: a source dtype other than those above,
+ * FLAME_TOPK_BASE with a 16-bit source, or more than 2^19 chunks per segment on average (some key then has
+ * 2^31 elements or more) is FLAME_ENOTSUP; a NULL table, k or scratch, a scratch smaller than
+ * flame_topk_scratch_bytes says, n_segs <= 0, n_chunks outside [1, 2^31) or an unknown flag is FLAME_EINVAL.
+ * Device tables only.  Not a launch branch of flame_launch_branches().
+ */
+#define FLAME_TOPK_BASE 1u
+int64_t flame_topk_chunk_elems(void);
+int64_t flame_topk_scratch_bytes(int32_t n_segs, int64_t n_chunks);
+int flame_topk_select(int src_dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                      int64_t n_chunks, const int64_t *k, void *scratch, int64_t scratch_bytes, void *stream);
 
 /*
  * Coordinate-wise trimmed mean and, at its limit, the coordinate-wise median (Yin, Chen,
