@@ -1316,6 +1316,184 @@ __global__ __launch_bounds__(kBlock) FLAME_SPARSE_FN void agg_reduce_sparse_kern
     }
 }
 
+// ---------------------------------------------------------------- low-rank updates
+// flame_agg_reduce_lowrank: factor pairs U_c [m, r_c], V_c [r_c, n] (fp32 or bf16) into an fp32 aggregate,
+// out = in + sum_c (U_c * rate_c) V_c ("the low-rank contract"; flame_amd/lowrank.py is the
+// format).  The clients' ranks stack into one K dimension, so a key is ONE [m, K] x [K, n] product onto
+// the model, on the fp32 matrix cores: v_mfma_f32_32x32x2_f32.
+//   * Tiles.  A workgroup owns one 128 x 128 output tile; tiles are numbered across the segments
+//     (tile_begin), row-major inside one.  Wave w owns the 64 x 64 quarter (w >> 1, w & 1) as 2 x 2 blocks
+//     of 32 x 32: four 16-register accumulators, loaded from `in` (the instruction's C operand, so there
+//     is no separate add) and stored to `out` with the tile's edges masked.  Register v of lane l of a
+//     block is element (8 (v / 4) + 4 (l / 32) + v % 4, l % 32).
+//   * The K rows.  The host writes one flame_lowrank_row per k row of a segment: where row q of the
+//     client's U (column q) and V start, U's row stride, the rate, and whether a 4-element vector load
+//     may be used.  A client's rank is padded to the instruction's k = 2 and a segment's rows to whole
+//     stages with rows whose pointers are NULL: they are ZEROS in both operands (a zero against garbage
+//     is a NaN the moment the garbage is an inf).  The kernel never searches for its client.
+//   * Stages.  kLrStage = 16 k rows per stage go through LDS, double-buffered: stage s + 1's global
+//     loads are issued into registers before stage s's 8 k-steps (32 matrix instructions per wave) and
+//     written to the other buffer after them; one barrier per stage.  Lane t loads row i = t & 127 of the
+//     left factor for the 8 k rows of its half (t >> 7, wave-uniform): two quads, each one 4-element
+//     vector load where the row table allows it (a client's r_c values of one i are contiguous), else
+//     four scalar loads; the rate is folded in (one v_mul_f32, bf16 widened exactly first) and the values
+//     go to ldsA[k][i], k-major, so the A operand's lanes read 32 consecutive words.  The right factor's
+//     16 x 128 stage is 512 4-element vectors along j, two per lane, stored to ldsB[k][j] as they are.
+//     Rows i >= m and columns j >= n load zeros.
+//   * A k-step reads A[k = 2 s + l / 32][i = l % 32] and B[k][j = l % 32] for the wave's two row blocks
+//     and two column blocks (four ds_read_b32) and issues four v_mfma_f32_32x32x2_f32.
+// Offsets are 64-bit (i * n + j; a key may pass 2^32 elements).  No atomic; equal launches give equal bits.
+// Memory safety rests on the host's tables (m, n, ld and the pointers agree), as every pointer table's does.
+constexpr int kLrTile = FLAME_LOWRANK_TILE;             // output rows and columns per workgroup
+constexpr int kLrStage = FLAME_LOWRANK_STAGE;           // k rows per LDS stage
+constexpr int kLrQuad = 4;                              // k rows (left) / columns (right) per vector load
+static_assert(kBlock == 256 && kLrTile == 128 && kLrStage == 16, "2 x 2 waves of 64 x 64; 2 left quads and 2 right vectors per lane");
+static_assert(sizeof(flame_lowrank_segment) == 64 && sizeof(flame_lowrank_row) == 32, "the planner writes these as 8 and 4 words");
+using f16v = __attribute__((ext_vector_type(16))) float;
+
+template <int FD> struct LrIn;
+template <> struct LrIn<FLAME_F32> {
+    using T = float;
+    __device__ static __forceinline__ float w(T x) { return x; }
+    __device__ static __forceinline__ void ld4(const T* p, float (&x)[4]) {
+        const f4 v = *G(reinterpret_cast<const f4*>(p));
+        x[0] = v[0]; x[1] = v[1]; x[2] = v[2]; x[3] = v[3];
+    }
+};
+template <> struct LrIn<FLAME_BF16> {
+    using T = uint16_t;
+    using u2 = __attribute__((ext_vector_type(2))) uint32_t;
+    __device__ static __forceinline__ float w(T x) { return bf16_to_f32(x); }
+    __device__ static __forceinline__ void ld4(const T* p, float (&x)[4]) {
+        const u2 v = *G(reinterpret_cast<const u2*>(p));
+        x[0] = __uint_as_float(v[0] << 16); x[1] = __uint_as_float(v[0] & 0xFFFF0000u);
+        x[2] = __uint_as_float(v[1] << 16); x[3] = __uint_as_float(v[1] & 0xFFFF0000u);
+    }
+};
+
+template <int FD>
+__global__ __launch_bounds__(kBlock, 2) void agg_reduce_lowrank_kernel(const flame_lowrank_segment* __restrict__ segs, int n_segs,
+                                                                    const flame_lowrank_row* __restrict__ rows, int64_t n_tiles) {
+    using In = LrIn<FD>;
+    using T = typename In::T;
+    __shared__ __attribute__((aligned(16))) float ldsA[2][kLrStage][kLrTile];
+    __shared__ __attribute__((aligned(16))) float ldsB[2][kLrStage][kLrTile];
+    const int64_t tile = blockIdx.x;
+    if (tile >= n_tiles) return;
+    int s = 0;
+    for (int hi = n_segs - 1; s < hi;) {                 // largest s with tile_begin <= tile (workgroup-uniform)
+        const int mid = (s + hi + 1) >> 1;
+        if (segs[mid].tile_begin <= tile) s = mid; else hi = mid - 1;
+    }
+    const flame_lowrank_segment sg = segs[s];
+    const int64_t m = sg.m, n = sg.n;
+    if (m <= 0 || n <= 0) return;
+    const int64_t tiles_n = (n + kLrTile - 1) / kLrTile, tl = tile - sg.tile_begin;
+    const int64_t i0 = (tl / tiles_n) * kLrTile, j0 = (tl % tiles_n) * kLrTile;
+    if (i0 >= m) return;                                 // the whole workgroup, before any barrier
+    const int n_stages = static_cast<int>(sg.k_rows / kLrStage);
+    if (n_stages == 0 && sg.in == sg.out) return;        // every client has rank 0 here
+    const flame_lowrank_row* rw = rows + sg.k_begin;
+    const int t = static_cast<int>(threadIdx.x), l = t & 63, lr = l & 31, lh = l >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6), wi = (w >> 1) * 64, wj = (w & 1) * 64;
+    const float* in = reinterpret_cast<const float*>(sg.in);
+    float* out = reinterpret_cast<float*>(sg.out);
+
+    // the accumulators: the tile of `in`, zeros past the edges
+    f16v acc[2][2];
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int64_t i = i0 + wi + bi * 32 + 8 * (v / 4) + 4 * lh + (v % 4), j = j0 + wj + bj * 32 + lr;
+                acc[bi][bj][v] = (i < m && j < n) ? ld1(in + i * n + j) : 0.f;
+            }
+
+    // one stage's global loads into registers: a (left, rate folded in) and b (right)
+    const int ai = t & (kLrTile - 1), ah = __builtin_amdgcn_readfirstlane(t >> 7) * 8;
+    const int64_t gi = i0 + ai;
+    float a[2][kLrQuad], b[2][kLrQuad];
+    auto fetch = [&](int stage) {
+        const flame_lowrank_row* sr = rw + static_cast<int64_t>(stage) * kLrStage;
+#pragma unroll
+        for (int qd = 0; qd < 2; ++qd) {
+            const flame_lowrank_row* qr = sr + ah + qd * kLrQuad;
+            const flame_lowrank_row r0 = qr[0];
+            if ((r0.flags & FLAME_LOWRANK_ROW_UVEC) && r0.u && gi < m) {
+                In::ld4(reinterpret_cast<const T*>(r0.u) + gi * r0.ld, a[qd]);
+#pragma unroll
+                for (int e = 0; e < kLrQuad; ++e) a[qd][e] = __fmul_rn(a[qd][e], r0.rate);
+            } else {
+#pragma unroll
+                for (int e = 0; e < kLrQuad; ++e) {
+                    const flame_lowrank_row r = qr[e];
+                    a[qd][e] = (r.u && gi < m) ? __fmul_rn(In::w(ld1(reinterpret_cast<const T*>(r.u) + gi * r.ld)), r.rate) : 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int sl = t + x * kBlock;
+            const flame_lowrank_row r = sr[sl >> 5];
+            const int64_t gj = j0 + (sl & 31) * kLrQuad;
+            if (!r.v || gj >= n) {
+#pragma unroll
+                for (int e = 0; e < kLrQuad; ++e) b[x][e] = 0.f;
+            } else if ((r.flags & FLAME_LOWRANK_ROW_VVEC) && gj + kLrQuad <= n) {
+                In::ld4(reinterpret_cast<const T*>(r.v) + gj, b[x]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < kLrQuad; ++e) b[x][e] = (gj + e < n) ? In::w(ld1(reinterpret_cast<const T*>(r.v) + gj + e)) : 0.f;
+            }
+        }
+    };
+    auto put = [&](int buf) {
+#pragma unroll
+        for (int qd = 0; qd < 2; ++qd)
+#pragma unroll
+            for (int e = 0; e < kLrQuad; ++e) ldsA[buf][ah + qd * kLrQuad + e][ai] = a[qd][e];
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int sl = t + x * kBlock;
+            *reinterpret_cast<f4*>(&ldsB[buf][sl >> 5][(sl & 31) * kLrQuad]) = f4{b[x][0], b[x][1], b[x][2], b[x][3]};
+        }
+    };
+
+    if (n_stages > 0) {
+        fetch(0);
+        put(0);
+    }
+    __syncthreads();
+    for (int st = 0; st < n_stages; ++st) {
+        const int buf = st & 1;
+        if (st + 1 < n_stages) fetch(st + 1);
+#pragma unroll
+        for (int ks = 0; ks < kLrStage / 2; ++ks) {
+            const int k = 2 * ks + lh;
+            const float a0 = ldsA[buf][k][wi + lr], a1 = ldsA[buf][k][wi + 32 + lr];
+            const float b0 = ldsB[buf][k][wj + lr], b1 = ldsB[buf][k][wj + 32 + lr];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        if (st + 1 < n_stages) put(buf ^ 1);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int64_t i = i0 + wi + bi * 32 + 8 * (v / 4) + 4 * lh + (v % 4), j = j0 + wj + bj * 32 + lr;
+                if (i < m && j < n) st1(out + i * n + j, acc[bi][bj][v]);
+            }
+}
+
 // ---------------------------------------------------------------- MX downlink: the quantiser
 // flame_mx_quantize: fp32 / bf16 / f16 keys into OCP e4m3 / e5m2 bytes or packed e2m1 nibbles plus one
 // E8M0 scale byte per 32 elements, by flame_amd.mx.quantize's rule ("the MX quantiser"):
@@ -5121,6 +5299,32 @@ int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment* 
     else
         hipLaunchKernelGGL((agg_reduce_sparse_kernel<kSparseUnroll, false>), grid, block, 0, st, segs, n_segs, ix, vl, nnz,
                            n_clients, rates32, scales32, bd, n_chunks);
+    return check_launch(who);
+}
+
+// Low-rank updates into an fp32 aggregate: one launch over every factored key of a client group.  Outside
+// the launch-branch table, one instantiation per factor dtype; every refusal comes before the first HIP call.
+int64_t flame_lowrank_tile(void) { return kLrTile; }
+int64_t flame_lowrank_stage_rows(void) { return kLrStage; }
+
+int flame_agg_reduce_lowrank(int agg_dtype, int factor_dtype, unsigned flags, const flame_lowrank_segment* segs,
+                             int32_t n_segs, int64_t n_tiles, const flame_lowrank_row* rows, int64_t n_rows, void* stream) {
+    const char* const who = "flame_agg_reduce_lowrank";
+    if (agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: aggregate dtype %d is not supported (low-rank updates into f32 only)", who, agg_dtype);
+    if (factor_dtype != FLAME_F32 && factor_dtype != FLAME_BF16)
+        return set_err(FLAME_ENOTSUP, "%s: factor dtype %d is not supported (f32 or bf16 factors only)", who, factor_dtype);
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (!rows) return set_err(FLAME_EINVAL, "%s: row table is NULL", who);
+    if (n_rows < 0) return set_err(FLAME_EINVAL, "%s: n_rows < 0: %lld", who, (long long)n_rows);
+    if (n_tiles <= 0 || n_tiles >= (1ll << 32) / kBlock)     // a grid holds fewer than 2^32 lanes
+        return set_err(FLAME_EINVAL, "%s: n_tiles out of range: %lld", who, (long long)n_tiles);
+    if (int rc = check_flags(who, flags, 0)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_tiles)), block(kBlock);
+    dispatch<FLAME_F32, FLAME_BF16>(factor_dtype, [&](auto fd) {
+        hipLaunchKernelGGL((agg_reduce_lowrank_kernel<decltype(fd)::value>), grid, block, 0, st, segs, n_segs, rows, n_tiles);
+    });
     return check_launch(who);
 }
 

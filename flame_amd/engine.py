@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import mx, shm_lease, sparse
+from . import lowrank, mx, shm_lease, sparse
 
 DTYPE_CODE = {
     torch.float32: N.FLAME_F32, torch.bfloat16: N.FLAME_BF16, torch.float16: N.FLAME_F16,
@@ -493,12 +493,13 @@ def is_sparse(w) -> bool:
 
 
 def refuse_sparse(ws, who: str) -> None:
-    """TypeError when one of the updates ``ws`` is a sparse update: ``who`` does not take them (a values
-    tensor would otherwise pass for a dense fp32 key)."""
+    """TypeError when one of the updates ``ws`` is a sparse update or a low-rank one: ``who`` takes neither
+    (a values tensor would otherwise pass for a dense fp32 key)."""
     for w in ws:
         if w is not None and is_sparse(w):
             raise TypeError(f"flame_amd: {who} does not take sparse updates (a follow-up, not a silent slow path).  "
                             f"{SPARSE_SUPPORTED}")
+    refuse_lowrank(ws, who)
 
 
 def sparse_route(agg_dtype, ws, k, agg_shape) -> bool:
@@ -533,6 +534,69 @@ def sparse_route(agg_dtype, ws, k, agg_shape) -> bool:
         if v.numel() > numel or numel >= sparse.INDEX_LIMIT:
             raise TypeError(f"flame_amd: key {k!r}: {v.numel()} sparse entries into {numel} elements (strictly ascending int32 "
                             f"indices address at most min(numel, 2^31) of them).  {SPARSE_SUPPORTED}")
+    return True
+
+
+# low-rank updates (flame_amd.lowrank.LowRankWeights: a left factor [m, r] and a right factor [r, n] per
+# factored key), which one flame_agg_reduce_lowrank launch per factor dtype sums into an fp32 aggregate
+LOWRANK_SUPPORTED = ("Low-rank updates are supported as flame_amd.lowrank.LowRankWeights whose every entry holds the key "
+                     "as a left factor [m, r] with a right factor [r, n] of the same dtype (all torch.float32 or all "
+                     "torch.bfloat16 for a key; r may differ between updates and may be 0) in LowRankWeights.right and the "
+                     "aggregate's shape, (m, n) or (m, ...) with prod(...) == n, in LowRankWeights.shapes, summed into an "
+                     "fp32 aggregate by engine.accumulate without clip scales (FedAvg, FedProx and FedGFT with defer=False)")
+
+
+def is_lowrank(w) -> bool:
+    """``w`` is a low-rank update, a :class:`flame_amd.lowrank.LowRankWeights` (one isinstance, as :func:`is_mx`)."""
+    return isinstance(w, lowrank.LowRankWeights)
+
+
+def refuse_lowrank(ws, who: str) -> None:
+    """TypeError when one of the updates ``ws`` is a low-rank update: ``who`` does not take them (a left
+    factor would otherwise pass for a dense key of another shape)."""
+    for w in ws:
+        if w is not None and is_lowrank(w):
+            raise TypeError(f"flame_amd: {who} does not take low-rank updates (a follow-up, not a silent slow path).  "
+                            f"{LOWRANK_SUPPORTED}")
+
+
+def lowrank_route(agg_dtype, ws, k, agg_shape) -> bool:
+    """True when the updates ``ws`` (all carrying ``k``) hold key ``k`` as factor pairs that ONE
+    flame_agg_reduce_lowrank launch takes; False when none holds it factored (its present route); every
+    case in between is a TypeError."""
+    held = [is_lowrank(w) and k in w.right for w in ws]
+    if not any(held):
+        return False
+    if not all(held):
+        raise TypeError(f"flame_amd: key {k!r} is factored in update {held.index(True)} and dense in update "
+                        f"{held.index(False)}: per-key mixtures of low-rank and dense updates are not supported.  {LOWRANK_SUPPORTED}")
+    if agg_dtype != torch.float32:
+        raise TypeError(f"flame_amd: key {k!r}: low-rank updates into a {agg_dtype} aggregate are not supported.  {LOWRANK_SUPPORTED}")
+    if len(agg_shape) < 2:
+        raise TypeError(f"flame_amd: key {k!r}: low-rank updates into an aggregate of shape {tuple(agg_shape)} are not "
+                        f"supported (two dimensions or more).  {LOWRANK_SUPPORTED}")
+    m, n = lowrank.matrix_shape(agg_shape)
+    first = None
+    for w in ws:
+        u, v = w[k], w.right[k]
+        for name, f in (("left", u), ("right", v)):
+            if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.dtype not in lowrank.FACTOR_DTYPES:
+                raise TypeError(f"flame_amd: key {k!r}: the {name} low-rank factor is {getattr(f, 'dtype', type(f).__name__)} "
+                                f"{tuple(getattr(f, 'shape', ()))}, not 2-D torch.float32 or torch.bfloat16.  {LOWRANK_SUPPORTED}")
+        first = first or u.dtype
+        if u.dtype != v.dtype or u.dtype != first:
+            raise TypeError(f"flame_amd: key {k!r}: mixed low-rank factor dtypes ({first}, {u.dtype}, {v.dtype}) within a key "
+                            f"are not supported.  {LOWRANK_SUPPORTED}")
+        shape = w.shapes.get(k)
+        if shape is None:
+            raise TypeError(f"flame_amd: key {k!r} has low-rank factors without a LowRankWeights.shapes entry: the factors "
+                            f"do not say which tensor they multiply out to.  {LOWRANK_SUPPORTED}")
+        if tuple(shape) != tuple(agg_shape):
+            raise TypeError(f"flame_amd: key {k!r}: the low-rank update's logical shape {tuple(shape)} is not the aggregate's "
+                            f"{tuple(agg_shape)}.  {LOWRANK_SUPPORTED}")
+        if u.shape[0] != m or v.shape[1] != n or u.shape[1] != v.shape[0]:
+            raise TypeError(f"flame_amd: key {k!r}: the low-rank factors {tuple(u.shape)} x {tuple(v.shape)} disagree with "
+                            f"each other or with (m, n) = ({m}, {n}).  {LOWRANK_SUPPORTED}")
     return True
 
 
@@ -1641,6 +1705,10 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
             groups.setdefault(tuple(per_key[k]), []).append(k)
     any_mx = any(is_mx(w) for w, _ in entries)      # (a float8 tensor in a plain dict: _check_cast refuses it)
     any_sparse = any(is_sparse(w) for w, _ in entries)
+    any_lowrank = any(is_lowrank(w) for w, _ in entries)
+    if any_lowrank and scales is not None:
+        raise TypeError(f"flame_amd: clip scales (the update guard) do not take low-rank updates (a follow-up, not a silent "
+                        f"slow path).  {LOWRANK_SUPPORTED}")
     routed = []
     for cis, ks in groups.items():
         # MX keys: float8 elements + block scales of MXWeights under an fp32 aggregate (reduce_ groups
@@ -1648,9 +1716,11 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape) is not None}
         # sparse keys: fp32 values + int32 indices of SparseWeights under an fp32 aggregate (_SparseRound)
         spk = [k for k in ks if any_sparse and sparse_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape)]
+        # factored keys: factor pairs of LowRankWeights under an fp32 aggregate (_LowRankRound)
+        lrk = [k for k in ks if any_lowrank and lowrank_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape)]
         # same: one reduction launch per dtype pair -- the aggregate's own dtype, or bf16 / f16
         # updates under an fp32 aggregate (reduce_ groups those into flame_agg_reduce_mixed)
-        sps = set(spk)
+        sps = set(spk) | set(lrk)
         same = [k for k in ks if k not in sps and (k in mxk or (agg[k].dtype in DTYPE_CODE
                 and (all(entries[ci][0][k].dtype == agg[k].dtype for ci in cis)
                      or uplink16_dtype(agg[k].dtype, (entries[ci][0][k].dtype for ci in cis)) is not None)))]
@@ -1658,17 +1728,19 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
         for k in mixed:     # (a float8 tensor in a plain dict ends here)
             for ci in cis:
                 _check_cast(agg[k].dtype, weight_dtype(entries[ci][0], k))
-        routed.append((cis, mxk, same, mixed, spk))
+        routed.append((cis, mxk, same, mixed, spk, lrk))
     # every refusal of the round has been raised: the aggregate is untouched until here.  The sparse keys'
     # indices are validated on the device first (flame_sparse_index; its counters come back in one small
     # copy, a synchronisation point): a bad index raises ValueError before any reduction is launched
-    sparse_rounds = [_SparseRound(agg, spk, cis, entries, scales, device) if spk else None for cis, _, _, _, spk in routed]
+    sparse_rounds = [_SparseRound(agg, spk, cis, entries, scales, device) if spk else None for cis, _, _, _, spk, _ in routed]
     for sr in sparse_rounds:
         if sr is not None:
             sr.check()
-    for (cis, mxk, same, mixed, _), sr in zip(routed, sparse_rounds):
+    for (cis, mxk, same, mixed, _, lrk), sr in zip(routed, sparse_rounds):
         if sr is not None:
             sr.reduce()
+        if lrk:
+            _LowRankRound(agg, lrk, cis, entries, device).reduce()
         # with clip scales the float keys take the scaled kernel; integer keys are never scaled
         parts = [(same, None)] if scales is None else [
             ([k for k in same if agg[k].is_floating_point()], [scales[ci] for ci in cis]),
@@ -1773,6 +1845,95 @@ class _SparseRound:
         _keepalive(self.keep, device)
         for t in self.targets:
             t.writeback()
+
+
+def lowrank_tile() -> int:
+    """Output rows and columns per workgroup of flame_agg_reduce_lowrank, as compiled into the library."""
+    return int(N.lib().flame_lowrank_tile())
+
+
+def lowrank_stage_rows() -> int:
+    """k rows per stage of flame_agg_reduce_lowrank: a segment's rows are padded to a multiple."""
+    return int(N.lib().flame_lowrank_stage_rows())
+
+
+LOWRANK_ROW = np.dtype([("u", "<u8"), ("v", "<u8"), ("ld", "<i4"), ("flags", "<u4"), ("rate", "<f4"), ("pad", "<i4")])
+
+
+def plan_lowrank(segs, left, right, ranks, rates, esize: int, tile: Optional[int] = None, stage: Optional[int] = None):
+    """The metadata block flame_agg_reduce_lowrank reads (no GPU needed): ``[segments] [rows]``.  ``segs``:
+    ``[(out, in, m, n)]``; ``left`` / ``right`` / ``ranks``: ``[n_segs][n_clients]`` factor addresses and ranks;
+    ``rates``: one per client; ``esize``: bytes per factor element.  A client's rank is padded to an even
+    count and a segment's rows to whole stages with NULL rows; a rank-0 client has no row.  Returns ``(meta,
+    n_tiles, n_rows, byte offsets by name)``."""
+    tile, stage = tile or lowrank_tile(), stage or lowrank_stage_rows()
+    b, vec = _Block(1), 4 * esize
+    r32 = _f32(rates)
+    head, parts, k_begin = np.zeros((len(segs), N.LOWRANK_SEGMENT_INT64S), dtype=np.uint64), [], 0
+    for i, (out, inp, m, n) in enumerate(segs):
+        r = np.asarray(ranks[i], dtype=np.int64).reshape(-1)
+        if m < 0 or n < 0 or (r < 0).any() or len(r) != len(r32):
+            raise ValueError(f"plan_lowrank: segment {i}: negative size or rank, or not one rank per client (m={m}, n={n})")
+        pr = r + (r & 1)
+        total = int(pr.sum())
+        cid = np.repeat(np.arange(len(r)), pr)
+        q = np.arange(total) - np.repeat(np.cumsum(pr) - pr, pr)
+        real = q < r[cid]
+        rows = np.zeros(-(-total // stage) * stage, dtype=LOWRANK_ROW)
+        uq, vq = np.asarray(left[i], dtype=np.uint64)[cid], np.asarray(right[i], dtype=np.uint64)[cid]
+        rows["u"][:total] = np.where(real, uq + (q * esize).astype(np.uint64), 0)
+        rows["v"][:total] = np.where(real, vq + (q * n * esize).astype(np.uint64), 0)
+        rows["ld"][:total] = np.where(real, r[cid], 0)
+        rows["rate"][:total] = np.where(real, r32[cid], 0)
+        owner = np.full(len(rows), -1, dtype=np.int64)
+        owner[:total] = np.where(real, cid, -1)
+        quad = owner.reshape(-1, 4)
+        uvec = (quad[:, 0] >= 0) & (quad == quad[:, :1]).all(axis=1) & (rows["u"][::4] % vec == 0) & (rows["ld"][::4] % 4 == 0)
+        rows["flags"][::4] = np.where(uvec, N.FLAME_LOWRANK_ROW_UVEC, 0)
+        rows["flags"] |= np.where((rows["v"] != 0) & (rows["v"] % vec == 0) & (n % 4 == 0), N.FLAME_LOWRANK_ROW_VVEC, 0).astype(np.uint32)
+        head[i] = (out, inp, m, n, b.chunk_begin(-(-m // tile) * -(-n // tile)), k_begin, len(rows), 0)
+        parts.append(rows)
+        k_begin += len(rows)
+    b.add("segs", head)
+    b.add("rows", np.concatenate(parts).view(np.uint64) if k_begin else np.zeros(LOWRANK_ROW.itemsize // 8, dtype=np.uint64))
+    meta, _ = b.finish()
+    return meta, b.n_chunks, k_begin, b.offs
+
+
+class _LowRankRound:
+    """The factored keys ``keys`` of one client group of :func:`accumulate`: one flame_agg_reduce_lowrank
+    launch per factor dtype (normally one).  Host-resident or strided factors are copied to the device
+    once each; the aggregate goes through :class:`_Target`."""
+
+    def __init__(self, agg, keys, cis, entries, device):
+        self.agg, self.keys, self.device = agg, keys, device
+        self.ws, self.rates = [entries[ci][0] for ci in cis], [entries[ci][1] for ci in cis]
+
+    def reduce(self):
+        L, device = N.lib(), self.device
+        for code, ks in by_dtype(self.keys, lambda k: self.ws[0][k].dtype).items():
+            # an empty key, or one whose every client has rank 0, receives nothing: no staging, no segment
+            ks = [k for k in ks if self.agg[k].numel() and any(w[k].shape[1] for w in self.ws)]
+            if not ks:
+                continue
+            keep, esize = [], ITEMSIZE[code]
+            targets = [_Target(self.agg[k], device) for k in ks]
+            left = [[_staged(w[k], device) for w in self.ws] for k in ks]
+            right = [[_staged(w.right[k], device) for w in self.ws] for k in ks]
+            keep += [t.dev for t in targets] + [t for row in left + right for t in row]
+            shapes = [lowrank.matrix_shape(self.agg[k].shape) for k in ks]
+            meta, n_tiles, n_rows, o = plan_lowrank(
+                [(t.dev.data_ptr(), t.dev.data_ptr(), m, n) for t, (m, n) in zip(targets, shapes)],
+                [[t.data_ptr() for t in row] for row in left], [[t.data_ptr() for t in row] for row in right],
+                [[t.shape[1] for t in row] for row in left], self.rates, esize)
+            # every factor element once (the tiles' re-reads hit the cache), one fp32 read and write per element
+            nbytes = esize * sum(t.numel() for row in left + right for t in row) + 2 * ITEMSIZE[N.FLAME_F32] * sum(m * n for m, n in shapes)
+            _launch("flame_agg_reduce_lowrank", nbytes, device, keep, meta,
+                    lambda b: L.flame_agg_reduce_lowrank(N.FLAME_F32, code, 0, b + o["segs"], len(ks), n_tiles, b + o["rows"],
+                                                         n_rows, _stream_ptr(device)))
+            _keepalive(keep, device)
+            for t in targets:
+                t.writeback()
 
 
 def _prescaled(entries, scales, keys, device):

@@ -44,6 +44,9 @@
  *                               one E8M0 scale per 32 -- into an fp32 model; the same statements again)
  *   flame_sparse_index,         (no reference counterpart: top-k sparse updates -- int32 indices, fp32
  *   flame_agg_reduce_sparse     values -- into an fp32 model; an absent element contributes nothing)
+ *   flame_agg_reduce_lowrank    (no reference counterpart: low-rank updates -- factor pairs U [m, r], V [r, n],
+ *                               a LoRA adapter or a PowerSGD factorisation -- into an fp32 model: the exact
+ *                               aggregate sum_c rate_c U_c V_c as one product on the fp32 matrix cores)
  *   flame_mx_quantize           (no reference counterpart: the model as MXFP8 / MXFP4 bytes for the
  *                               downlink, by flame_amd.mx.quantize's rule)
  *   flame_topk_select           (no reference counterpart: exact top-k by magnitude of each key as ascending
@@ -468,6 +471,70 @@ int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment *
                             int64_t n_chunks, const void *const *indices, const void *const *values,
                             const int64_t *nnz, int32_t n_clients, const float *rates32,
                             const float *scales32, const void *bounds, int64_t bounds_bytes, void *stream);
+
+/*
+ * Low-rank updates into an fp32 aggregate (the contract is this project's own, DESIGN.md §2, "the low-rank
+ * contract"; flame_amd.lowrank is the format).  An update holds, per tensor, a left factor U [m, r] and a
+ * right factor V [r, n], both contiguous and both fp32 or both bf16; the tensor's logical shape is
+ * (m, n) or is flattened to it behind the first dimension.  One launch covers every factored tensor of a
+ * client group, on the fp32 matrix cores (v_mfma_f32_32x32x2_f32):
+ *   out[i,j] = in[i,j] + sum_c sum_q round_f32(U_c[i,q] * rate_c) * V_c[q,j]
+ * Clients in table order, q ascending; bf16 factors are widened exactly; the rate is folded into the
+ * left factor with one fp32 rounding; products and sums are accumulated in fp32 by the matrix
+ * instruction, starting from in[i,j].  The order of the additions inside one instruction is the
+ * hardware's: the result is NOT bitwise a sequential loop's.  It is deterministic (no atomic: equal
+ * launches give equal bits), exact whenever every partial sum is exactly representable, and within
+ * gamma_{K+1} (|in| + sum |round_f32(u * rate)| |v|) of the exact value otherwise, K the segment's k rows.
+ *   segs     : device array of flame_lowrank_segment.  out / in: the fp32 aggregate (in may == out), m x n
+ *              row-major, of ANY 4-byte alignment (it is accessed element by element).  tile_begin: the
+ *              prefix sum over previous segments of ceil(m / T) * ceil(n / T), T = flame_lowrank_tile() =
+ *              128; the grid covers n_tiles tiles.  k_begin: the segment's first entry of `rows`; k_rows:
+ *              how many it has, a multiple of flame_lowrank_stage_rows() = 16 (0: no client has a rank).
+ *   rows     : device array of flame_lowrank_row, n_rows in all: one per k row of a segment, the clients
+ *              in order and q ascending inside one.  u: &U_c[0, q]; v: &V_c[q, 0]; ld: r_c, U's row stride
+ *              in elements; rate: the client's rate as fp32.  A client's rows are padded to an even count
+ *              and a segment's to whole stages with rows whose u and v are NULL: zeros in both operands.
+ *              A client of rank 0 has no row.  flags: FLAME_LOWRANK_ROW_UVEC on the first row of an aligned
+ *              group of four (k_row % 4 == 0) says that the four are columns q .. q + 3 of ONE client and
+ *              that &U_c[i, q] is aligned to four elements for every i (u is, and ld % 4 == 0);
+ *              FLAME_LOWRANK_ROW_VVEC says that v is aligned to four elements and n % 4 == 0.  Without
+ *              a flag the elements are loaded one by one (4-byte aligned fp32 views, 2-byte aligned bf16).
+ *   factor_dtype: FLAME_F32 or FLAME_BF16, of every U and V of the launch.  agg_dtype: FLAME_F32.  flags: 0.
+ * Refusals, each before any HIP call and named in flame_last_error: an aggregate dtype other than FLAME_F32
+ * and a factor dtype other than FLAME_F32 / FLAME_BF16 are FLAME_ENOTSUP; any flag, a NULL segment or row
+ * table, n_segs <= 0, n_rows < 0 (with n_rows == 0 no row is read), and n_tiles outside [1, 2^24) (a grid holds fewer than 2^32 lanes) are
+ * FLAME_EINVAL.  m, n, ld and the ranks live in the device tables, which the entry point does not read:
+ * flame_amd.engine.plan_lowrank refuses negative ones.  Memory safety rests on those tables agreeing with
+ * the tensors.  Device tables only (no kernel-argument variant).  Not a launch branch of
+ * flame_launch_branches().
+ */
+#define FLAME_LOWRANK_TILE 128     /* output rows and columns per workgroup */
+#define FLAME_LOWRANK_STAGE 16     /* k rows per stage: k_rows is a multiple */
+#define FLAME_LOWRANK_ROW_UVEC 1u  /* rows k .. k + 3: one client's columns, 4-element vector loads of U */
+#define FLAME_LOWRANK_ROW_VVEC 2u  /* this row of V takes 4-element vector loads */
+typedef struct flame_lowrank_segment {
+    void *out;
+    const void *in;
+    int64_t m;
+    int64_t n;
+    int64_t tile_begin;
+    int64_t k_begin;
+    int64_t k_rows;
+    int64_t flags;            /* 0 */
+} flame_lowrank_segment;
+typedef struct flame_lowrank_row {
+    const void *u;
+    const void *v;
+    int32_t ld;
+    uint32_t flags;
+    float rate;
+    int32_t pad;
+} flame_lowrank_row;
+int64_t flame_lowrank_tile(void);
+int64_t flame_lowrank_stage_rows(void);
+int flame_agg_reduce_lowrank(int agg_dtype, int factor_dtype, unsigned flags, const flame_lowrank_segment *segs,
+                             int32_t n_segs, int64_t n_tiles, const flame_lowrank_row *rows, int64_t n_rows,
+                             void *stream);
 
 /*
  * The MX quantiser: fp32 / bf16 / f16 keys into MX element bytes and E8M0 scale bytes in one launch per
