@@ -55,3 +55,30 @@ def test_plan_tables_for_ragged_ranks():
     assert rows["flags"].tolist() == [VV, VV, VV, 0, UV | VV, VV, VV, VV, UV | VV, VV, VV, VV, VV, 0, 0, 0]
     with pytest.raises(ValueError, match="plan_lowrank"):
         engine.plan_lowrank([(64, 64, 5, 5)], left[:1], right[:1], [[1, -2, 0, 0]], rates, 4, tile=128, stage=16)
+
+
+def test_ragged_key_sets_are_one_launch_per_group_and_factor_dtype():
+    """Updates 0, 2 and 3 hold w (fp32 factors); all five hold u (bf16) and x (fp32): group (0, 2, 3) is one launch, group (0..4)
+    one per factor dtype in first-seen order, each over its own clients' rows and rates (the recorders of
+    tests/test_engine_launch_trace.py stand in for the library)."""
+    import uplink_cases as UC
+    from test_engine_launch_trace import CPU, STREAM
+    from test_uplink16_host import _calls, traced
+    shapes, carriers = {"w": (129, 127), "u": (31, 33), "x": (32, 32)}, {"w": (0, 2, 3)}
+    base, ups = UC.lowrank_case({"w": torch.float32, "u": torch.bfloat16, "x": torch.float32}, shapes=shapes, carriers=carriers)
+    agg, rates = {k: torch.from_numpy(v) for k, v in base.items()}, UC.rates_of(5)
+    ws = [UC.lowrank_weights(up, shapes) for up in ups]
+    with traced(lowrank_tile=lambda: 128, lowrank_stage_rows=lambda: 16) as tr:
+        engine.accumulate(agg, list(zip(ws, rates)), device=CPU)
+    calls = _calls(tr)
+    assert [c[0] for c in calls] == ["flame_agg_reduce_lowrank"] * 3
+    for (_, a), key, cis, code, tiles in zip(calls, "wux", (carriers["w"], range(5), range(5)), (N.FLAME_F32, N.FLAME_BF16, N.FLAME_F32), (2, 1, 1)):
+        ranks = [ws[c][key].shape[1] for c in cis]
+        k_rows = -(-sum(r + (r & 1) for r in ranks) // 16) * 16
+        assert a[:3] == [N.FLAME_F32, code, 0] and a[4:6] == [1, tiles] and a[7:] == [k_rows, STREAM]
+        words = tr.blocks[a[3]["block"]].numpy()
+        assert words[:N.LOWRANK_SEGMENT_INT64S].tolist() == [agg[key].data_ptr(), agg[key].data_ptr(), *shapes[key], 0, 0, k_rows, 0]
+        rows = words[a[6]["off"] // 8:][:k_rows * N.LOWRANK_ROW_INT64S].view(engine.LOWRANK_ROW)
+        real = rows[rows["u"] != 0]
+        want = [(ws[c][key].data_ptr() + q * ws[c][key].element_size(), float(np.float32(rates[c]))) for c, r in zip(cis, ranks) for q in range(r)]
+        assert list(zip(real["u"].tolist(), real["rate"].tolist())) == want, key

@@ -9,6 +9,7 @@ import torch
 from flame_amd import engine, sparse
 from flame_amd.optimizers import optimizer_provider
 
+import uplink_cases as UC
 from test_engine_launch_trace import CPU, STREAM
 from test_mx_host import _cache
 from test_uplink16_host import _calls, traced
@@ -106,3 +107,66 @@ def test_accumulate_is_an_index_launch_and_a_reduce_launch(scaled):
     nnz, elems = 3 * (1 + 41 + 83), sum(NUMELS.values())
     assert [e[1:] for e in tr.events if e[0] == "timed"][:2] == [["flame_sparse_index", 4 * nnz + sbytes],
                                                                  ["flame_agg_reduce_sparse", 8 * nnz + sbytes + 8 * elems]]
+
+
+# ---------------------------------------------------------------------------- client groups (tests/uplink_cases.py)
+def _bad_counts(tr, per_call):
+    """The recorder's flame_sparse_index, which also adds ``per_call[i]`` (one count per client of the group) to the ``bad``
+    array of its i-th call, as the kernel would: the array is the engine's own CPU tensor here."""
+    import ctypes
+    record, seen = tr.__getattr__("flame_sparse_index"), []
+
+    def call(*args):
+        counts = per_call[len(seen)]
+        seen.append(args)
+        assert args[5] == len(counts)
+        bad = (ctypes.c_int64 * len(counts)).from_address(args[6])
+        for i, c in enumerate(counts):
+            bad[i] += c
+        return record(*args)
+    tr.flame_sparse_index = call
+
+
+def test_key_set_groups_index_every_group_before_reducing_any():
+    """Two client groups, (0..5) with w sparse and b, n dense, (1, 3, 4) with v sparse: both index launches, then group by group
+    the gather and the group's dense keys (one launch per dtype)."""
+    model, ups = UC.sparse_group_case()
+    with traced(**SIZES) as tr:
+        engine.accumulate(model, list(zip(ups, UC.GROUP_RATES)), device=CPU)
+    calls = _calls(tr)
+    assert [c[0] for c in calls] == ["flame_sparse_index"] * 2 + ["flame_agg_reduce_sparse", "flame_agg_reduce", "flame_agg_reduce", "flame_agg_reduce_sparse"]
+    assert [(c[1][1], c[1][2], c[1][5]) for c in calls[:2]] == [(1, 2, 6), (1, 1, 3)]         # (segments, chunks, clients) per group
+    assert calls[2][1][2] == calls[0][1][0] and calls[5][1][2] == calls[1][1][0]              # each gather on its own group's block
+    for call, key, cis in ((calls[0], "w", range(6)), (calls[1], "v", UC.V_CARRIERS)):         # the group's own clients and rates
+        words, n = tr.blocks[call[1][0]["block"]].numpy(), len(cis)
+        table = lambda a: words[a["off"] // 8: a["off"] // 8 + n].tolist()                     # noqa: E731
+        assert table(call[1][3]) == [ups[c].indices[key].data_ptr() for c in cis] and table(call[1][4]) == [ups[c][key].numel() for c in cis]
+        rd = calls[2 if key == "w" else 5][1]
+        assert words[rd[9]["off"] // 8:].view(np.float32)[:n].tolist() == [float(np.float32(UC.GROUP_RATES[c])) for c in cis]
+
+
+def test_a_bad_index_in_a_later_group_names_the_entry_position():
+    """The second group's index launch reports one bad entry for its client 1, which is update 3 of the call: the message says 3,
+    and no reduction of either group has been launched."""
+    model, ups = UC.sparse_group_case(bad=True)
+    with traced(**SIZES) as tr:
+        _bad_counts(tr, [[0] * 6, [UC.bad_count(ups[c].indices["v"].numpy(), 1025) for c in UC.V_CARRIERS]])
+        with pytest.raises(ValueError, match=r"position\(s\) 3 \(1 bad entries\) hold"):
+            engine.accumulate(model, list(zip(ups, UC.GROUP_RATES)), device=CPU)
+    assert [c[0] for c in _calls(tr)] == ["flame_sparse_index"] * 2
+    with traced(**SIZES) as tr:          # several clients of several groups: every group is checked in order, the first bad one raises
+        _bad_counts(tr, [[0, 0, 2, 0, 0, 7], [4, 0, 0]])
+        with pytest.raises(ValueError, match=r"position\(s\) 2 \(2 bad entries\), 5 \(7 bad entries\) hold"):
+            engine.accumulate(model, list(zip(ups, UC.GROUP_RATES)), device=CPU)
+    assert [c[0] for c in _calls(tr)] == ["flame_sparse_index"] * 2
+
+
+def test_a_key_sparse_in_one_update_and_factored_in_another_is_refused():
+    """sparse_route sees the low-rank update as "dense": the message names the key and both updates, whichever comes first."""
+    from flame_amd import lowrank
+    agg = {"w": torch.full((40, 50), 0.5), "b": torch.full((7,), 0.5)}
+    sp = sparse.topk({"w": torch.ones(40, 50), "b": torch.ones(7)}, min_numel=8)
+    lr = lowrank.compress({"w": torch.ones(40, 50), "b": torch.ones(7)}, rank=2)
+    for entries, what in (([(sp, 0.5), (lr, 0.5)], "sparse in update 0 and dense in update 1"), ([(lr, 0.5), (sp, 0.25), (sp, 0.25)], "sparse in update 1 and dense in update 0")):
+        _refused(lambda: engine.accumulate(agg, entries, device=CPU), "'w'", what, "per-key mixtures of sparse and dense updates are not supported")
+    assert all(bool((v == 0.5).all()) for v in agg.values())
