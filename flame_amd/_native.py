@@ -28,6 +28,7 @@ FLAME_SEG_UNALIGNED = 1
 FLAME_SEG_CUR_IS_AVG = 2
 FLAME_LOWRANK_ROW_UVEC, FLAME_LOWRANK_ROW_VVEC = 1, 2          # flame_lowrank_row.flags
 LOWRANK_SEGMENT_INT64S, LOWRANK_ROW_INT64S = 8, 4              # sizeof(flame_lowrank_segment) / 8, sizeof(flame_lowrank_row) / 8
+LOWRANK_FACTOR_SEGMENT_INT64S = 16                             # sizeof(flame_lowrank_factor_segment) / 8
 FLAME_HIER_TOP_ACCUM = 1
 FLAME_HIER_TOP_APPLY = 2
 FLAME_HIER_MID_READONLY = 4
@@ -49,6 +50,7 @@ EXPORTS = (
     "flame_topk_chunk_elems", "flame_topk_scratch_bytes", "flame_topk_select",
     "flame_sparse_chunk_elems", "flame_sparse_index_scratch_bytes", "flame_sparse_index", "flame_agg_reduce_sparse",
     "flame_lowrank_tile", "flame_lowrank_stage_rows", "flame_agg_reduce_lowrank",
+    "flame_lowrank_factor_scratch_bytes", "flame_lowrank_factor",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
     "flame_update_gram", "flame_update_gram_scratch_bytes", "flame_update_gram_max_clients",
     "flame_agg_trimmed", "flame_agg_trimmed_max_k", "flame_agg_select", "flame_agg_select_max_clients", "flame_fedopt_reduce_adapt", "flame_fedopt_reduce_adapt_argmeta", "flame_fedopt_chain", "flame_fedopt_reduce_adapt_f64", "flame_fedopt_chain_f64", "flame_fedbuff_scale_add", "flame_hier_fedbuff", "flame_hier_fedbuff_argmeta",
@@ -139,6 +141,10 @@ def lib() -> ctypes.CDLL:
     L.flame_lowrank_stage_rows.argtypes = []
     L.flame_agg_reduce_lowrank.restype = ctypes.c_int
     L.flame_agg_reduce_lowrank.argtypes = [ctypes.c_int, ctypes.c_int, u32, vp, i32, i64, vp, i64, vp]
+    L.flame_lowrank_factor_scratch_bytes.restype = i64
+    L.flame_lowrank_factor_scratch_bytes.argtypes = [i64, i64]
+    L.flame_lowrank_factor.restype = ctypes.c_int
+    L.flame_lowrank_factor.argtypes = [u32, vp, i32, i32, i64, i64, i64, vp, i64, vp]
     L.flame_agg_trimmed.restype = ctypes.c_int
     L.flame_agg_trimmed.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, i32, i32, vp]
     L.flame_agg_trimmed_max_k.restype = ctypes.c_int

@@ -1494,6 +1494,327 @@ __global__ __launch_bounds__(kBlock, 2) void agg_reduce_lowrank_kernel(const fla
             }
 }
 
+// ---------------------------------------------------------------- low-rank downlink: the factoriser
+// flame_lowrank_factor: one PowerSGD power iteration per key on D = w - base ("the low-rank
+// downlink"): P = D Q, U = orth(P), V = U^T D.  D is never stored: both products stream w and base and
+// subtract in registers.  The operand and C/D lane maps are the uplink kernel's above: lane l feeds
+// A[l % 32][l / 32] and B[l / 32][l % 32]; register v of lane l is C[8 (v / 4) + 4 (l / 32) + v % 4][l % 32].
+//
+// lowrank_project_kernel<TRANS>: a tall-skinny product with r padded to the instruction's 32 columns.
+//   * Work items.  A workgroup owns one tile of kLfTile = 128 rows (TRANS: columns) of the key and one
+//     split [k0, k1) of the summed dimension K (the columns; TRANS: the rows), kper elements long, a
+//     multiple of the stage.  Items are numbered across the segments (p_begin / v_begin), tile-major.
+//   * The panel (Q, element (k, j) at q[k q_ldk + j q_ldj]; TRANS: U [m, r]) goes through LDS in stages of
+//     kLfStage = 64 k rows of 32 columns, double-buffered as the uplink's stages are: stage s + 1's global
+//     loads are issued into registers before stage s's matrix instructions and written to the other
+//     buffer after them; one barrier per stage.  Columns j >= r and rows k >= k1 are zeros.
+//   * The stream.  A lane loads 8 four-element vectors of w and 8 of base per stage (element by element
+//     with bounds where the key is not 16-byte aligned with n % 4 == 0, or at its ragged edge) and
+//     subtracts: 32 values of D that are matrix operands as they lie, no pass through LDS.
+//       P = D Q:   wave w owns rows 32 w .. 32 w + 31 of the tile, lane (i = l % 32, h = l / 32) holds
+//                  D[i][kb + 32 a + 16 h + 4 f + c] (a < 2, f < 4: 64 contiguous bytes, a row's two lanes
+//                  one 128-byte line) and feeds it as A; B is panel[32 a + 16 h + 4 f + c][l % 32].  Which
+//                  k a half-wave multiplies is free as long as A and B agree.  One accumulator.
+//       V = U^T D: the same row-major stream with rows as K.  Wave w takes rows kb + 16 w .. + 15 of the
+//                  stage; lane (j = l % 32, h) holds D[kb + 16 w + 2 e + h][x0 + 4 j + c] (e < 8; a
+//                  half-wave reads 512 contiguous bytes) and feeds it as B of accumulator c, whose column
+//                  l % 32 is the key's column x0 + 4 (l % 32) + c; A is panel[16 w + 2 e + h][l % 32] = U[i][q].
+//                  The transposed product comes from which lane index feeds which operand, not from a
+//                  transposing pass.  The four waves' accumulators are added in wave order through LDS.
+//   * Each item stores its 128 x 32 partial, [tile element][q], to scratch; lowrank_project_finish_kernel
+//     adds an output tile's partials in split order (as gram_finish_kernel does) and stores P into u, or
+//     V into v, rows / columns past the key's edge and q >= r not stored.  No atomic; equal launches give equal bits.
+// Element offsets of the stream are 32-bit (m n < 2^31, refused otherwise).
+constexpr int kLfTile = FLAME_LOWRANK_TILE;                 // rows (TRANS: columns) of the key per work item
+constexpr int kLfStage = 64;                                // k rows of the panel per LDS stage
+constexpr int kLfPad = 32;                                  // r padded to the instruction's columns
+constexpr int kLfPart = kLfTile * kLfPad;                   // fp32 values of one partial
+static_assert(kBlock == 256 && kLfTile == 4 * 32 && kLfStage * kLfPad == 8 * kBlock && kLfStage == 4 * 16,
+              "4 waves of 32 rows or 16 k rows; 8 panel values per lane");
+static_assert(sizeof(flame_lowrank_factor_segment) == 128, "the planner writes it as 16 words");
+
+template <bool TRANS>
+__device__ __forceinline__ int lf_segment(const flame_lowrank_factor_segment* __restrict__ segs, int n_segs, int64_t item) {
+    int s = 0;
+    for (int hi = n_segs - 1; s < hi;) {                 // largest s whose first item <= item (workgroup-uniform)
+        const int mid = (s + hi + 1) >> 1;
+        if ((TRANS ? segs[mid].v_begin : segs[mid].p_begin) <= item) s = mid; else hi = mid - 1;
+    }
+    return s;
+}
+
+template <bool TRANS>
+__global__ __launch_bounds__(kBlock, 2) void lowrank_project_kernel(const flame_lowrank_factor_segment* __restrict__ segs, int n_segs,
+                                                                    int rank, int64_t n_items, float* __restrict__ scratch) {
+    __shared__ __attribute__((aligned(16))) float pan[2][kLfStage][kLfPad];
+    __shared__ float red[TRANS ? 64 : 1][kWaveLanes];
+    const int64_t item = blockIdx.x;
+    if (item >= n_items) return;
+    const flame_lowrank_factor_segment* sp = segs + lf_segment<TRANS>(segs, n_segs, item);    // field by field: no copy on the stack
+    const int64_t m = sp->m, n = sp->n, ldu = sp->r;
+    const int64_t splits = TRANS ? sp->v_splits : sp->p_splits, kper = TRANS ? sp->v_kper : sp->p_kper;
+    if (m <= 0 || n <= 0 || splits <= 0 || kper <= 0) return;
+    const int r = static_cast<int>(ldu < rank ? (ldu < 0 ? 0 : ldu) : rank);
+    const int64_t local = item - (TRANS ? sp->v_begin : sp->p_begin);
+    const int64_t K = TRANS ? m : n, X = TRANS ? n : m;
+    const int64_t x0 = (local / splits) * kLfTile, k0 = (local % splits) * kper;
+    if (x0 >= X) return;                                 // the whole workgroup, before any barrier
+    const int64_t k1 = k0 + kper < K ? k0 + kper : K;
+    const int n_stages = k1 > k0 ? static_cast<int>((k1 - k0 + kLfStage - 1) / kLfStage) : 0;
+    const int t = static_cast<int>(threadIdx.x), l = t & 63, lr = l & 31, lh = l >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const float* wp = reinterpret_cast<const float*>(sp->w);
+    const float* bp = reinterpret_cast<const float*>(sp->base);
+    const float* pp = reinterpret_cast<const float*>(TRANS ? sp->u : sp->q);
+    const int64_t pk = TRANS ? ldu : sp->q_ldk, pj = TRANS ? 1 : sp->q_ldj;
+    const bool vec = ((reinterpret_cast<uintptr_t>(wp) | reinterpret_cast<uintptr_t>(bp)) & 15) == 0 && (n & 3) == 0;
+
+    // one stage's panel values into registers: 8 per lane, along whichever index is contiguous in memory
+    float pq[8];
+    // (every lambda is forced inline: called from two places, one left as a call would put the arrays on the stack)
+    auto pan_at = [&](int x, int& kk, int& jj) __attribute__((always_inline)) {
+        const int idx = t + x * kBlock;
+        if (pj == 1) { kk = idx >> 5; jj = idx & 31; } else { jj = idx >> 6; kk = idx & 63; }
+    };
+    auto fetch_pan = [&](int stage) __attribute__((always_inline)) {
+        const int64_t kb = k0 + static_cast<int64_t>(stage) * kLfStage;
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            int kk, jj;
+            pan_at(x, kk, jj);
+            pq[x] = (kb + kk < k1 && jj < r) ? ld1(pp + (kb + kk) * pk + jj * pj) : 0.f;
+        }
+    };
+    auto put_pan = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+            int kk, jj;
+            pan_at(x, kk, jj);
+            pan[buf][kk][jj] = pq[x];
+        }
+    };
+
+    // one stage's stream into registers: wv - bv is D
+    f4 wv[8], bv[8], d[8];       // (whole vectors assigned once per branch: element-wise writes from three branches went to the stack)
+    auto fetch_d = [&](int stage) __attribute__((always_inline)) {
+        const int64_t kb = k0 + static_cast<int64_t>(stage) * kLfStage;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t i = TRANS ? kb + 16 * w + 2 * u + lh : x0 + 32 * w + lr;
+            const int64_t j = TRANS ? x0 + 4 * lr : kb + 32 * (u >> 2) + 16 * lh + 4 * (u & 3);
+            const int64_t ilim = TRANS ? k1 : m, jlim = TRANS ? n : k1;
+            const uint32_t off = static_cast<uint32_t>(i * n + j);
+            f4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+            if (i < ilim && j < jlim) {
+                if (vec && j + 4 <= jlim) {
+                    a = *G(reinterpret_cast<const f4*>(wp + off));
+                    b = *G(reinterpret_cast<const f4*>(bp + off));
+                } else {
+                    const float a0 = ld1(wp + off), b0 = ld1(bp + off);
+                    const float a1 = j + 1 < jlim ? ld1(wp + off + 1) : 0.f, b1 = j + 1 < jlim ? ld1(bp + off + 1) : 0.f;
+                    const float a2 = j + 2 < jlim ? ld1(wp + off + 2) : 0.f, b2 = j + 2 < jlim ? ld1(bp + off + 2) : 0.f;
+                    const float a3 = j + 3 < jlim ? ld1(wp + off + 3) : 0.f, b3 = j + 3 < jlim ? ld1(bp + off + 3) : 0.f;
+                    a = f4{a0, a1, a2, a3};
+                    b = f4{b0, b1, b2, b3};
+                }
+            }
+            wv[u] = a;
+            bv[u] = b;
+        }
+    };
+    auto subtract = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) d[u] = wv[u] - bv[u];          // one IEEE subtract per element
+    };
+
+    constexpr int NACC = TRANS ? 4 : 1;
+    f16v acc[NACC];
+#pragma unroll
+    for (int c = 0; c < NACC; ++c)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[c][v] = 0.f;
+
+    if (n_stages > 0) {
+        fetch_pan(0);
+        fetch_d(0);
+        put_pan(0);
+        subtract();
+    }
+    __syncthreads();
+    for (int st = 0; st < n_stages; ++st) {
+        const int buf = st & 1;
+        if (st + 1 < n_stages) {
+            fetch_pan(st + 1);
+            fetch_d(st + 1);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if constexpr (TRANS) {
+                const float a = pan[buf][16 * w + 2 * u + lh][lr];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[u][c], acc[c], 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float b = pan[buf][32 * (u >> 2) + 16 * lh + 4 * (u & 3) + c][lr];
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(d[u][c], b, acc[0], 0, 0, 0);
+                }
+            }
+        }
+        if (st + 1 < n_stages) {
+            put_pan(buf ^ 1);
+            subtract();
+        }
+        __syncthreads();
+    }
+
+    float* part = scratch + item * kLfPart;
+    if constexpr (TRANS) {
+        for (int ww = 1; ww < kBlock / kWaveLanes; ++ww) {       // wave 0 += wave ww, in wave order
+            if (w == ww) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) red[c * 16 + v][l] = acc[c][v];
+            }
+            __syncthreads();
+            if (w == 0) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) acc[c][v] = __fadd_rn(acc[c][v], red[c * 16 + v][l]);
+            }
+            __syncthreads();
+        }
+        if (w != 0) return;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) st1(part + (4 * lr + c) * kLfPad + 8 * (v / 4) + 4 * lh + (v % 4), acc[c][v]);
+    } else {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) st1(part + (32 * w + 8 * (v / 4) + 4 * lh + (v % 4)) * kLfPad + lr, acc[0][v]);
+    }
+}
+
+// u (TRANS: v) = an output tile's partials added in split order.  The workgroup of a tile's first item does
+// the tile, every other one leaves at once; lane t owns values t + 256 s of the tile's 4,096.
+template <bool TRANS>
+__global__ __launch_bounds__(kBlock) void lowrank_project_finish_kernel(const flame_lowrank_factor_segment* __restrict__ segs, int n_segs,
+                                                                       int rank, int64_t n_items, const float* __restrict__ scratch) {
+    const int64_t item = blockIdx.x;
+    if (item >= n_items) return;
+    const flame_lowrank_factor_segment sg = segs[lf_segment<TRANS>(segs, n_segs, item)];
+    const int64_t splits = TRANS ? sg.v_splits : sg.p_splits;
+    if (sg.m <= 0 || sg.n <= 0 || splits <= 0) return;
+    const int64_t local = item - (TRANS ? sg.v_begin : sg.p_begin);
+    if (local % splits != 0) return;
+    const int r = static_cast<int>(sg.r < rank ? (sg.r < 0 ? 0 : sg.r) : rank);
+    const int64_t X = TRANS ? sg.n : sg.m, x0 = (local / splits) * kLfTile;
+    const int64_t sx = TRANS ? 1 : sg.r, sy = TRANS ? sg.n : 1;
+    float* out = reinterpret_cast<float*>(TRANS ? sg.v : sg.u);
+    const float* part = scratch + item * kLfPart + threadIdx.x;
+    float sum[kLfPart / kBlock];
+#pragma unroll
+    for (int s = 0; s < kLfPart / kBlock; ++s) sum[s] = 0.f;
+    for (int64_t p = 0; p < splits; ++p)
+#pragma unroll
+        for (int s = 0; s < kLfPart / kBlock; ++s) sum[s] = __fadd_rn(sum[s], ld1(part + p * kLfPart + s * kBlock));
+#pragma unroll
+    for (int s = 0; s < kLfPart / kBlock; ++s) {
+        const int e = static_cast<int>(threadIdx.x) + s * kBlock, y = e & 31;
+        const int64_t x = x0 + (e >> 5);
+        if (x < X && y < r) st1(out + x * sx + y * sy, sum[s]);
+    }
+}
+
+// lowrank_orth_kernel: u [m, r] = orth(u) in place, one workgroup per key: modified Gram-Schmidt with one
+// re-orthogonalisation, every dot and norm in fp64 (DESIGN.md §2 says why not Cholesky-QR).  Column c:
+//   (a) t_k = u_k . p_c for k < c;  p_c = f32(p_c - sum_k (t_k / s_k) u_k), s_k = u_k . u_k of the STORED u_k;
+//   (b) u_c = f32(p_c / |p_c|), or a column of zeros when |p_c|^2 is 0;
+//   (c) t_k = u_c . p_k for k > c;  p_k = f32(p_k - (t_k / s_c) u_c).
+// Dividing by s, not assuming it 1, makes each projection exact for the fp32 u that is stored: what is
+// left of a column that was nearly parallel to an earlier one is orthogonal to it to fp32 roundoff of ITSELF.
+// Lane t owns rows t, t + 256, ..: it alone reads and writes them, so only the sums cross lanes -- by
+// xor-shuffles inside a wave and the four wave sums added in wave order: a fixed order.
+constexpr int kLfWaves = kBlock / kWaveLanes;
+__global__ __launch_bounds__(kBlock) void lowrank_orth_kernel(const flame_lowrank_factor_segment* __restrict__ segs, int rank) {
+    __shared__ double wsum[kLfWaves][kLfPad];
+    __shared__ double coef[kLfPad], sq[kLfPad];
+    const flame_lowrank_factor_segment sg = segs[blockIdx.x];
+    const int64_t m = sg.m, ld = sg.r;
+    const int r = static_cast<int>(sg.r < rank ? (sg.r < 0 ? 0 : sg.r) : rank);
+    if (m <= 0 || sg.n <= 0 || r <= 0) return;          // the whole workgroup
+    float* u = reinterpret_cast<float*>(sg.u);
+    const int t = static_cast<int>(threadIdx.x);
+    // wsum[.][k] = the waves' sums of x[k], lo <= k < hi (every index a constant: x stays in registers)
+    auto block_sums = [&](double (&x)[kLfPad], int lo, int hi) {
+#pragma unroll
+        for (int k = 0; k < kLfPad; ++k)
+            if (k >= lo && k < hi) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) x[k] = __dadd_rn(x[k], __shfl_xor(x[k], o, kWaveLanes));
+            }
+        __syncthreads();                                 // the previous sums have been read
+        if ((t & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < kLfPad; ++k)
+                if (k >= lo && k < hi) wsum[t >> 6][k] = x[k];
+        }
+        __syncthreads();
+    };
+    auto total = [&](int k) { return __dadd_rn(__dadd_rn(__dadd_rn(wsum[0][k], wsum[1][k]), wsum[2][k]), wsum[3][k]); };
+    double dot[kLfPad];
+    for (int c = 0; c < r; ++c) {
+        if (c > 0) {                                     // (a)
+#pragma unroll
+            for (int k = 0; k < kLfPad; ++k) dot[k] = 0.0;
+            for (int64_t i = t; i < m; i += kBlock) {
+                const double pc = static_cast<double>(ld1(u + i * ld + c));
+#pragma unroll
+                for (int k = 0; k < kLfPad; ++k)
+                    if (k < c) dot[k] = __fma_rn(static_cast<double>(ld1(u + i * ld + k)), pc, dot[k]);
+            }
+            block_sums(dot, 0, c);
+            if (t < c) coef[t] = sq[t] > 0.0 ? total(t) / sq[t] : 0.0;
+            __syncthreads();
+        }
+        dot[0] = 0.0;
+        for (int64_t i = t; i < m; i += kBlock) {
+            double x = static_cast<double>(ld1(u + i * ld + c));
+            for (int k = 0; k < c; ++k) x = __fma_rn(-coef[k], static_cast<double>(ld1(u + i * ld + k)), x);
+            const float xf = static_cast<float>(x);
+            st1(u + i * ld + c, xf);
+            dot[0] = __fma_rn(static_cast<double>(xf), static_cast<double>(xf), dot[0]);
+        }
+        block_sums(dot, 0, 1);
+        const double nn = total(0);
+        const double inv = nn > 0.0 ? 1.0 / __dsqrt_rn(nn) : 0.0;
+        // (b), and (c)'s dots in the same pass: dot[c] is s_c
+#pragma unroll
+        for (int k = 0; k < kLfPad; ++k) dot[k] = 0.0;
+        for (int64_t i = t; i < m; i += kBlock) {
+            const float uf = static_cast<float>(static_cast<double>(ld1(u + i * ld + c)) * inv);
+            st1(u + i * ld + c, uf);
+            const double ud = static_cast<double>(uf);
+#pragma unroll
+            for (int k = 0; k < kLfPad; ++k)
+                if (k >= c && k < r) dot[k] = __fma_rn(ud, k == c ? ud : static_cast<double>(ld1(u + i * ld + k)), dot[k]);
+        }
+        block_sums(dot, c, r);
+        if (t >= c && t < r) {
+            const double ss = total(c);
+            if (t == c) sq[c] = ss; else coef[t] = ss > 0.0 ? total(t) / ss : 0.0;
+        }
+        __syncthreads();
+        for (int64_t i = t; i < m; i += kBlock) {        // (c)
+            const double uc = static_cast<double>(ld1(u + i * ld + c));
+            for (int k = c + 1; k < r; ++k)
+                st1(u + i * ld + k, static_cast<float>(__fma_rn(-coef[k], uc, static_cast<double>(ld1(u + i * ld + k)))));
+        }
+    }
+}
+
 // ---------------------------------------------------------------- MX downlink: the quantiser
 // flame_mx_quantize: fp32 / bf16 / f16 keys into OCP e4m3 / e5m2 bytes or packed e2m1 nibbles plus one
 // E8M0 scale byte per 32 elements, by flame_amd.mx.quantize's rule ("the MX quantiser"):
@@ -5325,6 +5646,41 @@ int flame_agg_reduce_lowrank(int agg_dtype, int factor_dtype, unsigned flags, co
     dispatch<FLAME_F32, FLAME_BF16>(factor_dtype, [&](auto fd) {
         hipLaunchKernelGGL((agg_reduce_lowrank_kernel<decltype(fd)::value>), grid, block, 0, st, segs, n_segs, rows, n_tiles);
     });
+    return check_launch(who);
+}
+
+// The low-rank factoriser (the downlink): outside the launch-branch table.  One call enqueues P = D Q
+// (project, finish), U = orth(P) and V = U^T D (project, finish) in order on the caller's stream; the
+// second pass reuses the first's scratch.  Every refusal comes before the first HIP call.
+constexpr int64_t kLfMaxItems = 1ll << 24;               // a grid holds fewer than 2^32 lanes
+
+int64_t flame_lowrank_factor_scratch_bytes(int64_t p_items, int64_t v_items) {
+    if (p_items <= 0 || v_items <= 0 || p_items >= kLfMaxItems || v_items >= kLfMaxItems) return 0;
+    return (p_items > v_items ? p_items : v_items) * kLfPart * static_cast<int64_t>(sizeof(float));
+}
+
+int flame_lowrank_factor(unsigned flags, const flame_lowrank_factor_segment* segs, int32_t n_segs, int32_t rank,
+                         int64_t max_elems, int64_t p_items, int64_t v_items, void* scratch, int64_t scratch_bytes,
+                         void* stream) {
+    const char* const who = "flame_lowrank_factor";
+    if (!segs || n_segs <= 0) return set_err(FLAME_EINVAL, "%s: segment table is NULL or n_segs <= 0", who);
+    if (rank < 1 || rank > kLfPad) return set_err(FLAME_EINVAL, "%s: rank %d is outside 1 .. %d", who, rank, kLfPad);
+    if (max_elems < 0) return set_err(FLAME_EINVAL, "%s: max_elems < 0: %lld", who, (long long)max_elems);
+    if (max_elems >= (1ll << 31))
+        return set_err(FLAME_ENOTSUP, "%s: a key of %lld elements: 2^31 or more are not factorised (32-bit offsets)", who,
+                       (long long)max_elems);
+    if (p_items <= 0 || p_items >= kLfMaxItems || v_items <= 0 || v_items >= kLfMaxItems)
+        return set_err(FLAME_EINVAL, "%s: work items out of range: %lld and %lld", who, (long long)p_items, (long long)v_items);
+    if (int rc = check_flags(who, flags, 0)) return rc;
+    if (int rc = need_scratch(who, scratch, scratch_bytes, flame_lowrank_factor_scratch_bytes(p_items, v_items))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* sc = static_cast<float*>(scratch);
+    const dim3 block(kBlock), pgrid(static_cast<unsigned>(p_items)), vgrid(static_cast<unsigned>(v_items));
+    hipLaunchKernelGGL((lowrank_project_kernel<false>), pgrid, block, 0, st, segs, n_segs, rank, p_items, sc);
+    hipLaunchKernelGGL((lowrank_project_finish_kernel<false>), pgrid, block, 0, st, segs, n_segs, rank, p_items, sc);
+    hipLaunchKernelGGL(lowrank_orth_kernel, dim3(static_cast<unsigned>(n_segs)), block, 0, st, segs, rank);
+    hipLaunchKernelGGL((lowrank_project_kernel<true>), vgrid, block, 0, st, segs, n_segs, rank, v_items, sc);
+    hipLaunchKernelGGL((lowrank_project_finish_kernel<true>), vgrid, block, 0, st, segs, n_segs, rank, v_items, sc);
     return check_launch(who);
 }
 

@@ -200,10 +200,22 @@ class MessageEncoder:
     ``sparse.apply_(model, msg["weights"])`` holds, in every sparsified key, bit for bit the encoder's base;
     what has not been sent stays in ``weights - base`` and competes again in the next message.  Keys that are
     not fp32, and keys under ``sparse_min_numel``, travel dense in every message.  A trainer that joins later
-    needs a ``reset()``."""
+    needs a ``reset()``.
+
+    ``lowrank`` (a rank in 1 .. 32; default None: nothing changes; not together with ``mx`` or ``sparse``) is the
+    low-rank downlink, of the same shape: the first message, the first after :meth:`reset` and any message whose
+    structure changes are dense, and the encoder takes its fp32 device base there, of every fp32 key of two
+    dimensions or more and at least ``lowrank_min_numel`` elements.  Every later message sends
+    ``engine.lowrank_factor(weights, lowrank, lowrank_min_numel, base=..., q=..., seed=lowrank_seed)``: a
+    :class:`flame_amd.lowrank.LowRankWeights` of one PowerSGD power iteration on the change since the base,
+    warm-started from the previous message's right factor (kept per key); the base advances by ``U V`` and what
+    the factors miss competes again in the next message.  The trainer applies ``lowrank.apply_(model,
+    msg["weights"])``.  Unlike the sparse downlink, its copy is NOT bit for bit the base: ``U @ V`` on its CPU and
+    on the matrix cores round differently, within the any-order fp32 bound of a length-r dot product per message,
+    and the differences add up until the next dense message.  :meth:`reset` is the way to re-synchronise."""
 
     def __init__(self, ring: int = 2, pin: bool = True, mx=None, mx_min_numel: int = 0, sparse=None,
-                 sparse_min_numel: int = 0):
+                 sparse_min_numel: int = 0, lowrank=None, lowrank_min_numel: int = 0, lowrank_seed: int = 0):
         if mx is not None:
             from . import mx as _mx
             if mx not in _mx.FORMATS:
@@ -213,8 +225,14 @@ class MessageEncoder:
                 raise ValueError("flame_amd.egress: mx and sparse are two downlinks; choose one")
             if not 0.0 < sparse <= 1.0:
                 raise ValueError(f"flame_amd.sparse.topk: ratio {sparse!r} is not in (0, 1]")
+        if lowrank is not None:
+            if mx is not None or sparse is not None:
+                raise ValueError("flame_amd.egress: mx, sparse and lowrank are three downlinks; choose one")
+            if isinstance(lowrank, bool) or not isinstance(lowrank, int) or not 1 <= lowrank <= 32:
+                raise ValueError(f"flame_amd.lowrank_factor: rank {lowrank!r} is not an integer in 1 .. 32")
         self.sparse, self.sparse_min_numel = sparse, sparse_min_numel
-        self._base, self._held = None, None
+        self.lowrank, self.lowrank_min_numel, self.lowrank_seed = lowrank, lowrank_min_numel, lowrank_seed
+        self._base, self._held, self._q = None, None, None
         self.mx, self.mx_min_numel = mx, mx_min_numel
         self.ring = max(1, int(ring))
         self.pin = pin and torch.cuda.is_available()
@@ -238,6 +256,9 @@ class MessageEncoder:
         if self.sparse is not None and isinstance(message, dict) and isinstance(message.get("weights"), dict):
             message = dict(message)
             message["weights"] = self._sparsified(message["weights"])
+        if self.lowrank is not None and isinstance(message, dict) and isinstance(message.get("weights"), dict):
+            message = dict(message)
+            message["weights"] = self._factorised(message["weights"])
         # a fresh random mark per message: no bytes of the message itself can pass for a placeholder
         pieces, total = _layout(message, os.urandom(_MARK_LEN))
         buf = self._buffer(total)
@@ -264,22 +285,41 @@ class MessageEncoder:
         return bytes(self.encode(message))
 
     def reset(self) -> None:
-        """Forget the sparse downlink's base: the next message sends the weights as they are."""
-        self._base, self._held = None, None
+        """Forget the sparse or low-rank downlink's base (and the low-rank downlink's right factors): the next
+        message sends the weights as they are."""
+        self._base, self._held, self._q = None, None, None
+
+    def _rebased(self, weights, who, min_numel, min_dim) -> bool:
+        """True when there is no base for the structure of ``weights``: an fp32 device clone of every fp32 key of
+        at least ``min_dim`` dimensions and ``min_numel`` elements is taken as the base."""
+        from . import engine
+        held = [(k, tuple(v.shape), v.dtype) if isinstance(v, torch.Tensor) else (k, None, None) for k, v in weights.items()]
+        if self._base is not None and held == self._held:
+            return False
+        device = engine._hip_device(None, who, prefer=weights)
+        self._base = {k: v.detach().to(device, copy=True).contiguous() for k, v in weights.items()
+                      if isinstance(v, torch.Tensor) and v.dtype == torch.float32 and v.dim() >= min_dim
+                      and v.numel() >= max(min_numel, 1)}
+        self._held, self._q = held, None
+        return True
 
     def _sparsified(self, weights):
         """The sparse downlink's weights: the dict itself while there is no base for its structure (the base is
         taken), else the top-k of the change against the base (the base advances by it)."""
         from . import engine
-        held = [(k, tuple(v.shape), v.dtype) if isinstance(v, torch.Tensor) else (k, None, None) for k, v in weights.items()]
-        if self._base is None or held != self._held:
-            device = engine._hip_device(None, "MessageEncoder(sparse=)", prefer=weights)
-            self._base = {k: v.detach().to(device, copy=True).contiguous() for k, v in weights.items()
-                          if isinstance(v, torch.Tensor) and v.dtype == torch.float32
-                          and v.numel() >= max(self.sparse_min_numel, 1)}
-            self._held = held
+        if self._rebased(weights, "MessageEncoder(sparse=)", self.sparse_min_numel, 0):
             return weights
         return engine.topk(weights, self.sparse, self.sparse_min_numel, base=self._base)
+
+    def _factorised(self, weights):
+        """The low-rank downlink's weights: the dict itself while there is no base for its structure, else the
+        factors of the change against the base (the base advances by their product; Q is kept per key)."""
+        from . import engine
+        if self._rebased(weights, "MessageEncoder(lowrank=)", self.lowrank_min_numel, 2):
+            return weights
+        sent, self._q = engine.lowrank_factor(weights, self.lowrank, self.lowrank_min_numel, base=self._base, q=self._q,
+                                              seed=self.lowrank_seed)
+        return sent
 
 _default = None
 

@@ -4,7 +4,7 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``topk``, ``synth_fill_``) need the native
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``topk``, ``lowrank_factor``, ``synth_fill_``) need the native
 library and a HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
@@ -1609,6 +1609,137 @@ def topk(weights, ratio: float = 0.01, min_numel: int = 0, *, base=None, device=
         ks.append(k)
     topk_(srcs, vals, idxs, ks, [b.view(-1) for b in bases] if base is not None else None)
     return sparse.SparseWeights(out, indices, shapes)
+
+
+# ------------------------------------------------------------------ the low-rank factoriser: PowerSGD on the device
+LOWRANK_FACTOR_MAX_RANK = 32     # the matrix instruction's columns
+LOWRANK_FACTOR_ITEMS = 512       # work items a pass aims at: two workgroups on each of 256 CUs
+LOWRANK_FACTOR_STAGE = 64        # K elements per LDS stage: a split is a multiple
+
+
+def plan_lowrank_factor(segs, tile: Optional[int] = None, items: Optional[int] = None):
+    """The metadata block flame_lowrank_factor reads (no GPU needed).  ``segs``: ``[(w, base, q, u, v, m, n, r,
+    q_ldk, q_ldj)]``, addresses and element counts.  Each pass (K = n, then K = m) splits K so that its tiles
+    times its splits come near ``items`` over the whole call, a function of the shapes alone.  Returns
+    ``(meta, p_items, v_items, largest m * n)``."""
+    tile, items = tile or lowrank_tile(), items or LOWRANK_FACTOR_ITEMS
+    if not segs:
+        raise ValueError("empty segment list")
+    for i, sg in enumerate(segs):
+        m, n, r = sg[5:8]
+        if m < 1 or n < 1 or not 1 <= r <= min(m, n, LOWRANK_FACTOR_MAX_RANK):
+            raise ValueError(f"plan_lowrank_factor: segment {i}: m = {m}, n = {n}, r = {r} (1 <= r <= min(m, n, 32))")
+        if m * n >= sparse.INDEX_LIMIT:
+            raise ValueError(f"plan_lowrank_factor: segment {i}: {m * n} elements; 2^31 or more are not factorised")
+    head = np.zeros((len(segs), N.LOWRANK_FACTOR_SEGMENT_INT64S), dtype=np.int64)
+    head[:, :10] = np.asarray(segs, dtype=np.uint64).view(np.int64)
+    for col, (xi, ki) in ((10, (5, 6)), (13, (6, 5))):              # P = D Q: tiles of m, K = n; V = U^T D: tiles of n, K = m
+        tiles = [-(-sg[xi] // tile) for sg in segs]
+        share = max(1, items // sum(tiles))
+        begin = 0
+        for i, sg in enumerate(segs):
+            stages = -(-sg[ki] // LOWRANK_FACTOR_STAGE)
+            per = -(-stages // min(stages, share))
+            splits = -(-stages // per)
+            head[i, col:col + 3] = (begin, splits, per * LOWRANK_FACTOR_STAGE)
+            begin += tiles[i] * splits
+        if col == 10:
+            p_items = begin
+    return head.reshape(-1), p_items, begin, max(sg[5] * sg[6] for sg in segs)
+
+
+def lowrank_factor_(ws: List[torch.Tensor], bases: List[torch.Tensor], qs: List[torch.Tensor], us: List[torch.Tensor],
+                    vs: List[torch.Tensor]) -> None:
+    """us[s], vs[s] = one power iteration on ``D = ws[s] - bases[s]``: ``P = D qs[s]``, ``us[s] = orth(P)``, ``vs[s] =
+    us[s]^T D``, written in place (kernels: flame_lowrank_factor; DESIGN.md §2 "the low-rank downlink").  ``ws`` /
+    ``bases``: contiguous fp32 ``[m, n]`` device tensors; ``qs``: fp32 ``[n, r]`` of any strides; ``us`` / ``vs``:
+    contiguous fp32 ``[m, r]`` / ``[r, n]``.  One call on torch's current stream; nothing is read back."""
+    if not (len(ws) == len(bases) == len(qs) == len(us) == len(vs)):
+        raise ValueError("flame_amd.lowrank_factor_: one base, q, u and v per key")
+    if not ws:
+        return
+    device = ws[0].device
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.lowrank_factor_: tensors must live on the GPU (no CPU fallback)")
+    segs = []
+    for w, b, q, u, v in zip(ws, bases, qs, us, vs):
+        if w.dim() != 2 or q.dim() != 2:
+            raise ValueError("flame_amd.lowrank_factor_: w is [m, n] and q is [n, r]")
+        (m, n), r = w.shape, q.shape[1]
+        for t, shape, dense in ((w, (m, n), True), (b, (m, n), True), (q, (n, r), False), (u, (m, r), True), (v, (r, n), True)):
+            if t.dtype != torch.float32 or t.device != device or tuple(t.shape) != shape or (dense and not t.is_contiguous()):
+                raise ValueError(f"flame_amd.lowrank_factor_: a key of {m} x {n} at rank {r} needs a contiguous fp32 "
+                                 f"device tensor of {shape} here, got {t.dtype} {tuple(t.shape)}")
+        segs.append((w.data_ptr(), b.data_ptr(), q.data_ptr(), u.data_ptr(), v.data_ptr(), m, n, r, q.stride(0), q.stride(1)))
+    meta, p_items, v_items, max_elems = plan_lowrank_factor(segs)
+    L = N.lib()
+    sbytes = int(L.flame_lowrank_factor_scratch_bytes(p_items, v_items))
+    scratch = torch.empty(sbytes, dtype=torch.uint8, device=device)
+    keep = [scratch]
+    rank = max(sg[7] for sg in segs)
+    # two reads of w and of base, the panels and factors once each
+    nbytes = sum(16 * sg[5] * sg[6] + 8 * sg[7] * (sg[5] + sg[6]) for sg in segs)
+    _launch("flame_lowrank_factor", nbytes, device, keep, meta,
+            lambda b: L.flame_lowrank_factor(0, b, len(segs), rank, max_elems, p_items, v_items, scratch.data_ptr(), sbytes,
+                                             _stream_ptr(device)))
+    _keepalive(keep + list(ws) + list(bases) + list(qs) + list(us) + list(vs), device)
+
+
+def lowrank_factor(weights, rank: int, min_numel: int = 0, *, base, q=None, seed: int = 0, device=None):
+    """The low-rank downlink's message (DESIGN.md §2 "the low-rank downlink"): ``(LowRankWeights, q_next)``.
+    Every fp32 key of at least two dimensions and ``max(min_numel, 1)`` elements is factorised by one PowerSGD
+    power iteration on the change ``D = weights[key] - base[key]``, viewed ``[m, n]`` by
+    :func:`lowrank.matrix_shape`, at rank ``r = min(rank, m, n)`` (``rank <= 32``): ``P = D Q``, ``U = orth(P)``
+    (a column with nothing left is zeros, never NaN), ``V = U^T D``; then ``base[key] += U V`` in place, the
+    flame_agg_reduce_lowrank launch with one client at rate 1.  What the factors miss stays in ``weights - base``
+    and competes again next time (error feedback).  Every other key passes through as the object it is.
+
+    ``base``: ``{key: contiguous fp32 device tensor of the key's numel}``, one per factorised key.  ``q``: the
+    ``q_next`` of the previous call (``{key: fp32 [n, r]}``, here views of that call's ``V``); a key it lacks
+    starts from ``noise_fill`` of ``(seed, the key's position in weights)``, so a run is reproducible.  A
+    host-resident or strided key is staged to the device first.  Nothing is read back.
+
+    Unlike the sparse downlink, a trainer that applies ``lowrank.apply_`` does NOT hold the base bit for bit:
+    ``U @ V`` on its CPU and on the matrix cores round differently, each within the any-order fp32 bound of a
+    length-r dot product, ``gamma_r |U| |V|``, per message; the differences add up until the next dense message."""
+    if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= LOWRANK_FACTOR_MAX_RANK:
+        raise ValueError(f"flame_amd.lowrank_factor: rank {rank!r} is not an integer in 1 .. {LOWRANK_FACTOR_MAX_RANK}")
+    device = _hip_device(device, "lowrank_factor", prefer=weights)
+    out, right, shapes, q_next = collections.OrderedDict(), {}, {}, {}
+    keys, ws, bases, qs, fresh = [], [], [], [], []
+    for pos, (key, v) in enumerate(weights.items()):
+        out[key] = v
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float32 and v.dim() >= 2 and v.numel() >= max(min_numel, 1)):
+            continue
+        if v.numel() >= sparse.INDEX_LIMIT:
+            raise ValueError(f"flame_amd.lowrank_factor: key {key!r} has {v.numel()} elements; 2^31 or more are not factorised")
+        if key not in base:
+            raise KeyError(f"flame_amd.lowrank_factor: no base for key {key!r}")
+        b = base[key]
+        if not (b.is_contiguous() and b.dtype == torch.float32 and b.numel() == v.numel() and b.device == device):
+            raise ValueError(f"flame_amd.lowrank_factor: the base of key {key!r} must be a contiguous fp32 device tensor "
+                             f"of {v.numel()} elements")
+        m, n = lowrank.matrix_shape(v.shape)
+        r = min(rank, m, n)
+        qk = q.get(key) if q is not None else None
+        if qk is None:
+            qk = torch.empty((n, r), dtype=torch.float32, device=device)
+            fresh.append((qk, pos))
+        elif tuple(qk.shape) != (n, r) or qk.dtype != torch.float32 or qk.device != device:
+            raise ValueError(f"flame_amd.lowrank_factor: q of key {key!r} must be an fp32 device tensor of {(n, r)}")
+        keys.append(key)
+        ws.append(_staged(v.detach(), device).view(m, n))
+        bases.append(b.view(m, n))
+        qs.append(qk)
+        out[key] = torch.empty((m, r), dtype=torch.float32, device=device)
+        right[key] = torch.empty((r, n), dtype=torch.float32, device=device)
+        shapes[key], q_next[key] = tuple(v.shape), right[key].t()
+    sent = lowrank.LowRankWeights(out, right, shapes)
+    if keys:
+        noise_fill_([t for t, _ in fresh], [pos for _, pos in fresh], [0] * len(fresh), seed, 0, 1.0)
+        lowrank_factor_(ws, bases, qs, [out[k] for k in keys], [right[k] for k in keys])
+        _LowRankRound({k: b.view(shapes[k]) for k, b in zip(keys, bases)}, keys, [0], [(sent, 1.0)], device).reduce()
+    return sent, q_next
 
 
 # ------------------------------------------------------------------ dict-level helpers used by the optimizers

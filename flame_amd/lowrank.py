@@ -83,6 +83,26 @@ def compress(weights, rank: int, min_numel: int = 0, dtype=torch.float32) -> Low
     return LowRankWeights(out, right, shapes)
 
 
+def apply_(model: dict, msg) -> dict:
+    """The trainer's side of the low-rank downlink (``egress.MessageEncoder(lowrank=)``): ``msg`` applied to
+    ``model`` in place.  A factored key of a :class:`LowRankWeights` is the change since the last message:
+    ``model[k] += (U @ V).view(shape)``, the product in fp32 where the model lives.  Every other key, and every
+    key of a plain dict, is copied over.  The encoder's base took the same product from the matrix cores, which
+    round in another order: the two differ by at most the any-order fp32 bound of a length-r dot product per
+    message, ``gamma_r |U| |V|``, and the differences add up until the next dense message.  Returns ``model``."""
+    right = msg.right if isinstance(msg, LowRankWeights) else {}
+    for k, v in msg.items():
+        if k in right:
+            dev = model[k].device
+            model[k] += (v.to(dev, torch.float32) @ right[k].to(dev, torch.float32)).view(model[k].shape)
+        elif isinstance(v, torch.Tensor) and isinstance(model.get(k), torch.Tensor) and model[k].shape == v.shape \
+                and model[k].dtype == v.dtype:
+            model[k].copy_(v)
+        else:
+            model[k] = v.clone() if isinstance(v, torch.Tensor) else v
+    return model
+
+
 def densify(w: LowRankWeights) -> dict:
     """``{key: fp32 U @ V in the key's logical shape}`` for the factored keys of ``w``; every other key as it is."""
     out = collections.OrderedDict()

@@ -537,6 +537,56 @@ int flame_agg_reduce_lowrank(int agg_dtype, int factor_dtype, unsigned flags, co
                              void *stream);
 
 /*
+ * The low-rank factoriser (the contract is this project's own, DESIGN.md §2, "the low-rank downlink"): one
+ * power iteration of PowerSGD (Vogels et al., NeurIPS 2019) per fp32 key, on the change D = w - base, which
+ * is formed in registers (one fp32 subtract per element) and never stored.  Per segment:
+ *   P = D Q            [m, r], on the fp32 matrix cores (v_mfma_f32_32x32x2_f32), K split over workgroups
+ *   U = orth(P)        modified Gram-Schmidt with one re-orthogonalisation, dots and norms in fp64; a
+ *                      column whose remaining norm is 0 is a column of zeros
+ *   V = U^T D          [r, n], the same stream of w and base read once more
+ * One call enqueues five launches on `stream` (project, finish, orth, project, finish) and reads nothing
+ * back.  No atomic: a tile's partials are added in a fixed order, and equal calls give equal bits.
+ *   segs      : device array of flame_lowrank_factor_segment.  w / base: fp32 [m, n] row-major, any 4-byte
+ *               alignment (16-byte aligned with n % 4 == 0 takes vector loads).  q: fp32, element (k, j) of
+ *               the [n, r] right factor at q[k * q_ldk + j * q_ldj] (the previous V serves as it lies:
+ *               q_ldk = 1, q_ldj = n).  u: fp32 [m, r] out; v: fp32 [r, n] out.  r <= rank.  A pass's work
+ *               items are (tile of T = 128 rows or columns) x (K split): p_begin / v_begin are the prefix
+ *               sums of tiles * splits over previous segments, p_kper / v_kper the K elements per split,
+ *               multiples of 64, with (splits - 1) * kper < K (n for the first pass, m for the second).
+ *   rank      : 1 .. 32; every segment's r is clamped to it.
+ *   max_elems : the largest m * n of the table, < 2^31 (the stream is addressed with 32-bit offsets).
+ *   scratch   : device buffer of >= flame_lowrank_factor_scratch_bytes(p_items, v_items) bytes, 16-byte
+ *               aligned; its contents on entry do not matter.
+ * Refusals, each before any HIP call and named in flame_last_error: max_elems >= 2^31 is FLAME_ENOTSUP; a
+ * NULL table or scratch, a scratch smaller than flame_lowrank_factor_scratch_bytes says, n_segs <= 0, rank
+ * outside 1 .. 32, max_elems < 0, p_items or v_items outside [1, 2^24) or any flag is FLAME_EINVAL.  m, n and r
+ * live in the device table, which the entry point does not read: flame_amd.engine.plan_lowrank_factor
+ * refuses bad ones.  Device tables only.  Not a launch branch of flame_launch_branches().
+ */
+typedef struct flame_lowrank_factor_segment {
+    const void *w;
+    const void *base;
+    const void *q;
+    void *u;
+    void *v;
+    int64_t m;
+    int64_t n;
+    int64_t r;
+    int64_t q_ldk;
+    int64_t q_ldj;
+    int64_t p_begin;
+    int64_t p_splits;
+    int64_t p_kper;
+    int64_t v_begin;
+    int64_t v_splits;
+    int64_t v_kper;
+} flame_lowrank_factor_segment;
+int64_t flame_lowrank_factor_scratch_bytes(int64_t p_items, int64_t v_items);
+int flame_lowrank_factor(unsigned flags, const flame_lowrank_factor_segment *segs, int32_t n_segs, int32_t rank,
+                         int64_t max_elems, int64_t p_items, int64_t v_items, void *scratch, int64_t scratch_bytes,
+                         void *stream);
+
+/*
  * The MX quantiser: fp32 / bf16 / f16 keys into MX element bytes and E8M0 scale bytes in one launch per
  * (source dtype, element format) -- the model message's downlink (flame_amd.egress.MessageEncoder(mx=)).
  * flame_amd.mx.quantize is the definition ("the MX quantiser"); flame_agg_reduce_mx's and
