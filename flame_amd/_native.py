@@ -49,6 +49,7 @@ EXPORTS = (
     "flame_mx_quantize", "flame_mx_quantize_chunk_elems",
     "flame_topk_chunk_elems", "flame_topk_scratch_bytes", "flame_topk_select",
     "flame_sparse_chunk_elems", "flame_sparse_index_scratch_bytes", "flame_sparse_index", "flame_agg_reduce_sparse",
+    "flame_sign_chunk_elems", "flame_agg_reduce_sign",
     "flame_lowrank_tile", "flame_lowrank_stage_rows", "flame_agg_reduce_lowrank",
     "flame_lowrank_factor_scratch_bytes", "flame_lowrank_factor",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
@@ -135,6 +136,10 @@ def lib() -> ctypes.CDLL:
     L.flame_sparse_index.argtypes = [vp, i32, i64, vp, vp, i32, vp, vp, i64, vp]
     L.flame_agg_reduce_sparse.restype = ctypes.c_int
     L.flame_agg_reduce_sparse.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp]
+    L.flame_sign_chunk_elems.restype = i64
+    L.flame_sign_chunk_elems.argtypes = []
+    L.flame_agg_reduce_sign.restype = ctypes.c_int
+    L.flame_agg_reduce_sign.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, vp, i32, vp, vp]
     L.flame_lowrank_tile.restype = i64
     L.flame_lowrank_tile.argtypes = []
     L.flame_lowrank_stage_rows.restype = i64

@@ -33,6 +33,7 @@
 #include <cstring>
 #include <cstdarg>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/flame_amd.h"
 #include "fastmath.h"
@@ -1314,6 +1315,136 @@ __global__ __launch_bounds__(kBlock) FLAME_SPARSE_FN void agg_reduce_sparse_kern
                 if (o + j < sub_len) st1(out + o + j, acc[o + j]);
         }
     }
+}
+
+// ---------------------------------------------------------------- 1-bit sign updates
+// flame_agg_reduce_sign: scaled-sign updates (one bit per element, one fp32 scale per 256) into an fp32
+// aggregate ("the sign contract"; flame_amd/sign.py is the format).  Element e of a key is
+// bit e % 64 of 64-bit word e / 64, set = negative, and its magnitude is scales[e / 256].  Per element,
+// clients in order, acc = acc + (bit ? -t : t) with t = scale * rate formed once per client and block:
+// (-s) * r and -(s * r) have the same bits for every non-NaN s.
+//   * Tile.  A chunk is 16,384 elements, a wave owns a tile of 4,096 of them: 64 words, 16 blocks.  Lane l
+//     owns elements 64 k + l of the tile, k = 0 .. 63, in 64 accumulators it keeps for the whole client
+//     loop: every model load and store of the wave is one coalesced 256-byte row, and word k of a client's
+//     tile IS the wave's lane mask of step k.  Waves share nothing: no LDS, no barrier.
+//   * Client.  One coalesced load of the tile's 64 words (lane l takes word l, non-temporal) and one of its
+//     16 scales (lanes 0 .. 15); CU clients' loads are issued together.  Lanes 0 .. 15 form t of their
+//     block.  Step k brings word k into a scalar register pair (v_readlane_b32 twice) and block k / 4's t
+//     into a vector register (one v_readlane_b32 and one v_mov_b32 per four steps); the add is then
+//     v_cndmask_b32 t, -t under that pair and v_add_f32 -- no per-lane shift or mask arithmetic (sign_steps,
+//     4.5 vector instructions per element and client in all).  Bits and scales are only ever loaded.
+//   * Edges.  The last tile of a key loads no word at or past ceil(numel / 64) and no scale at or past
+//     ceil(numel / 256) (zeros instead) and neither loads nor stores an element at or past numel: the pad
+//     bits of the last word land in accumulators that are never stored.  Model accesses are dwords, so
+//     FLAME_SEG_UNALIGNED changes nothing here.  Register figures and residency: DESIGN.md §4.
+#ifndef FLAME_T_SIGN_UNROLL
+#define FLAME_T_SIGN_UNROLL 8
+#endif
+constexpr int kSignUnroll = FLAME_T_SIGN_UNROLL;        // clients whose loads are in flight per wave (the MXFP8 kernel's)
+constexpr int kSignSteps = 64;                          // accumulators per lane = 64-bit words per tile
+constexpr int kSignBlockElems = 256;                    // elements per scale
+constexpr int kSignTile = kSignSteps * kWaveLanes;      // elements per wave
+constexpr int kSignTileBlocks = kSignTile / kSignBlockElems;
+constexpr int64_t kSignChunk = static_cast<int64_t>(kBlock / kWaveLanes) * kSignTile;
+static_assert(kWaveLanes == 64 && kSignSteps % kSignTileBlocks == 0 && kSignTileBlocks <= kWaveLanes,
+              "a word is a wave's lane mask; whole steps per block; one lane per scale");
+
+// Steps K and K + 1 of one client (lane l holds word l of the tile in lo / hi, t is the steps' block's): the
+// lane masks into vcc and s[100:101], then a += mask ? -t : t twice.  Assembly, because from C++ (readlane
+// builtins and a select under the inverse ballot of the pair) the scheduler reads the masks of many steps
+// ahead, runs out of scalar registers and moves 0.75 masks per step through v_writelane_b32 / v_readlane_b32
+// (385 and 389 more per 512 steps in the listing).  Two steps per statement so that each v_cndmask_b32 is two
+// instructions behind the v_readlane_b32 that wrote its mask (gfx950: a VALU read of an SGPR that a VALU wrote
+// needs two wait states) without an s_nop.  Nothing but vector registers is written to.
+template <int K>
+__device__ __forceinline__ void sign_steps(float& a0, float& a1, float t, uint32_t lo, uint32_t hi) {
+    float x;
+    asm volatile("v_readlane_b32 vcc_lo, %4, %6\n\t"
+                 "v_readlane_b32 vcc_hi, %5, %6\n\t"
+                 "v_readlane_b32 s100, %4, %7\n\t"
+                 "v_readlane_b32 s101, %5, %7\n\t"
+                 "v_cndmask_b32_e64 %2, %3, -%3, vcc\n\t"
+                 "v_add_f32_e32 %0, %0, %2\n\t"
+                 "v_cndmask_b32_e64 %2, %3, -%3, s[100:101]\n\t"
+                 "v_add_f32_e32 %1, %1, %2"
+                 : "+v"(a0), "+v"(a1), "=&v"(x)
+                 : "v"(t), "v"(lo), "v"(hi), "n"(K), "n"(K + 1)
+                 : "vcc", "s100", "s101");
+}
+
+// One client into the tile's accumulators: step pairs P = 0 .. 31, block 2 P / 4's t out of lane 2 P / 4 of tl
+template <int... P>
+__device__ __forceinline__ void sign_client(float (&acc)[kSignSteps], uint32_t lo, uint32_t hi, float tl,
+                                            std::integer_sequence<int, P...>) {
+    constexpr int PER = kSignSteps / kSignTileBlocks;   // steps per scale block
+    static_assert(PER % 2 == 0, "a pair of steps shares a block");
+    (sign_steps<2 * P>(acc[2 * P], acc[2 * P + 1],
+                       __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, tl), 2 * P / PER)), lo, hi), ...);
+}
+
+// One wave's tile: `in` / `out` at the tile's first element, `rem` elements of the key from there on (FULL:
+// at least a tile), words from w0 of nw and scales from b0 of nb.  bp / sp: the segment's client rows.
+template <int CU, bool FULL>
+__device__ __forceinline__ void sign_tile(const float* in, float* out, int64_t rem, const uint64_t* __restrict__ bp,
+                                          const uint64_t* __restrict__ sp, int n_clients, const float* __restrict__ r32,
+                                          int64_t w0, int64_t nw, int64_t b0, int64_t nb, int lane) {
+    float acc[kSignSteps];
+#pragma unroll
+    for (int k = 0; k < kSignSteps; ++k) acc[k] = (FULL || kWaveLanes * k + lane < rem) ? ld1(in + kWaveLanes * k + lane) : 0.f;
+    struct Ld { uint32_t lo, hi; float t; };
+    auto load_client = [&](int c, Ld& l) {
+        uint64_t w = 0;
+        if (FULL || w0 + lane < nw) w = __builtin_nontemporal_load(G(reinterpret_cast<const uint64_t*>(bp[c]) + w0 + lane));
+        float s = 0.f;
+        if (lane < kSignTileBlocks && (FULL || b0 + lane < nb))
+            s = __builtin_nontemporal_load(G(reinterpret_cast<const float*>(sp[c]) + b0 + lane));
+        l.lo = static_cast<uint32_t>(w);
+        l.hi = static_cast<uint32_t>(w >> 32);
+        l.t = __fmul_rn(s, r32[c]);                     // lane b < 16: block b's t
+    };
+    auto combine = [&](const Ld& l) { sign_client(acc, l.lo, l.hi, l.t, std::make_integer_sequence<int, kSignSteps / 2>{}); };
+    int i = 0;
+    for (; i + CU <= n_clients; i += CU) {
+        Ld l[CU];
+#pragma unroll
+        for (int u = 0; u < CU; ++u) load_client(i + u, l[u]);
+#pragma unroll
+        for (int u = 0; u < CU; ++u) combine(l[u]);
+    }
+    for (; i < n_clients; ++i) {
+        Ld l;
+        load_client(i, l);
+        combine(l);
+    }
+#pragma unroll
+    for (int k = 0; k < kSignSteps; ++k)
+        if (FULL || kWaveLanes * k + lane < rem) st1(out + kWaveLanes * k + lane, acc[k]);
+}
+
+template <int CU>
+__global__ __launch_bounds__(kBlock) void agg_reduce_sign_kernel(const flame_segment* __restrict__ segs, int n_segs,
+                                                                 const uint64_t* __restrict__ bits,
+                                                                 const uint64_t* __restrict__ scales, int n_clients,
+                                                                 const float* __restrict__ r32, int64_t n_chunks) {
+    static_assert(LaneChunk<flame_segment, kSignSteps>::CE == kSignChunk, "a chunk is four tiles");
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, kSignSteps> lc(segs, n_segs, chunk);
+    const flame_segment sg = lc.sg;
+    const int t = static_cast<int>(threadIdx.x), lane = t % kWaveLanes;
+    const int wave = __builtin_amdgcn_readfirstlane(t / kWaveLanes);
+    const int64_t tile = (chunk - sg.chunk_begin) * kSignChunk + static_cast<int64_t>(wave) * kSignTile;
+    if (tile >= sg.numel) return;                       // the whole wave: an idle chunk, or the key ends before this tile
+    const int64_t rem = sg.numel - tile;
+    const int64_t nw = (sg.numel + kWaveLanes - 1) / kWaveLanes, nb = (sg.numel + kSignBlockElems - 1) / kSignBlockElems;
+    const uint64_t* bp = lc.row(bits, n_clients);
+    const uint64_t* sp = lc.row(scales, n_clients);
+    const float* in = reinterpret_cast<const float*>(sg.in) + tile;
+    float* out = reinterpret_cast<float*>(sg.out) + tile;
+    if (rem >= kSignTile)
+        sign_tile<CU, true>(in, out, rem, bp, sp, n_clients, r32, tile / kWaveLanes, nw, tile / kSignBlockElems, nb, lane);
+    else
+        sign_tile<1, false>(in, out, rem, bp, sp, n_clients, r32, tile / kWaveLanes, nw, tile / kSignBlockElems, nb, lane);
 }
 
 // ---------------------------------------------------------------- low-rank updates
@@ -5620,6 +5751,36 @@ int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment* 
     else
         hipLaunchKernelGGL((agg_reduce_sparse_kernel<kSparseUnroll, false>), grid, block, 0, st, segs, n_segs, ix, vl, nnz,
                            n_clients, rates32, scales32, bd, n_chunks);
+    return check_launch(who);
+}
+
+// 1-bit sign updates into an fp32 aggregate: one launch over every sign key of a client group.  Outside the
+// launch-branch table, one instantiation; every refusal comes before the first HIP call.  The pointer tables
+// live in device memory, so what this entry point can hold to 8 bytes is the tables themselves: that every
+// bit pointer IN them is 8-byte aligned is the caller's to keep (flame_amd/engine.py copies a view that is not).
+int64_t flame_sign_chunk_elems(void) { return kSignChunk; }
+
+int flame_agg_reduce_sign(int agg_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                          const void* const* bits, const void* const* scales, int32_t n_clients, const float* rates32,
+                          void* stream) {
+    const char* const who = "flame_agg_reduce_sign";
+    if (agg_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: aggregate dtype %d is not supported (sign updates into f32 only)", who, agg_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (n_clients < 1) return set_err(FLAME_EINVAL, "%s: n_clients < 1", who);
+    if (!bits) return set_err(FLAME_EINVAL, "%s: bit pointer table is NULL", who);
+    if (!scales) return set_err(FLAME_EINVAL, "%s: scale pointer table is NULL", who);
+    if (!rates32) return set_err(FLAME_EINVAL, "%s: rate array is NULL", who);
+    if ((reinterpret_cast<uintptr_t>(segs) | reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(scales)) % 8)
+        return set_err(FLAME_EINVAL, "%s: a table is not 8-byte aligned (segments, bit pointers and scale pointers are 64-bit words)", who);
+    if (flags & FLAME_AGG_INIT_FIRST)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_AGG_INIT_FIRST is not supported (a sign update has no aggregate dtype of its own)", who);
+    if (int rc = no_seg_rates(who, flags)) return rc;
+    if (int rc = check_flags(who, flags, 0)) return rc;
+    hipLaunchKernelGGL((agg_reduce_sign_kernel<kSignUnroll>), dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), segs, n_segs, reinterpret_cast<const uint64_t*>(bits),
+                       reinterpret_cast<const uint64_t*>(scales), n_clients, rates32, n_chunks);
     return check_launch(who);
 }
 

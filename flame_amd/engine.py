@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import lowrank, mx, shm_lease, sparse
+from . import lowrank, mx, shm_lease, sign, sparse
 
 DTYPE_CODE = {
     torch.float32: N.FLAME_F32, torch.bfloat16: N.FLAME_BF16, torch.float16: N.FLAME_F16,
@@ -558,6 +558,7 @@ def refuse_lowrank(ws, who: str) -> None:
         if w is not None and is_lowrank(w):
             raise TypeError(f"flame_amd: {who} does not take low-rank updates (a follow-up, not a silent slow path).  "
                             f"{LOWRANK_SUPPORTED}")
+    refuse_sign(ws, who)
 
 
 def lowrank_route(agg_dtype, ws, k, agg_shape) -> bool:
@@ -597,6 +598,65 @@ def lowrank_route(agg_dtype, ws, k, agg_shape) -> bool:
         if u.shape[0] != m or v.shape[1] != n or u.shape[1] != v.shape[0]:
             raise TypeError(f"flame_amd: key {k!r}: the low-rank factors {tuple(u.shape)} x {tuple(v.shape)} disagree with "
                             f"each other or with (m, n) = ({m}, {n}).  {LOWRANK_SUPPORTED}")
+    return True
+
+
+# 1-bit sign updates (flame_amd.sign.SignWeights: one bit per element as uint8 bytes + one fp32 scale per
+# 256 elements per compressed key), which one flame_agg_reduce_sign launch sums into an fp32 aggregate
+SIGN_SUPPORTED = ("Sign updates are supported as flame_amd.sign.SignWeights whose every entry holds the key as a 1-D uint8 "
+                  "tensor of 8 * ceil(numel / 64) bytes (bit e % 8 of byte e // 8, 1 = negative) with a 1-D fp32 tensor of "
+                  "ceil(numel / 256) block scales in SignWeights.scales and the aggregate's shape in SignWeights.shapes, "
+                  "summed into an fp32 aggregate by engine.accumulate without clip scales (FedAvg, FedProx and FedGFT "
+                  "with defer=False)")
+
+
+def is_sign(w) -> bool:
+    """``w`` is a sign update, a :class:`flame_amd.sign.SignWeights` (one isinstance, as :func:`is_mx`)."""
+    return isinstance(w, sign.SignWeights)
+
+
+def refuse_sign(ws, who: str) -> None:
+    """TypeError when one of the updates ``ws`` is a sign update: ``who`` does not take them (the bit bytes
+    would otherwise pass for a uint8 key of another shape)."""
+    for w in ws:
+        if w is not None and is_sign(w):
+            raise TypeError(f"flame_amd: {who} does not take sign updates (a follow-up, not a silent slow path).  "
+                            f"{SIGN_SUPPORTED}")
+
+
+def sign_route(agg_dtype, ws, k, agg_shape) -> bool:
+    """True when the updates ``ws`` (all carrying ``k``) hold key ``k`` as sign bits + block scales that ONE
+    flame_agg_reduce_sign launch takes; False when none holds it so (its present route); every case in
+    between is a TypeError."""
+    held = [is_sign(w) and k in w.scales for w in ws]
+    if not any(held):
+        return False
+    if not all(held):
+        raise TypeError(f"flame_amd: key {k!r} is a sign update in update {held.index(True)} and not in update "
+                        f"{held.index(False)}: per-key mixtures of sign updates with dense, MX, sparse or low-rank ones are "
+                        f"not supported.  {SIGN_SUPPORTED}")
+    if agg_dtype != torch.float32:
+        raise TypeError(f"flame_amd: key {k!r}: a sign update into a {agg_dtype} aggregate is not supported.  {SIGN_SUPPORTED}")
+    numel = math.prod(agg_shape)
+    nbytes, nblocks = 8 * -(-numel // sign.WORD), -(-numel // sign.BLOCK)
+    for w in ws:
+        b, s = w[k], w.scales[k]
+        if not isinstance(b, torch.Tensor) or b.dtype != torch.uint8 or b.dim() != 1:
+            raise TypeError(f"flame_amd: key {k!r}: the sign update's bits are {getattr(b, 'dtype', type(b).__name__)} "
+                            f"{tuple(getattr(b, 'shape', ()))}, not 1-D torch.uint8.  {SIGN_SUPPORTED}")
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or s.dim() != 1:
+            raise TypeError(f"flame_amd: key {k!r}: the sign update's scales are {getattr(s, 'dtype', type(s).__name__)} "
+                            f"{tuple(getattr(s, 'shape', ()))}, not 1-D torch.float32.  {SIGN_SUPPORTED}")
+        shape = w.shapes.get(k)
+        if shape is None:
+            raise TypeError(f"flame_amd: key {k!r} is a sign update without a SignWeights.shapes entry: the bits do not "
+                            f"say how many elements they hold.  {SIGN_SUPPORTED}")
+        if tuple(shape) != tuple(agg_shape):
+            raise TypeError(f"flame_amd: key {k!r}: the sign update's logical shape {tuple(shape)} is not the aggregate's "
+                            f"{tuple(agg_shape)}.  {SIGN_SUPPORTED}")
+        if b.numel() != nbytes or s.numel() != nblocks:
+            raise TypeError(f"flame_amd: key {k!r}: the sign update holds {b.numel()} bit bytes and {s.numel()} scales, not "
+                            f"the {nbytes} and {nblocks} of {numel} elements.  {SIGN_SUPPORTED}")
     return True
 
 
@@ -1840,8 +1900,18 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
     if any_lowrank and scales is not None:
         raise TypeError(f"flame_amd: clip scales (the update guard) do not take low-rank updates (a follow-up, not a silent "
                         f"slow path).  {LOWRANK_SUPPORTED}")
-    routed = []
+    any_sign = any(is_sign(w) for w, _ in entries)
+    if any_sign and scales is not None:
+        raise TypeError(f"flame_amd: clip scales (the update guard) do not take sign updates (a follow-up, not a silent "
+                        f"slow path).  {SIGN_SUPPORTED}")
+    routed, sign_keys = [], {}
     for cis, ks in groups.items():
+        # sign keys: bit bytes + fp32 block scales of SignWeights under an fp32 aggregate (_SignRound); asked
+        # first, so a mixture with any other kind of update is refused as one
+        sgk = [k for k in ks if any_sign and sign_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape)]
+        if sgk:
+            sign_keys[cis], held = sgk, set(sgk)
+            ks = [k for k in ks if k not in held]
         # MX keys: float8 elements + block scales of MXWeights under an fp32 aggregate (reduce_ groups
         # those into one flame_agg_reduce_mx per element format)
         mxk = {k for k in ks if any_mx and mx_route(agg[k].dtype, [entries[ci][0] for ci in cis], k, agg[k].shape) is not None}
@@ -1872,6 +1942,8 @@ def accumulate(agg: dict, entries, *, device=None, key_groups=None, after_group=
             sr.reduce()
         if lrk:
             _LowRankRound(agg, lrk, cis, entries, device).reduce()
+        if cis in sign_keys:
+            _SignRound(agg, sign_keys[cis], cis, entries, device).reduce()
         # with clip scales the float keys take the scaled kernel; integer keys are never scaled
         parts = [(same, None)] if scales is None else [
             ([k for k in same if agg[k].is_floating_point()], [scales[ci] for ci in cis]),
@@ -1975,6 +2047,74 @@ class _SparseRound:
                                                     self.bounds.data_ptr(), self.sbytes, _stream_ptr(device)))
         _keepalive(self.keep, device)
         for t in self.targets:
+            t.writeback()
+
+
+def sign_chunk_elems() -> int:
+    """Elements per chunk of flame_agg_reduce_sign (four waves' tiles), as compiled into the library."""
+    return int(N.lib().flame_sign_chunk_elems())
+
+
+def plan_sign(segs: Sequence[Seg], bits, scales, rates, chunk: Optional[int] = None):
+    """The metadata block flame_agg_reduce_sign reads (no GPU needed): ``[segments] [bit pointers] [scale
+    pointers] [rates32]``, the two tables ``[n_segs][n_clients]``.  Every segment starts a chunk of
+    flame_sign_chunk_elems() elements; one of 0 elements has none.  Returns ``(meta, n_chunks, byte offsets
+    by name)``."""
+    b = _Block(chunk or sign_chunk_elems())
+    bits, scales = np.asarray(bits, dtype=np.uint64), np.asarray(scales, dtype=np.uint64)
+    if bits.shape != (len(segs), len(rates)) or scales.shape != bits.shape:
+        raise ValueError("plan_sign: one bit pointer and one scale pointer per segment and client")
+    if (bits % 8).any():
+        raise ValueError("plan_sign: a bit pointer is not 8-byte aligned (the kernel loads 64-bit words)")
+    head = np.zeros((len(segs), SEG_WORDS), dtype=np.uint64)
+    for i, s in enumerate(segs):
+        head[i, :2] = (s.out, s.inp)
+        head[i, 6:9] = (s.numel, b.chunk_begin(s.numel), s.flags)
+    b.add("segs", head)
+    b.add("bits", bits)
+    b.add("scales", scales)
+    b.add("r32", _f32(rates))
+    meta, n_chunks = b.finish()
+    return meta, n_chunks, b.offs
+
+
+class _SignRound:
+    """The sign keys ``keys`` of one client group of :func:`accumulate`: ONE flame_agg_reduce_sign launch.
+    Bits and scales are read where they are when the device can (device tensors, pinned host memory: the
+    MX route's rule, :func:`_row_pointer`) and copied to the device otherwise; a bits view that does not
+    start on 8 bytes is copied to an allocation that does.  The aggregate goes through :class:`_Target`."""
+
+    def __init__(self, agg, keys, cis, entries, device):
+        # an empty key receives nothing: no staging, no segment
+        self.agg, self.keys, self.device = agg, [k for k in keys if agg[k].numel()], device
+        self.ws, self.rates = [entries[ci][0] for ci in cis], [entries[ci][1] for ci in cis]
+
+    @staticmethod
+    def _bits(b: torch.Tensor, device, keep) -> int:
+        if b.data_ptr() % 8:
+            b = _staged(b, device)
+            if b.data_ptr() % 8:
+                b = b.clone()
+        return _row_pointer(b, device, keep)
+
+    def reduce(self):
+        if not self.keys:
+            return
+        L, device, keep = N.lib(), self.device, []
+        targets = [_Target(self.agg[k], device) for k in self.keys]
+        keep += [t.dev for t in targets]
+        bits = [[self._bits(w[k], device, keep) for w in self.ws] for k in self.keys]
+        scales = [[_row_pointer(w.scales[k], device, keep) for w in self.ws] for k in self.keys]
+        segs = [Seg(t.dev.numel(), out=t.dev.data_ptr(), inp=t.dev.data_ptr()) for t in targets]
+        meta, n_chunks, o = plan_sign(segs, bits, scales, self.rates)
+        # per client and key the bit words and the scales, one fp32 read and one fp32 write per element
+        nbytes = sum(w[k].numel() + 4 * w.scales[k].numel() for w in self.ws for k in self.keys) \
+            + 2 * ITEMSIZE[N.FLAME_F32] * sum(s.numel for s in segs)
+        _launch("flame_agg_reduce_sign", nbytes, device, keep, meta,
+                lambda b: L.flame_agg_reduce_sign(N.FLAME_F32, 0, b + o["segs"], len(segs), n_chunks, b + o["bits"],
+                                                  b + o["scales"], len(self.rates), b + o["r32"], _stream_ptr(device)))
+        _keepalive(keep, device)
+        for t in targets:
             t.writeback()
 
 

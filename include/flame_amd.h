@@ -44,6 +44,9 @@
  *                               one E8M0 scale per 32 -- into an fp32 model; the same statements again)
  *   flame_sparse_index,         (no reference counterpart: top-k sparse updates -- int32 indices, fp32
  *   flame_agg_reduce_sparse     values -- into an fp32 model; an absent element contributes nothing)
+ *   flame_agg_reduce_sign       (no reference counterpart: scaled-sign updates -- one bit per element, one fp32
+ *                               scale per 256, as signSGD / EF-signSGD / 1-bit Adam send them -- into an fp32
+ *                               model; the same statements over the dequantized update)
  *   flame_agg_reduce_lowrank    (no reference counterpart: low-rank updates -- factor pairs U [m, r], V [r, n],
  *                               a LoRA adapter or a PowerSGD factorisation -- into an fp32 model: the exact
  *                               aggregate sum_c rate_c U_c V_c as one product on the fp32 matrix cores)
@@ -471,6 +474,47 @@ int flame_agg_reduce_sparse(int agg_dtype, unsigned flags, const flame_segment *
                             int64_t n_chunks, const void *const *indices, const void *const *values,
                             const int64_t *nnz, int32_t n_clients, const float *rates32,
                             const float *scales32, const void *bounds, int64_t bounds_bytes, void *stream);
+
+/*
+ * 1-bit sign updates into an fp32 aggregate (the contract is this project's own, DESIGN.md §2, "the sign
+ * contract"; flame_amd.sign is the format).  An update holds, per tensor, one bit per flat C-order element
+ * and one fp32 scale per block of 256 elements (the last block may be partial), as flame_amd.sign.compress
+ * writes them.
+ *   Bits    : element e is bit e % 8 of byte e / 8 -- on this little-endian device bit e % 64 of 64-bit word
+ *             e / 64.  A set bit means negative.  A bit pointer addresses 8 * ceil(numel / 64) bytes, whole
+ *             words, and is 8-BYTE ALIGNED; the pad bits of the last word are never read into a result.
+ *   Scales  : fp32 [ceil(numel / 256)], 4-byte aligned: element e's magnitude is scales[e / 256], of any
+ *             value (0, subnormal, inf, negative: the rule below says what they give).
+ *   agg_dtype: FLAME_F32.  flags: 0.
+ *   segs    : out / in = the fp32 aggregate (in may == out; one may differ from the other, then every element
+ *             of out is written); chunk_begin counts chunks of flame_sign_chunk_elems() = 16,384 elements
+ *             (a wave owns a tile of 4,096: 64 words, 16 scales), every segment starts a chunk, a segment of
+ *             0 elements has none.  No other field is read: the model is accessed in dwords, so
+ *             FLAME_SEG_UNALIGNED says nothing here.  The table lives in device memory.
+ *   bits    : device array [n_segs][n_clients] of device pointers to the bit words.
+ *   scales  : device array [n_segs][n_clients] of device pointers to the block scales.
+ *   rates32 : device [n_clients].
+ * Per element e, clients in order, no FMA, denormals kept:
+ *   acc = in[e]                                                  (fp32)
+ *   t   = round_f32(s_i[e / 256] * rate_i)                       once per client and block
+ *   acc = round_f32(acc + (bit_i[e] ? -t : t))
+ *   out[e] = acc
+ * (-s) * r and -(s * r) have the same bits for every non-NaN s, so this is bit for bit what
+ * flame_agg_reduce gives for FLAME_F32 over flame_amd.sign.dequantize(update); where a scale is NaN both
+ * hold a NaN, whose sign and payload are not part of the contract.  Nothing at or past numel is loaded from
+ * `in` or stored to `out`, no word at or past ceil(numel / 64) and no scale at or past ceil(numel / 256) is
+ * loaded.  Equal launches give equal bits (no atomic).
+ * Refusals, each before any HIP call and named in flame_last_error: an aggregate dtype other than FLAME_F32
+ * is FLAME_ENOTSUP; FLAME_AGG_INIT_FIRST is FLAME_ENOTSUP; FLAME_AGG_SEG_RATES is FLAME_ENOTSUP; any other
+ * flag, a NULL table or rate array, a segment, bit-pointer or scale-pointer table that is not 8-byte aligned,
+ * n_segs <= 0, n_clients < 1 or n_chunks outside [1, 2^31) is FLAME_EINVAL.  The bit pointers themselves are
+ * device memory this entry point cannot look at: their alignment is the caller's to keep.
+ * Device tables only (no kernel-argument variant).  Not a launch branch of flame_launch_branches().
+ */
+int64_t flame_sign_chunk_elems(void);
+int flame_agg_reduce_sign(int agg_dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                          int64_t n_chunks, const void *const *bits, const void *const *scales,
+                          int32_t n_clients, const float *rates32, void *stream);
 
 /*
  * Low-rank updates into an fp32 aggregate (the contract is this project's own, DESIGN.md §2, "the low-rank
