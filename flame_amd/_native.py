@@ -24,6 +24,7 @@ FLAME_FEDADAM, FLAME_FEDYOGI, FLAME_FEDADAGRAD = 0, 1, 2
 FLAME_OPT_STATE_ZERO = 1
 FLAME_OPT_XCD_MAP = 2
 FLAME_TOPK_BASE = 1                                            # flame_topk_select: every segment's m is its base
+FLAME_ONEBIT_BASE = 1                                          # flame_onebit_pack: every segment's m is its base
 FLAME_SEG_UNALIGNED = 1
 FLAME_SEG_CUR_IS_AVG = 2
 FLAME_LOWRANK_ROW_UVEC, FLAME_LOWRANK_ROW_VVEC = 1, 2          # flame_lowrank_row.flags
@@ -50,6 +51,7 @@ EXPORTS = (
     "flame_topk_chunk_elems", "flame_topk_scratch_bytes", "flame_topk_select",
     "flame_sparse_chunk_elems", "flame_sparse_index_scratch_bytes", "flame_sparse_index", "flame_agg_reduce_sparse",
     "flame_sign_chunk_elems", "flame_agg_reduce_sign",
+    "flame_onebit_pack_chunk_elems", "flame_onebit_pack",
     "flame_lowrank_tile", "flame_lowrank_stage_rows", "flame_agg_reduce_lowrank",
     "flame_lowrank_factor_scratch_bytes", "flame_lowrank_factor",
     "flame_update_dist", "flame_update_dist_scratch_bytes",
@@ -140,6 +142,10 @@ def lib() -> ctypes.CDLL:
     L.flame_sign_chunk_elems.argtypes = []
     L.flame_agg_reduce_sign.restype = ctypes.c_int
     L.flame_agg_reduce_sign.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp, vp, i32, vp, vp]
+    L.flame_onebit_pack_chunk_elems.restype = i64
+    L.flame_onebit_pack_chunk_elems.argtypes = []
+    L.flame_onebit_pack.restype = ctypes.c_int
+    L.flame_onebit_pack.argtypes = [ctypes.c_int, u32, vp, i32, i64, vp]
     L.flame_lowrank_tile.restype = i64
     L.flame_lowrank_tile.argtypes = []
     L.flame_lowrank_stage_rows.restype = i64

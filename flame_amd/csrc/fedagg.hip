@@ -2563,6 +2563,133 @@ __global__ __launch_bounds__(kBlock) FLAME_TOPK_FN void topk_write_kernel(const 
     }
 }
 
+// ---------------------------------------------------------------- 1-bit sign packer
+// flame_onebit_pack: the device-side producer of flame_amd/sign.py's format and, with a base, the sign
+// downlink ("the sign packer").  With d[e] = f32(x[e]), or f32(x[e] - base[e]) under
+// FLAME_ONEBIT_BASE (fp32 only, one IEEE subtract): bit e is d[e]'s sign bit, scale j is the fold-order sum of
+// block j's 256 magnitudes divided by its true length, and base[e] becomes base[e] + (bit ? -scale : scale).
+//   * Lane layout: a dword per lane, the uplink's own.  Lane l owns elements 64 k + l of the wave's tile, so
+//     every load and store of the wave is one coalesced row and the ballot of step k's sign bits IS word k.
+//     (16-byte loads would need nibbles OR-reduced over 16 lanes; not built, not measured.)
+//   * Tile: 1,024 elements per wave -- 16 steps, 16 words, 4 blocks -- and 4,096 per chunk.  A 2M-element
+//     model is 2,048 tiles for the 1,024 SIMDs; 16 (with a base 32) dword loads per lane are issued before the
+//     first use.  Every key starts a chunk (LaneChunk), so no word or block straddles two keys.
+//   * The fold.  h = 128, 64 are in-lane: block j's steps (4j + 0 + 4j + 2) + (4j + 1 + 4j + 3).  h = 32:
+//     v_permlane32_swap of two blocks' registers and one add leave block A's 32 partial sums in lanes 0 .. 31
+//     and block B's in lanes 32 .. 63; twice, then v_permlane16_swap of the two results and one add: the
+//     wave's four rows of 16 lanes hold blocks 0, 2, 1, 3.  h = 8 .. 1 are four v_add_f32_dpp on that one
+//     register (row_ror:8, row_ror:4 -- after ror:8 lanes l and l ^ 8 hold the same bits, so either
+//     direction of the rotation brings the xor-4 partner's value -- then quad_perm [2,3,0,1], [1,0,3,2]).
+//     fp32 addition commutes bit for bit, so a butterfly leaves the fold's result in every lane of the row.
+//     Seven cross-lane instructions per tile; no LDS, no barrier, waves share nothing.
+//   * Stores.  Lane k keeps step k's mask (the ballot's scalar pair selected into two vector registers), so a
+//     tile ends in one 8-byte store by lanes 0 .. 15 and one 4-byte store by the first lane of each row;
+//     the base goes back in coalesced dwords.  Vector stores only.
+//   * Edges.  The last tile of a key loads zeros (+0) at and past numel, which give bit 0 and magnitude 0: the
+//     last word is whole with zero pad bits, the last block divides by its true length; no word at or past
+//     ceil(numel / 64), no scale at or past ceil(numel / 256) and no base element at or past numel is stored.
+//     Sources and bases move in elements, so FLAME_SEG_UNALIGNED changes nothing here.  Offsets are 64-bit.
+constexpr int kObSteps = 16;                            // elements per lane = 64-bit words per tile
+constexpr int kObTile = kObSteps * kWaveLanes;          // elements per wave
+constexpr int kObBlocks = kObTile / kSignBlockElems;    // scales per tile
+constexpr int kObPer = kObSteps / kObBlocks;            // steps per block
+constexpr int64_t kObChunk = static_cast<int64_t>(kBlock / kWaveLanes) * kObTile;
+static_assert(kWaveLanes == 64 && kObBlocks == 4 && kObPer == 4, "a word is a lane mask; four blocks fold by two swaps of pairs and one of rows");
+
+__device__ __forceinline__ uint32_t ob_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+__device__ __forceinline__ float ob_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
+// lanes 0 .. 31: a[l] + a[l + 32]; lanes 32 .. 63: b[l - 32] + b[l]
+__device__ __forceinline__ float ob_fold32(float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(ob_bits(a), ob_bits(b), false, false);
+    return __fadd_rn(ob_f32(r[0]), ob_f32(r[1]));
+}
+// rows 0 .. 3 of 16 lanes: p's rows 0 + 1, q's rows 0 + 1, p's rows 2 + 3, q's rows 2 + 3
+__device__ __forceinline__ float ob_fold16(float p, float q) {
+    const auto r = __builtin_amdgcn_permlane16_swap(ob_bits(p), ob_bits(q), false, false);
+    return __fadd_rn(ob_f32(r[0]), ob_f32(r[1]));
+}
+template <int CTRL> __device__ __forceinline__ float ob_fold_row(float v) {
+    return __fadd_rn(v, ob_f32(static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(ob_bits(v)), CTRL, 0xF, 0xF, true))));
+}
+
+// One wave's tile: `rem` elements of the key from the tile's first one on (FULL: at least a tile); src / base
+// / words / scales point at the tile's first element, word and scale.
+template <int SD, bool BASE, bool FULL>
+__device__ __forceinline__ void onebit_tile(const typename Tr<SD>::T* src, float* base, uint64_t* words, float* scales,
+                                            int64_t rem, int lane) {
+    using T = typename Tr<SD>::T;
+    T x[kObSteps];
+    float b[kObSteps], d[kObSteps];
+#pragma unroll
+    for (int k = 0; k < kObSteps; ++k)
+        x[k] = (FULL || kWaveLanes * k + lane < rem) ? __builtin_nontemporal_load(G(src + kWaveLanes * k + lane)) : T(0);
+    if constexpr (BASE) {
+#pragma unroll
+        for (int k = 0; k < kObSteps; ++k) b[k] = (FULL || kWaveLanes * k + lane < rem) ? ld1(base + kWaveLanes * k + lane) : 0.f;
+    }
+    uint32_t wlo = 0, whi = 0;
+    float part[kObBlocks];
+#pragma unroll
+    for (int k = 0; k < kObSteps; ++k) {
+        d[k] = BASE ? __fsub_rn(Tr<SD>::ld(x[k]), b[k]) : Tr<SD>::ld(x[k]);
+        const uint64_t m = __builtin_amdgcn_ballot_w64(static_cast<int32_t>(ob_bits(d[k])) < 0);
+        if (lane == k) {
+            wlo = static_cast<uint32_t>(m);
+            whi = static_cast<uint32_t>(m >> 32);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kObBlocks; ++j)
+        part[j] = __fadd_rn(__fadd_rn(__builtin_fabsf(d[4 * j]), __builtin_fabsf(d[4 * j + 2])),
+                            __fadd_rn(__builtin_fabsf(d[4 * j + 1]), __builtin_fabsf(d[4 * j + 3])));
+    float s = ob_fold16(ob_fold32(part[0], part[1]), ob_fold32(part[2], part[3]));     // rows: blocks 0, 2, 1, 3
+    s = ob_fold_row<0x128>(s);          // row_ror:8
+    s = ob_fold_row<0x124>(s);          // row_ror:4
+    s = ob_fold_row<0x4E>(s);           // quad_perm [2,3,0,1]
+    s = ob_fold_row<0xB1>(s);           // quad_perm [1,0,3,2]
+    const int row = lane / 16, blk = ((row & 1) << 1) | (row >> 1);
+    const int64_t left = rem - static_cast<int64_t>(blk) * kSignBlockElems;            // the key's elements from this lane's block on
+    const float len = static_cast<float>(left >= kSignBlockElems ? kSignBlockElems : (left > 0 ? static_cast<int>(left) : 1));
+    s = __fdiv_rn(s, len);
+    if (lane % 16 == 0 && (FULL || left > 0)) st1(scales + blk, s);
+    if (lane < kObSteps && (FULL || kWaveLanes * lane < rem)) st1(words + lane, (static_cast<uint64_t>(whi) << 32) | wlo);
+    if constexpr (BASE) {
+#pragma unroll
+        for (int j = 0; j < kObBlocks; ++j) {
+            // block j's scale out of the first lane of its row, into every lane
+            const float sj = ob_f32(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ob_bits(s)), 16 * (((j & 1) << 1) | (j >> 1)))));
+#pragma unroll
+            for (int k = kObPer * j; k < kObPer * (j + 1); ++k)
+                if (FULL || kWaveLanes * k + lane < rem)
+                    st1(base + kWaveLanes * k + lane, __fadd_rn(b[k], __builtin_copysignf(sj, d[k])));
+        }
+    }
+}
+
+template <int SD, bool BASE>
+__global__ __launch_bounds__(kBlock) void onebit_pack_kernel(const flame_segment* __restrict__ segs, int n_segs, int64_t n_chunks) {
+    using T = typename Tr<SD>::T;
+    static_assert(LaneChunk<flame_segment, kObSteps>::CE == kObChunk, "a chunk is four tiles");
+    static_assert(!BASE || SD == FLAME_F32, "a base goes with an fp32 source");
+    const int64_t chunk = blockIdx.x;
+    if (chunk >= n_chunks) return;
+    const LaneChunk<flame_segment, kObSteps> lc(segs, n_segs, chunk);
+    const flame_segment sg = lc.sg;
+    const int t = static_cast<int>(threadIdx.x), lane = t % kWaveLanes;
+    const int wave = __builtin_amdgcn_readfirstlane(t / kWaveLanes);
+    const int64_t tile = (chunk - sg.chunk_begin) * kObChunk + static_cast<int64_t>(wave) * kObTile;
+    if (tile >= sg.numel) return;                       // the whole wave: an idle chunk, or the key ends before this tile
+    const int64_t rem = sg.numel - tile;
+    const T* src = reinterpret_cast<const T*>(sg.in) + tile;
+    float* base = BASE ? reinterpret_cast<float*>(sg.m) + tile : nullptr;
+    uint64_t* words = reinterpret_cast<uint64_t*>(sg.out) + tile / kWaveLanes;
+    float* scales = reinterpret_cast<float*>(sg.cur_out) + tile / kSignBlockElems;
+    if (rem >= kObTile)
+        onebit_tile<SD, BASE, true>(src, base, words, scales, rem, lane);
+    else
+        onebit_tile<SD, BASE, false>(src, base, words, scales, rem, lane);
+}
+
 // ---------------------------------------------------------------- trimmed mean / median
 // Coordinate-wise trimmed mean (Yin et al., ICML 2018; flame has no counterpart file): per element
 // the k smallest and the k largest of the n client values are dropped, the other n - 2k are summed
@@ -5781,6 +5908,35 @@ int flame_agg_reduce_sign(int agg_dtype, unsigned flags, const flame_segment* se
     hipLaunchKernelGGL((agg_reduce_sign_kernel<kSignUnroll>), dim3(static_cast<unsigned>(n_chunks)), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), segs, n_segs, reinterpret_cast<const uint64_t*>(bits),
                        reinterpret_cast<const uint64_t*>(scales), n_clients, rates32, n_chunks);
+    return check_launch(who);
+}
+
+// The sign packer (the 1-bit downlink): outside the launch-branch table, one instantiation per source dtype
+// and one more for fp32 with a base.  Every refusal comes before the first HIP call.
+int64_t flame_onebit_pack_chunk_elems(void) { return kObChunk; }
+
+int flame_onebit_pack(int src_dtype, unsigned flags, const flame_segment* segs, int32_t n_segs, int64_t n_chunks,
+                      void* stream) {
+    const char* const who = "flame_onebit_pack";
+    if (!is_f32_or_16(src_dtype))
+        return set_err(FLAME_ENOTSUP, "%s: source dtype %d is not supported (f32, bf16 or f16 only)", who, src_dtype);
+    if (int rc = need_segs(who, segs, n_segs)) return rc;
+    if (reinterpret_cast<uintptr_t>(segs) % 8)
+        return set_err(FLAME_EINVAL, "%s: the segment table is not 8-byte aligned (segments are 64-bit words)", who);
+    if (int rc = check_chunks(n_chunks)) return set_err(rc, "%s: n_chunks out of range: %lld", who, (long long)n_chunks);
+    if (int rc = check_flags(who, flags, FLAME_ONEBIT_BASE)) return rc;
+    const bool base = flags & FLAME_ONEBIT_BASE;
+    if (base && src_dtype != FLAME_F32)
+        return set_err(FLAME_ENOTSUP, "%s: FLAME_ONEBIT_BASE with source dtype %d is not supported (an fp32 base goes with an f32 source)",
+                       who, src_dtype);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(static_cast<unsigned>(n_chunks)), block(kBlock);
+    if (base)
+        hipLaunchKernelGGL((onebit_pack_kernel<FLAME_F32, true>), grid, block, 0, st, segs, n_segs, n_chunks);
+    else
+        dispatch<FLAME_F32, FLAME_BF16, FLAME_F16>(src_dtype, [&](auto sd) {
+            hipLaunchKernelGGL((onebit_pack_kernel<decltype(sd)::value, false>), grid, block, 0, st, segs, n_segs, n_chunks);
+        });
     return check_launch(who);
 }
 

@@ -212,10 +212,21 @@ class MessageEncoder:
     the factors miss competes again in the next message.  The trainer applies ``lowrank.apply_(model,
     msg["weights"])``.  Unlike the sparse downlink, its copy is NOT bit for bit the base: ``U @ V`` on its CPU and
     on the matrix cores round differently, within the any-order fp32 bound of a length-r dot product per message,
-    and the differences add up until the next dense message.  :meth:`reset` is the way to re-synchronise."""
+    and the differences add up until the next dense message.  :meth:`reset` is the way to re-synchronise.
+
+    ``sign`` (default False: nothing changes; not together with ``mx``, ``sparse`` or ``lowrank``) is the 1-bit
+    downlink, of the sparse downlink's shape: the first message, the first after :meth:`reset` and any message
+    whose structure changes are dense, and the encoder takes its fp32 device base there, of every fp32 key of at
+    least ``sign_min_numel`` elements.  Every later message sends ``engine.sign_compress(weights,
+    sign_min_numel, base=...)``: a :class:`flame_amd.sign.SignWeights` of the signs of the change since the
+    base with one mean magnitude per 256 elements, 0.035 of the fp32 bytes, packed by one flame_onebit_pack
+    launch; the base advances by exactly what was sent, so what the signs miss stays in ``weights - base`` and
+    is sent again (error feedback on the server's side).  A trainer that applies every message with
+    ``sign.apply_(model, msg["weights"])`` holds, in every compressed key, bit for bit the encoder's base."""
 
     def __init__(self, ring: int = 2, pin: bool = True, mx=None, mx_min_numel: int = 0, sparse=None,
-                 sparse_min_numel: int = 0, lowrank=None, lowrank_min_numel: int = 0, lowrank_seed: int = 0):
+                 sparse_min_numel: int = 0, lowrank=None, lowrank_min_numel: int = 0, lowrank_seed: int = 0,
+                 sign: bool = False, sign_min_numel: int = 0):
         if mx is not None:
             from . import mx as _mx
             if mx not in _mx.FORMATS:
@@ -230,6 +241,9 @@ class MessageEncoder:
                 raise ValueError("flame_amd.egress: mx, sparse and lowrank are three downlinks; choose one")
             if isinstance(lowrank, bool) or not isinstance(lowrank, int) or not 1 <= lowrank <= 32:
                 raise ValueError(f"flame_amd.lowrank_factor: rank {lowrank!r} is not an integer in 1 .. 32")
+        if sign and (mx is not None or sparse is not None or lowrank is not None):
+            raise ValueError("flame_amd.egress: mx, sparse, lowrank and sign are four downlinks; choose one")
+        self.sign, self.sign_min_numel = bool(sign), sign_min_numel
         self.sparse, self.sparse_min_numel = sparse, sparse_min_numel
         self.lowrank, self.lowrank_min_numel, self.lowrank_seed = lowrank, lowrank_min_numel, lowrank_seed
         self._base, self._held, self._q = None, None, None
@@ -259,6 +273,9 @@ class MessageEncoder:
         if self.lowrank is not None and isinstance(message, dict) and isinstance(message.get("weights"), dict):
             message = dict(message)
             message["weights"] = self._factorised(message["weights"])
+        if self.sign and isinstance(message, dict) and isinstance(message.get("weights"), dict):
+            message = dict(message)
+            message["weights"] = self._signed(message["weights"])
         # a fresh random mark per message: no bytes of the message itself can pass for a placeholder
         pieces, total = _layout(message, os.urandom(_MARK_LEN))
         buf = self._buffer(total)
@@ -285,7 +302,7 @@ class MessageEncoder:
         return bytes(self.encode(message))
 
     def reset(self) -> None:
-        """Forget the sparse or low-rank downlink's base (and the low-rank downlink's right factors): the next
+        """Forget the sparse, low-rank or sign downlink's base (and the low-rank downlink's right factors): the next
         message sends the weights as they are."""
         self._base, self._held, self._q = None, None, None
 
@@ -320,6 +337,14 @@ class MessageEncoder:
         sent, self._q = engine.lowrank_factor(weights, self.lowrank, self.lowrank_min_numel, base=self._base, q=self._q,
                                               seed=self.lowrank_seed)
         return sent
+
+    def _signed(self, weights):
+        """The sign downlink's weights: the dict itself while there is no base for its structure, else the signs
+        and block scales of the change against the base (the base advances by what they say)."""
+        from . import engine
+        if self._rebased(weights, "MessageEncoder(sign=)", self.sign_min_numel, 0):
+            return weights
+        return engine.sign_compress(weights, self.sign_min_numel, base=self._base)
 
 _default = None
 

@@ -4,7 +4,7 @@ and launches the native kernels (``include/flame_amd.h``) on torch's current str
 Pure-Python planning (``plan``, ``plan_hier``, ``plan_feddyn``, ``rate32``,
 ``chunk_elems``) needs no GPU and is unit-tested on CPU; the launchers (``reduce_``,
 ``fedopt_reduce_adapt_``, ``fedopt_chain_``, ``scale_add_``, ``hier_fedbuff_``,
-``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``topk``, ``lowrank_factor``, ``synth_fill_``) need the native
+``feddyn_round_``, ``update_stats``, ``trimmed_mean``, ``noise_fill``, ``mx_quantize``, ``topk``, ``lowrank_factor``, ``sign_compress``, ``synth_fill_``) need the native
 library and a HIP device.
 
 Every launcher takes ONE path to the library: tensors grouped per dtype (``by_dtype``),
@@ -1800,6 +1800,113 @@ def lowrank_factor(weights, rank: int, min_numel: int = 0, *, base, q=None, seed
         lowrank_factor_(ws, bases, qs, [out[k] for k in keys], [right[k] for k in keys])
         _LowRankRound({k: b.view(shapes[k]) for k, b in zip(keys, bases)}, keys, [0], [(sent, 1.0)], device).reduce()
     return sent, q_next
+
+
+# ------------------------------------------------------------------ the sign packer: 1-bit compression on the device
+def plan_sign_pack(segs: Sequence[Seg], chunk: Optional[int] = None):
+    """[segments (10 words)] -> (meta, n_chunks): the metadata block of one flame_onebit_pack launch (no GPU
+    needed).  A segment's ``inp`` is the source, ``out`` the bits, ``cur_out`` the scales, ``m`` the base or 0;
+    every segment starts a chunk, so a word or a block never straddles two keys; one of 0 elements has none."""
+    if not segs:
+        raise ValueError("flame_amd.plan_sign_pack: empty segment list")
+    b = _Block(chunk or int(N.lib().flame_onebit_pack_chunk_elems()))
+    head = np.zeros((len(segs), SEG_WORDS), dtype=np.uint64)
+    for i, s in enumerate(segs):
+        if s.out % 8:
+            raise ValueError("flame_amd.plan_sign_pack: a bits pointer is not 8-byte aligned (the kernel stores 64-bit words)")
+        head[i] = (s.out, s.inp, 0, s.cur_out, s.m, 0, s.numel, b.chunk_begin(s.numel), 0, 0)
+    b.add("segs", head)
+    return b.finish()
+
+
+def sign_pack_(srcs: List[torch.Tensor], bits: List[torch.Tensor], scales: List[torch.Tensor],
+               bases: Optional[List[torch.Tensor]] = None) -> None:
+    """bits[s], scales[s] = the sign bits and fold-order block scales of srcs[s], written in place (kernel:
+    flame_onebit_pack; DESIGN.md §2 "the sign packer"): ``sign.compress_tensor(src, fold=True)`` bit for bit.
+    ``srcs`` are contiguous device tensors of f32 / bf16 / f16 on one device, ``bits[s]`` contiguous uint8
+    device tensors of ``8 * ceil(numel / 64)`` bytes starting on 8 bytes, ``scales[s]`` contiguous fp32 device
+    tensors of ``ceil(numel / 256)`` elements.  With ``bases`` (fp32 sources only; contiguous fp32 device tensors
+    of the sources' numels) the bits and scales are those of ``src - base`` and every base advances by what
+    was sent, ``base += sign.dequantize_tensor(bits, scales)``.  One flame_onebit_pack launch per source dtype
+    on torch's current stream; nothing is read back."""
+    if not (len(srcs) == len(bits) == len(scales)) or (bases is not None and len(bases) != len(srcs)):
+        raise ValueError("flame_amd.sign_pack_: one bits tensor and one scales tensor per source (and one base, if any)")
+    if not srcs:
+        return
+    device = srcs[0].device
+    if device.type != "cuda":
+        raise RuntimeError("flame_amd.sign_pack_: tensors must live on the GPU (no CPU fallback)")
+    L = N.lib()
+    keep = []
+    for code, idx in by_dtype(range(len(srcs)), lambda s: srcs[s].dtype).items():
+        dt = srcs[idx[0]].dtype
+        if dt not in sign.COMPRESSED_FROM:
+            raise TypeError(f"flame_amd.sign_pack_: {dt} keys are not compressed (f32, bf16, f16 only)")
+        if bases is not None and dt != torch.float32:
+            raise TypeError(f"flame_amd.sign_pack_: a base goes with an fp32 source, not {dt}")
+        segs = []
+        for s in idx:
+            n = srcs[s].numel()
+            want = [(srcs[s], dt, n), (bits[s], torch.uint8, 8 * -(-n // sign.WORD)), (scales[s], torch.float32, -(-n // sign.BLOCK))]
+            if bases is not None:
+                want.append((bases[s], torch.float32, n))
+            for t, tdt, tn in want:
+                if not (t.is_contiguous() and t.device == device):
+                    raise ValueError("flame_amd.sign_pack_: contiguous tensors on one device")
+                if t.dtype != tdt or t.numel() != tn:
+                    raise ValueError(f"flame_amd.sign_pack_: a key of {n} elements needs {tn} of {tdt} here, "
+                                     f"got {t.numel()} of {t.dtype}")
+            if n:
+                segs.append(Seg(n, out=bits[s].data_ptr(), inp=srcs[s].data_ptr(), cur_out=scales[s].data_ptr(),
+                                m=bases[s].data_ptr() if bases is not None else 0))
+        if not segs:
+            continue
+        meta, n_chunks = plan_sign_pack(segs)
+        # the source read once, the base read and written, the words and the scales written
+        nbytes = sum(sg.numel * (ITEMSIZE[code] + (8 if bases is not None else 0)) + 8 * -(-sg.numel // sign.WORD)
+                     + 4 * -(-sg.numel // sign.BLOCK) for sg in segs)
+        flags = N.FLAME_ONEBIT_BASE if bases is not None else 0
+        _launch("flame_onebit_pack", nbytes, device, keep, meta,
+                lambda b: L.flame_onebit_pack(code, flags, b, len(segs), n_chunks, _stream_ptr(device)))
+    _keepalive(keep + list(srcs) + list(bits) + list(scales) + list(bases or ()), device)
+
+
+def sign_compress(weights, min_numel: int = 0, *, base=None, device=None) -> "sign.SignWeights":
+    """``sign.compress(weights, min_numel, fold=True)`` computed on the device: the same keys are compressed
+    (fp32 / bf16 / f16 of at least ``max(min_numel, 1)`` elements) to the same bits and the same fold-order
+    scales (DESIGN.md §2 "the sign packer"); every other key passes through as the object it is.  The outputs
+    are new device tensors.  A host-resident or strided source is staged to the device first.
+
+    With ``base`` (``{key: contiguous fp32 device tensor of the key's numel}``, one per compressed key) only
+    fp32 keys are compressed, the bits and scales are those of ``weights[key] - base[key]``, and the bases are
+    updated in place: ``base += sign.dequantize(sent)``, one fp32 add per element.  A 16-bit key with a base
+    raises TypeError, a compressed key without one KeyError."""
+    device = _hip_device(device, "sign_compress", prefer=weights)
+    out, scales, shapes = collections.OrderedDict(), {}, {}
+    srcs, bits, bases = [], [], []
+    for key, v in weights.items():
+        out[key] = v
+        if not (isinstance(v, torch.Tensor) and v.dtype in sign.COMPRESSED_FROM and v.numel() >= max(min_numel, 1)):
+            continue
+        if base is not None:
+            if key in base and v.dtype != torch.float32:
+                raise TypeError(f"flame_amd.sign_compress: key {key!r} is {v.dtype}; a base goes with an fp32 key")
+            if v.dtype != torch.float32:
+                continue
+            if key not in base:
+                raise KeyError(f"flame_amd.sign_compress: no base for key {key!r}")
+            if not (base[key].is_contiguous() and base[key].dtype == torch.float32 and base[key].numel() == v.numel()):
+                raise ValueError(f"flame_amd.sign_compress: the base of key {key!r} must be a contiguous fp32 tensor of "
+                                 f"{v.numel()} elements")
+            bases.append(base[key])
+        n = v.numel()
+        srcs.append(_staged(v.detach(), device).view(-1))
+        out[key] = torch.empty(8 * -(-n // sign.WORD), dtype=torch.uint8, device=device)
+        scales[key] = torch.empty(-(-n // sign.BLOCK), dtype=torch.float32, device=device)
+        shapes[key] = tuple(v.shape)
+        bits.append(out[key])
+    sign_pack_(srcs, bits, [scales[k] for k in scales], [b.view(-1) for b in bases] if base is not None else None)
+    return sign.SignWeights(out, scales, shapes)
 
 
 # ------------------------------------------------------------------ dict-level helpers used by the optimizers

@@ -54,6 +54,8 @@
  *                               downlink, by flame_amd.mx.quantize's rule)
  *   flame_topk_select           (no reference counterpart: exact top-k by magnitude of each key as ascending
  *                               index / value pairs, optionally of the change against a base it advances)
+ *   flame_onebit_pack           (no reference counterpart: each key as sign bits and one fp32 scale per 256,
+ *                               optionally of the change against a base it advances by what it sends)
  *   flame_agg_trimmed           (no reference counterpart: the coordinate-wise trimmed mean / median
  *                               of Yin et al., ICML 2018, over the same tables)
  *   flame_agg_select            (no reference counterpart: the same trimmed mean / median for any
@@ -515,6 +517,38 @@ int64_t flame_sign_chunk_elems(void);
 int flame_agg_reduce_sign(int agg_dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
                           int64_t n_chunks, const void *const *bits, const void *const *scales,
                           int32_t n_clients, const float *rates32, void *stream);
+
+/*
+ * The sign packer: each key as one bit per element and one fp32 scale per block of 256 -- the device-side
+ * producer of flame_amd.sign's format and, with a base, the 1-bit downlink
+ * (flame_amd.egress.MessageEncoder(sign=True)).  DESIGN.md §2, "the sign packer", is the contract.
+ *   src_dtype : FLAME_F32, FLAME_BF16 or FLAME_F16: every segment's in (a 16-bit source is widened exactly).
+ *   flags     : 0 or FLAME_ONEBIT_BASE (FLAME_F32 only): every segment's m is its base.
+ *   segs      : in = the source x, numel elements; out = the bits, 8 * ceil(numel / 64) bytes, 8-BYTE ALIGNED;
+ *               cur_out = the scales, fp32 [ceil(numel / 256)]; m = the base, fp32 [numel] (read and written
+ *               only under FLAME_ONEBIT_BASE); chunk_begin counts chunks of flame_onebit_pack_chunk_elems() =
+ *               4,096 source elements (a wave owns a tile of 1,024: 16 words, 4 scales) and every segment
+ *               starts a chunk; a segment of 0 elements has none.  Sources and bases move in elements, so
+ *               FLAME_SEG_UNALIGNED says nothing here.  No other field is read.  Device memory.
+ * Per segment, with d[e] = f32(x[e]) (under FLAME_ONEBIT_BASE f32(x[e] - m[e]), one IEEE subtract):
+ *   bit e     = the sign bit of d[e] (-0.0 gives 1, x == m gives 0), bit e % 64 of 64-bit word e / 64; the
+ *               last word is written whole, its pad bits 0.
+ *   scale j   = the fold-order sum of block j's 256 magnitudes |d| (the last block zero-padded; a = a[:h] +
+ *               a[h:] for h = 128, 64, .., 1, each one fp32 add, no FMA, denormals kept) divided by the
+ *               block's true length as an fp32, one IEEE round-to-nearest division.  A block holding an inf
+ *               has scale inf, one holding a NaN has scale NaN; the bit of a NaN d is not part of the contract.
+ *   m[e]      = f32(m[e] + (bit e ? -scale : +scale)) under FLAME_ONEBIT_BASE, for every element of the key.
+ * Nothing at or past numel is loaded or stored, no word at or past ceil(numel / 64) and no scale at or past
+ * ceil(numel / 256) is stored.  One launch; equal launches give equal bytes (no atomic).
+ * Refusals, each before any HIP call and named in flame_last_error: a source dtype other than those above, or
+ * FLAME_ONEBIT_BASE with a 16-bit source, is FLAME_ENOTSUP; a NULL segment table or one that is not 8-byte
+ * aligned, n_segs <= 0, n_chunks outside [1, 2^31) or an unknown flag is FLAME_EINVAL.
+ * Device tables only.  Not a launch branch of flame_launch_branches().
+ */
+#define FLAME_ONEBIT_BASE 1u
+int64_t flame_onebit_pack_chunk_elems(void);
+int flame_onebit_pack(int src_dtype, unsigned flags, const flame_segment *segs, int32_t n_segs,
+                      int64_t n_chunks, void *stream);
 
 /*
  * Low-rank updates into an fp32 aggregate (the contract is this project's own, DESIGN.md §2, "the low-rank
